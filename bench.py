@@ -7,6 +7,11 @@ are synthetic (Zipf(1.0) flowIds, U{1..32} thresholds, 1 % prioritized), generat
 the timed region and resident in HBM. With N > 1 ranks each step also runs the node-wide metric
 rollup over RCCL (all-reduce of pass/block totals, all-gather of per-flowId QPS snapshots).
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the result line.
+`--dump-outputs DIR` also writes the results of the last timed step as DIR/<field>.npy (the inputs are seeded, so
+two builds can be compared output for output). `--full` adds what takes runs of its own: the per-phase device
+times (phases_ms), the host-buffer path (end_to_end) and the oracle on the host threads (cpu_baseline).
+
 Prints one JSON line (rank 0). See DESIGN.md §Measurement for the roofline bytes.
 """
 import argparse
@@ -75,6 +80,24 @@ class ShardWorkload:
         words[:, 0] = ts
         words[:, 1] = (acq << 32) | key | prio
         return words.view(torch.uint8).reshape(-1)
+
+
+def dump_outputs(out_dir, records, prefix="", suffix="", max_rows=1_000_000):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one float64 array per field of
+    the structured array `records` as out_dir/<prefix><field><suffix>.npy (every field is an integer of at most 53
+    bits, so float64 holds it exactly). An output of more than max_rows rows is sampled at max_rows fixed indices
+    (seeded, ascending, the same for every run of the same size); the indices go to <prefix>sample_index<suffix>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(records)
+    if n > max_rows:
+        idx = np.sort(np.random.default_rng(20240607).choice(n, size=max_rows, replace=False))
+        records = records[idx]
+    else:
+        idx = np.arange(n)
+    np.save(os.path.join(out_dir, f"{prefix}sample_index{suffix}.npy"), idx.astype(np.float64))
+    for name in records.dtype.names:
+        np.save(os.path.join(out_dir, f"{prefix}{name}{suffix}.npy"),
+                np.ascontiguousarray(records[name]).astype(np.float64))
 
 
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "r06_c3_pmc_summary.json")
@@ -223,6 +246,8 @@ def node_main(args):
     for d in range(N):
         torch.cuda.synchronize(d)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[(total_steps - 1) % 2].cpu().numpy().view(abi.RES_DTYPE))
     last = batches[-1].view(torch.int64).reshape(-1, 2)[:, 1] & 0x7FFFFFFF
     touched = int(torch.unique(last).numel())
     ms_per_step = elapsed * 1000.0 / args.steps
@@ -392,6 +417,12 @@ def c5_main(args, rank, world, dev, coll, one_dev):
     else:
         elapsed, decided = elapsed, float(stats[1].item())
 
+    if args.dump_outputs:  # the last timed step's decisions of this rank and the node's merged metric rows of its second
+        suffix = f".rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, outs[-1].cpu().numpy().view(abi.LOCAL_RES_DTYPE), suffix=suffix)
+        rows = merged[-1].cpu().numpy().copy().view(abi.METRIC_NODE_DTYPE).reshape(-1)
+        dump_outputs(args.dump_outputs, rows, prefix="metric_", suffix=suffix, max_rows=400_000)
+
     parity = None
     if check:  # every decision of this rank, then the merged rows of every second against the node replay
         bad = 0
@@ -480,8 +511,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--flows", type=int, default=1_000_000)
     ap.add_argument("--requests", type=int, default=16_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--e2e-batches", type=int, default=16, help="host-buffer batches for the end-to-end figure (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="c3: after the timed steps also measure what the headline does not need: the per-phase device "
+                         "times of one batch (phases_ms), the host-buffer path (end_to_end) and the oracle on the host "
+                         "threads (cpu_baseline). Off by default: a plain run sets up, warms up, times --steps steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the results of the last timed step (what the caller of the timed "
+                         "path receives) as DIR/<field>.npy, float64; a fixed seeded sample of the rows of a large "
+                         "output, its indices in DIR/sample_index.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="leave the cpu_baseline out (c3: only measured with --full)")
+    ap.add_argument("--e2e-batches", type=int, default=16,
+                    help="with --full: host-buffer batches for the end-to-end figure (0: skip)")
     ap.add_argument("--limiter-qps", type=float, default=0.0,
                     help="namespace GlobalRequestLimiter maxAllowedQps (SURVEY §8d C3's second run: 1e12 exercises the "
                          "pre-pass without rejecting); 0: limiter off, the headline configuration")
@@ -536,8 +577,11 @@ def main():
     eng.load_rules(wl.rules)
 
     total_steps = args.warmup + args.steps
-    n_phase = 2  # extra batches through the synchronous path for the per-phase device times
-    batches = [wl.batch(b) for b in range(total_steps + n_phase)]
+    n_phase = 2 if args.full else 0  # extra batches through the synchronous path for the per-phase device times
+    # Batches are generated before they are timed and stay resident in HBM, at most `chunk` of them (64 GiB) at a
+    # time: a run of more steps than that stops the clock between chunks while the next one is generated.
+    chunk = max(8, (64 << 30) // (args.requests * REQ_B))
+    batches = {}
     # one output buffer per batch in flight (the pipeline keeps up to 4 batches enqueued)
     outs = [torch.empty(args.requests * RES_B, dtype=torch.uint8, device=dev) for _ in range(4)]
     snaps = [torch.empty((wl.K, 2), dtype=torch.float64, device=dev) for _ in range(2)]
@@ -564,41 +608,58 @@ def main():
             eng.wait(pend[0])
             rollup.run(snaps[pend[1] % 2].to(coll))
 
-    run_steps(0, args.warmup)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    run_steps(args.warmup, total_steps)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = 0.0
+    for c0 in range(0, total_steps, chunk):
+        c1 = min(c0 + chunk, total_steps)
+        batches.clear()
+        for b in range(c0, c1):
+            batches[b] = wl.batch(b)
+        torch.cuda.synchronize()
+        if c0 < args.warmup:
+            run_steps(c0, min(c1, args.warmup))
+        if c1 > args.warmup:
+            if world > 1:
+                dist.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run_steps(max(c0, args.warmup), c1)
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            elapsed += time.perf_counter() - t0
     t_max = torch.tensor([elapsed], dtype=torch.float64, device=coll)
     if world > 1:
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
     elapsed = float(t_max.item())
 
-    # per-phase device time of one batch on its own (synchronous path, HIP events on the call's stream; untimed)
-    eng.enable_stats(True)
-    phase = {"sort_ms": 0.0, "walk_ms": 0.0, "total_ms": 0.0}
-    stream = torch.cuda.current_stream(dev)
-    for b in range(total_steps, total_steps + n_phase):
-        eng.decide_device(batches[b].data_ptr(), args.requests, outs[0].data_ptr(), stream.cuda_stream)
-        st = eng.stats()
-        for k in phase:
-            phase[k] += st[k] / n_phase
-        long_segments = st["long_segments"]
-    eng.enable_stats(False)
+    if args.dump_outputs:  # the last timed step's results, as its caller finds them in the buffer it passed
+        got = outs[(total_steps - 1) % 4].cpu().numpy().view(abi.RES_DTYPE)
+        dump_outputs(args.dump_outputs, got, suffix=f".rank{rank}" if world > 1 else "")
+
+    phases = None
+    if args.full:
+        # per-phase device time of one batch on its own (synchronous path, HIP events on the call's stream; untimed)
+        for b in range(total_steps, total_steps + n_phase):
+            batches[b] = wl.batch(b)
+        eng.enable_stats(True)
+        phase = {"sort_ms": 0.0, "walk_ms": 0.0, "total_ms": 0.0}
+        stream = torch.cuda.current_stream(dev)
+        for b in range(total_steps, total_steps + n_phase):
+            eng.decide_device(batches[b].data_ptr(), args.requests, outs[0].data_ptr(), stream.cuda_stream)
+            st = eng.stats()
+            for k in phase:
+                phase[k] += st[k] / n_phase
+            long_segments = st["long_segments"]
+        eng.enable_stats(False)
+        phases = {"device_total_one_batch_unpipelined": phase["total_ms"], "sort": phase["sort_ms"],
+                  "walk": phase["walk_ms"], "long_segments": long_segments}
 
     # touched flowIds of the last batch (for the algorithmic byte count)
-    last = batches[-1].view(torch.int64).reshape(-1, 2)[:, 1] & 0x7FFFFFFF
+    last = batches[max(batches)].view(torch.int64).reshape(-1, 2)[:, 1] & 0x7FFFFFFF
     touched = int(torch.unique(last).numel())
     ms_per_step = elapsed * 1000.0 / args.steps
     value = args.requests * world / (elapsed / args.steps)
     b_alg = args.requests * (REQ_B + RES_B) + touched * (STATE_B + RULE_B)
-    walk_ms = phase["walk_ms"]
-    total_ms = phase["total_ms"]
     step_gbs = b_alg / (ms_per_step / 1000.0) / 1e9  # pipelined: algorithmic bytes per batch over the step time
     result = {
         "metric": "flow decisions/sec (node) at 1M flowIds, 1/2/4/8 GPU; HBM GB/s vs peak",
@@ -623,12 +684,12 @@ def main():
                      "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": step_gbs / HBM_PEAK_GBS,
                      "traffic": pmc_traffic(), "traffic_source": os.path.relpath(PMC_SUMMARY, ROOT),
                      "algorithmic_bytes_per_step": b_alg, "touched_flow_ids": touched},
-        "phases_ms": {"device_total_one_batch_unpipelined": total_ms, "sort": phase["sort_ms"], "walk": walk_ms,
-                      "long_segments": long_segments},
     }
-    if world == 1 and args.e2e_batches > 0:
+    if phases is not None:
+        result["phases_ms"] = phases
+    if args.full and world == 1 and args.e2e_batches > 0:
         result["end_to_end"] = end_to_end(eng, wl, total_steps + n_phase, args.e2e_batches, args.requests)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.flows, args.requests)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -19,7 +19,7 @@ if [ "$MODE" = all ] || [ "$MODE" = test ]; then
   step smoke 200 python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step bench 400 python -u bench.py --steps 10 --warmup 3
+  step bench 400 python -u bench.py --full --steps 10 --warmup 3
 fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then
   step rocprof 400 rocprofv3 --kernel-trace --stats -T -d gpurun_out/prof -o run --output-format csv -- python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline --e2e-batches 0
