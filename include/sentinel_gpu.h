@@ -829,6 +829,75 @@ int sg_node_conc_decide_batch(sg_node* nd, const sg_conc_req* req, uint64_t n, s
 int sg_node_conc_decide_batch_host(sg_node* nd, const sg_conc_req* req, uint64_t n, sg_conc_result* out);
 int sg_node_conc_expire(sg_node* nd, int64_t now_ms, const uint8_t* client_online, uint32_t n_clients, uint64_t* removed);
 int sg_node_conc_read_state(sg_node* nd, uint32_t key, int32_t* now_calls, uint64_t* live_tokens);
+/* The local slot chain over the node: StatisticSlot → FlowSlot → DegradeSlot (sg_local_*) for a multi-GPU node from one
+ * handle — the sharded deployment described at sg_local_owners, composed inside the library. Every shard loads the whole
+ * rule set under the node's resource indices and decides the entries and exits of the resources it owns (a key group on
+ * one owner); it never sees events of other resources, whose state stays empty and yields no rows. The front handle
+ * carries no local traffic: it is the staging copy of the rules and names the owners. Same conventions as the calls
+ * above: 0 or SG_E_*, the message in sg_node_last_error, pipelined node batches completed first, device buffers on
+ * devices[0], the shards in SG_CLUSTER_NOT_STARTED.
+ *   sg_node_local_load_rules      ← sg_local_load_rules on the front, then on every shard: fresh statistics, so owners
+ *                                   may change freely. A shard that fails leaves the local chain unloaded (load again).
+ *   sg_node_local_load_flow_rules ← sg_local_load_flow_rules (returns the rules kept). The resources keep their
+ *                                   statistics, which live on their owner, so after the node has decided a local batch no
+ *                                   resource may move: rules whose key groups (RELATE references) give any resource
+ *                                   another owner are refused with SG_E_UNSUPPORTED. The check runs on the front before
+ *                                   any shard is touched (the front goes back to the rules in force); before the first
+ *                                   batch every rule set is accepted. n_contexts >= 1 starts before the node's first
+ *                                   batch (SG_E_UNSUPPORTED after it). A shard that fails midway (allocation, device)
+ *                                   leaves the earlier shards on the new rules: load again.
+ *   sg_node_local_set_entry_types ← sg_local_set_entry_types on every shard
+ *   sg_node_local_owner_of        owner shard of a resource
+ *   sg_node_local_decide_batch(_host) ← sg_local_decide_batch over the node, synchronous. Before any shard is touched the
+ *                                   node refuses the batch for everything one handle refuses from the events alone, over
+ *                                   the whole batch (a slice of an unsorted batch can itself be sorted, and spans less
+ *                                   time): timestamps negative, decreasing, or older than the node's previous local batch
+ *                                   (SG_E_TIME); origin outside 0..n_origins (SG_E_INVAL); more than 65536 window periods
+ *                                   (SG_E_UNSUPPORTED); n > max_batch (SG_E_CAPACITY); null buffers, rules not loaded
+ *                                   (SG_E_INVAL). A batch refused so leaves every shard unchanged. The events are then
+ *                                   split stably by owner on the device (arrival order kept within a shard; an event
+ *                                   whose resource index is not below the resource count goes to shard 0, which answers
+ *                                   it as one handle does), every shard with work decides its slice concurrently (peer
+ *                                   copies for shards off devices[0]), and the results are gathered into caller order:
+ *                                   they equal one handle deciding the batch. A failure inside a shard — SG_E_DEVICE,
+ *                                   SG_E_NOMEM (its origin / context node pool cannot grow), SG_E_CAPACITY (a table of
+ *                                   its own is full) — is reported after every shard has finished and can leave the
+ *                                   other shards' slices applied: the node's statistics then hold part of the batch, and
+ *                                   its last timestamp does not advance. The same holds for sg_node_cparam_* and
+ *                                   sg_node_conc_* batches, which run their shards the same way.
+ *   sg_node_local_read_state      ← sg_local_read_state of the resource on its owner
+ *   sg_node_local_metrics(_device) ← MetricTimerListener.run for the node, the final table ordered by (timestamp,
+ *                                   resource) as sg_local_metrics gives it (into HOST memory / device memory on
+ *                                   devices[0]): the shards' raw rows are counted, laid out one after the other on
+ *                                   devices[0] and merged on the device — a resource's rows come from its owner (rt = rt /
+ *                                   success when success != 0), the ENTRY_NODE rows of one second are summed over the
+ *                                   shards (rt = Σrt / Σsuccess, kept when isValidMetricNode holds for the sums). When the
+ *                                   sum of the shards' row counts exceeds cap: SG_E_CAPACITY, *n_rows = that sum (a
+ *                                   sufficient capacity: the merged table can only be shorter) and no row is consumed: the
+ *                                   same call with that capacity returns the whole table (a shard with no new row has
+ *                                   then run its empty fetch, whose one effect is currentWindow(now_ms)).
+ *   sg_node_local_merge_rows      the merge alone, on n raw rows (sg_local_metrics_raw_device of every GPU, fetched at one
+ *                                   now_ms) in device memory on devices[0]: what a deployment with one process per GPU
+ *                                   calls after its all-gather. Contract: timestamps multiples of 1000 less than 60 s
+ *                                   apart, one row per (timestamp, resource), resources below the loaded resource count
+ *                                   or SG_ENTRY_NODE_RESOURCE — else SG_E_INVAL and d_out untouched. More rows than cap:
+ *                                   SG_E_CAPACITY, *n_out = the rows needed, d_out untouched. Runs on `stream` and waits
+ *                                   for it.
+ * Out of scope here: sg_slot_ext / ParamFlowSlot arguments over the node (every event is in context 0 with null
+ * args), the embedded token server over the node, a pipelined sg_node_local_enqueue. Cross-device shards are built
+ * (peer copies, per-shard buffers) and unmeasured on hardware, as the rest of the node handle. */
+int sg_node_local_load_rules(sg_node* nd, const sg_local_config* cfg, const sg_local_rule* rules, uint32_t n);
+int sg_node_local_load_flow_rules(sg_node* nd, const sg_local_flow_rule* rules, uint32_t n, int32_t n_origins,
+                                  int32_t n_contexts);
+int sg_node_local_set_entry_types(sg_node* nd, const uint8_t* inbound, uint32_t n);
+int sg_node_local_owner_of(const sg_node* nd, uint32_t resource, uint32_t* shard);
+int sg_node_local_decide_batch(sg_node* nd, const sg_local_event* ev, uint64_t n, sg_local_result* out, void* stream);
+int sg_node_local_decide_batch_host(sg_node* nd, const sg_local_event* ev, uint64_t n, sg_local_result* out);
+int sg_node_local_read_state(sg_node* nd, uint32_t res, int64_t* second, int64_t* borrow, int64_t* minute, int64_t* head);
+int sg_node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* out, uint64_t cap, uint64_t* n_rows);
+int sg_node_local_metrics_device(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, uint64_t cap, uint64_t* n_rows);
+int sg_node_local_merge_rows(sg_node* nd, const sg_metric_node* d_rows, uint64_t n, sg_metric_node* d_out, uint64_t cap,
+                             uint64_t* n_out, void* stream);
 
 /* ---------- token-server wire codec ----------
  * The default token server frames every message with a 2-byte big-endian length

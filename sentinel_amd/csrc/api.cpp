@@ -4777,6 +4777,36 @@ struct sg_node {
     uint64_t snap_cap = 0;
     bool node_key_stale = true;         // the flow rules changed since d_node_key was built
     std::vector<double*> r_snap;        // per shard on another device: its part there
+    // the local slot chain over the node (sg_node_local_*): every shard holds the node's rules under the node's
+    // resource indices and decides the events of the resources it owns; the front is the staging copy of the rules
+    // (it carries no local traffic) and names the owners
+    bool l_loaded = false;
+    sg_local_config l_cfg{};
+    std::vector<sg_local_rule> l_rules;
+    std::vector<sg_local_flow_rule> l_frules;   // the flow rules in force (the front's rollback)
+    bool l_has_frules = false;
+    int32_t l_n_origins = 0, l_n_contexts = 0;
+    std::vector<uint32_t> l_owner;      // [K] owner shard of each resource
+    uint8_t* d_l_owner = nullptr;       // the same on devices[0]
+    int64_t l_last_ts = -1;             // the node's previous local batch (time order)
+    uint64_t l_batches = 0;             // local batches decided since sg_node_local_load_rules
+    sg_local_event* d_lsub_ev = nullptr;   // [max_batch] the shards' slices
+    sg_local_result* d_lsub_out = nullptr; // [max_batch] their results
+    sg_local_event* d_lev_h = nullptr;     // host path
+    sg_local_result* d_lout_h = nullptr;
+    int* d_lerr = nullptr;
+    // the node's metric rows: every shard's raw rows one after the other, merged by k_merge_*
+    unsigned long long* d_mbits = nullptr;  // [60][W]
+    uint32_t* d_mpre = nullptr;             // [60][W]
+    uint32_t m_words = 0;                   // W of the allocation
+    MergeSlots* d_mslots = nullptr;
+    sg_metric_node* d_mrows = nullptr;      // the shards' raw rows (grown on demand)
+    uint64_t mrows_cap = 0;
+    sg_metric_node* d_mout = nullptr;       // the host form's merged table
+    uint64_t mout_cap = 0;
+    std::vector<sg_metric_node*> r_mrows;   // per shard on another device: its rows there
+    std::vector<uint64_t> r_mrows_cap;
+    std::vector<uint64_t*> r_mcnt;          // per shard, on its device: its row count
 };
 
 namespace {
@@ -4967,6 +4997,23 @@ void sg_node_destroy(sg_node* nd) {
     dfree(nd->d_nout_h);
     dfree(nd->d_nvals_h);
     dfree(nd->d_snap);
+    dfree(nd->d_l_owner);
+    dfree(nd->d_lsub_ev);
+    dfree(nd->d_lsub_out);
+    dfree(nd->d_lev_h);
+    dfree(nd->d_lout_h);
+    dfree(nd->d_lerr);
+    dfree(nd->d_mbits);
+    dfree(nd->d_mpre);
+    dfree(nd->d_mslots);
+    dfree(nd->d_mrows);
+    dfree(nd->d_mout);
+    for (size_t g = 0; g < nd->r_mcnt.size(); ++g) {
+        (void)hipSetDevice(nd->devices[g]);
+        dfree(nd->r_mrows[g]);
+        dfree(nd->r_mcnt[g]);
+    }
+    (void)hipSetDevice(nd->devices.empty() ? 0 : nd->devices[0]);
     for (uint32_t* p : nd->d_node_key) dfree(p);
     for (size_t g = 0; g < nd->r_nreq.size(); ++g) {
         (void)hipSetDevice(nd->devices[g]);
@@ -5057,6 +5104,9 @@ int sg_node_create(const sg_config* cfg, const int32_t* devices, uint32_t n_shar
     nd->r_vals.assign(n_shards, nullptr);
     nd->r_vals_cap.assign(n_shards, 0);
     nd->r_snap.assign(n_shards, nullptr);
+    nd->r_mrows.assign(n_shards, nullptr);
+    nd->r_mrows_cap.assign(n_shards, 0);
+    nd->r_mcnt.assign(n_shards, nullptr);
     const uint64_t n = cfg->max_batch;
     if (hipStreamCreateWithFlags(&nd->s0, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&nd->routed, hipEventDisableTiming) != hipSuccess ||
@@ -6035,6 +6085,379 @@ int sg_node_conc_read_state(sg_node* nd, uint32_t key, int32_t* now_calls, uint6
     }
     *live_tokens = live;
     return SG_OK;
+}
+
+}  // extern "C"
+
+// ---- the local slot chain over the node (sg_node_local_*) ----
+//
+// StatisticSlot → FlowSlot → DegradeSlot (SphU.entry / Entry.exit) for a multi-GPU node from one handle: every shard
+// loads the node's whole rule set under the node's resource indices and decides the events of the resources it owns
+// (sg_local_owners: a key group lives on one owner), the node routes a batch by owner with a stable multisplit
+// (node.hip k_lroute_*), and the node's MetricTimerListener table is the shards' raw rows merged on the device
+// (k_merge_*). The front handle carries no local traffic: it is the staging copy of the rules that names the owners.
+
+namespace {
+
+// a remote shard's slice and results reuse the token batches' per-shard buffers (node_slice_alloc)
+static_assert(sizeof(sg_local_event) <= std::max(sizeof(sg_cparam_req), sizeof(sg_conc_req)), "slice buffer");
+static_assert(sizeof(sg_local_result) <= std::max(sizeof(sg_result), sizeof(sg_conc_result)), "result buffer");
+
+// The owners the front's loaded rules give (sg_local_owners over the node's G shards).
+int node_local_owners(sg_node* nd, std::vector<uint32_t>& own) {
+    own.assign(nd->front->ltab.size(), 0);
+    const int rc = sg_local_owners(nd->front, (uint32_t)nd->shards.size(), own.data(), (uint32_t)own.size());
+    return rc ? node_child(nd, nd->front, rc) : SG_OK;
+}
+
+int node_local_set_owners(sg_node* nd, const std::vector<uint32_t>& own) {
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    dfree(nd->d_l_owner);
+    const std::vector<uint8_t> o8(own.begin(), own.end());
+    if (hipMalloc(&nd->d_l_owner, o8.size() ? o8.size() : 1) != hipSuccess) return nfail(nd, SG_E_NOMEM, "owner table");
+    if (!o8.empty()) NHIP(nd, hipMemcpy(nd->d_l_owner, o8.data(), o8.size(), hipMemcpyHostToDevice));
+    nd->l_owner = own;
+    return SG_OK;
+}
+
+// The front back on the rules in force (it holds no statistics: a fresh load of both rule sets).
+void node_local_front_rollback(sg_node* nd) {
+    sg_handle* f = nd->front;
+    if (sg_local_load_rules(f, &nd->l_cfg, nd->l_rules.data(), (uint32_t)nd->l_rules.size()) != SG_OK) return;
+    if (nd->l_has_frules)
+        (void)sg_local_load_flow_rules(f, nd->l_frules.data(), (uint32_t)nd->l_frules.size(), nd->l_n_origins,
+                                       nd->l_n_contexts);
+}
+
+// k_merge_* over `n` raw rows on devices[0] into d_out (device); *n_out rows. Waits for the result.
+int node_merge_rows(sg_node* nd, const sg_metric_node* d_rows, uint64_t n, sg_metric_node* d_out, uint64_t cap,
+                    uint64_t* n_out, hipStream_t stream) {
+    *n_out = 0;
+    MergeArgs m{};
+    m.rows = d_rows;
+    m.n = n;
+    m.K = (uint32_t)nd->l_rules.size();
+    m.W = nd->m_words;
+    m.bits = nd->d_mbits;
+    m.pre = nd->d_mpre;
+    m.st = nd->d_mslots;
+    m.out = d_out;
+    m.cap = cap;
+    NHIP(nd, launch_merge_rows(m, stream));
+    unsigned long long total = 0;
+    int err = 0;
+    NHIP(nd, hipMemcpyAsync(&total, &nd->d_mslots->n_out, sizeof(total), hipMemcpyDeviceToHost, stream));
+    NHIP(nd, hipMemcpyAsync(&err, &nd->d_mslots->err, sizeof(err), hipMemcpyDeviceToHost, stream));
+    NHIP(nd, hipStreamSynchronize(stream));
+    if (err & kMergeBad)
+        return nfail(nd, SG_E_INVAL, "metric rows outside the merge's contract: timestamps multiples of 1000 within one "
+                                     "minute, one row per (timestamp, resource), resources below the resource count");
+    *n_out = total;
+    if (err & kMergeCap) return nfail(nd, SG_E_CAPACITY, "merged metric table larger than the buffer (*n_out rows)");
+    return SG_OK;
+}
+
+// MetricTimerListener.run for the node: the shards' row counts, their raw rows one after the other on devices[0],
+// the merge into d_out (device) or, with h_out, into the node's own table copied out.
+int node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, sg_metric_node* h_out, uint64_t cap,
+                       uint64_t* n_rows) {
+    if (!nd || !n_rows || (!d_out && !h_out && cap)) return SG_E_INVAL;
+    *n_rows = 0;
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    node_drain(nd);
+    const uint32_t G = (uint32_t)nd->shards.size();
+    // 1. every shard's count (a capacity of 0 rows: the count alone, no side effect)
+    for (uint32_t g = 0; g < G; ++g) {
+        sg_handle* h = nd->shards[g];
+        NHIP(nd, hipSetDevice(nd->devices[g]));
+        if (!nd->r_mcnt[g] && hipMalloc(&nd->r_mcnt[g], sizeof(uint64_t)) != hipSuccess)
+            return nfail(nd, SG_E_NOMEM, "metric row counter");
+        const int rc = sg_local_metrics_raw_enqueue(h, now_ms, nullptr, 0, nd->r_mcnt[g], nd->streams[g]);
+        if (rc) {
+            node_sync_shards(nd, g);
+            return node_child(nd, h, rc);
+        }
+    }
+    std::vector<uint64_t> cnt(G, 0);
+    uint64_t sum = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        NHIP(nd, hipSetDevice(nd->devices[g]));
+        NHIP(nd, hipMemcpyAsync(&cnt[g], nd->r_mcnt[g], sizeof(uint64_t), hipMemcpyDeviceToHost, nd->streams[g]));
+        NHIP(nd, hipStreamSynchronize(nd->streams[g]));
+        sum += cnt[g];
+    }
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    *n_rows = sum;  // a sufficient capacity: the merged table can only be shorter (ENTRY_NODE rows of a second collapse)
+    if (sum > cap) return nfail(nd, SG_E_CAPACITY, "metric row buffer too small (*n_rows rows suffice)");
+    if (sum == 0) return SG_OK;
+    if (sum > nd->mrows_cap) {
+        dfree(nd->d_mrows);
+        nd->mrows_cap = 0;
+        if (hipMalloc(&nd->d_mrows, sizeof(sg_metric_node) * sum) != hipSuccess) return nfail(nd, SG_E_NOMEM, "node metric rows");
+        nd->mrows_cap = sum;
+    }
+    if (h_out && sum > nd->mout_cap) {
+        dfree(nd->d_mout);
+        nd->mout_cap = 0;
+        if (hipMalloc(&nd->d_mout, sizeof(sg_metric_node) * sum) != hipSuccess) return nfail(nd, SG_E_NOMEM, "node metric table");
+        nd->mout_cap = sum;
+    }
+    // 2. every shard's rows (its listener state advances), a remote shard's through a buffer on its device
+    std::vector<uint64_t> off(G, 0);
+    uint64_t at = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        off[g] = at;
+        at += cnt[g];
+        if (!cnt[g]) continue;
+        sg_handle* h = nd->shards[g];
+        const bool remote = nd->devices[g] != nd->devices[0];
+        NHIP(nd, hipSetDevice(nd->devices[g]));
+        if (remote && cnt[g] > nd->r_mrows_cap[g]) {
+            dfree(nd->r_mrows[g]);
+            nd->r_mrows_cap[g] = 0;
+            if (hipMalloc(&nd->r_mrows[g], sizeof(sg_metric_node) * cnt[g]) != hipSuccess) {
+                node_sync_shards(nd, g);
+                return nfail(nd, SG_E_NOMEM, "shard metric rows");
+            }
+            nd->r_mrows_cap[g] = cnt[g];
+        }
+        sg_metric_node* dst = remote ? nd->r_mrows[g] : nd->d_mrows + off[g];
+        const int rc = sg_local_metrics_raw_enqueue(h, now_ms, dst, cnt[g], nd->r_mcnt[g], nd->streams[g]);
+        if (rc) {
+            node_sync_shards(nd, g);
+            return node_child(nd, h, rc);
+        }
+    }
+    for (uint32_t g = 0; g < G; ++g) {
+        if (!cnt[g]) continue;
+        NHIP(nd, hipSetDevice(nd->devices[g]));
+        NHIP(nd, hipStreamSynchronize(nd->streams[g]));
+        if (nd->devices[g] != nd->devices[0])
+            NHIP(nd, hipMemcpyPeer(nd->d_mrows + off[g], nd->devices[0], nd->r_mrows[g], nd->devices[g],
+                                   sizeof(sg_metric_node) * cnt[g]));
+    }
+    // 3. the merge
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    uint64_t rows = 0;
+    const int rc = node_merge_rows(nd, nd->d_mrows, sum, h_out ? nd->d_mout : d_out, h_out ? sum : cap, &rows, nd->s0);
+    if (rc) return rc;
+    if (h_out && rows) NHIP(nd, hipMemcpy(h_out, nd->d_mout, sizeof(sg_metric_node) * rows, hipMemcpyDeviceToHost));
+    *n_rows = rows;
+    return SG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sg_node_local_load_rules(sg_node* nd, const sg_local_config* cfg, const sg_local_rule* rules, uint32_t n) {
+    if (!nd || !cfg || (!rules && n)) return SG_E_INVAL;
+    node_drain(nd);
+    const uint32_t G = (uint32_t)nd->shards.size();
+    // the front first (validation; the staging copy that names the owners), then every shard: fresh statistics, so
+    // the owners may change freely. A shard that fails leaves the node's local chain unloaded (load again).
+    int rc = sg_local_load_rules(nd->front, cfg, rules, n);
+    if (rc) return node_child(nd, nd->front, rc);
+    nd->l_loaded = false;
+    nd->l_cfg = *cfg;
+    nd->l_rules.assign(rules, rules + n);
+    nd->l_frules.clear();
+    nd->l_has_frules = false;
+    nd->l_n_origins = nd->l_n_contexts = 0;
+    nd->l_last_ts = -1;
+    nd->l_batches = 0;
+    std::vector<uint32_t> own;
+    rc = node_local_owners(nd, own);
+    if (rc) return rc;
+    for (uint32_t g = 0; g < G; ++g) {
+        rc = sg_local_load_rules(nd->shards[g], cfg, rules, n);
+        if (rc) return node_child(nd, nd->shards[g], rc);
+    }
+    rc = node_local_set_owners(nd, own);
+    if (rc) return rc;
+    // the merge's scratch: (second, resource) bitmap and its prefix counts, the slots' sums
+    const uint32_t W = (n + 63) / 64;
+    if (W > nd->m_words || !nd->d_mbits) {
+        dfree(nd->d_mbits);
+        dfree(nd->d_mpre);
+        nd->m_words = 0;
+        const size_t words = (size_t)kMinuteS * (W ? W : 1);
+        if (hipMalloc(&nd->d_mbits, sizeof(unsigned long long) * words) != hipSuccess ||
+            hipMalloc(&nd->d_mpre, sizeof(uint32_t) * words) != hipSuccess)
+            return nfail(nd, SG_E_NOMEM, "metric merge scratch");
+    }
+    nd->m_words = W;
+    if (!nd->d_mslots && hipMalloc(&nd->d_mslots, sizeof(MergeSlots)) != hipSuccess)
+        return nfail(nd, SG_E_NOMEM, "metric merge scratch");
+    if (!nd->d_lerr && hipMalloc(&nd->d_lerr, sizeof(int)) != hipSuccess) return nfail(nd, SG_E_NOMEM, "error word");
+    nd->l_loaded = true;
+    return SG_OK;
+}
+
+int sg_node_local_load_flow_rules(sg_node* nd, const sg_local_flow_rule* rules, uint32_t n, int32_t n_origins,
+                                  int32_t n_contexts) {
+    if (!nd || (!rules && n)) return SG_E_INVAL;
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    node_drain(nd);
+    // what a shard that has decided a batch refuses, a shard that has not would accept: the node's batches decide
+    if (n_contexts > 0 && nd->l_n_contexts == 0 && nd->l_batches > 0)
+        return nfail(nd, SG_E_UNSUPPORTED, "context tracking (n_contexts >= 1) starts before the node's first local batch");
+    // the front first: validation, and the owners the new key groups give. The resources keep their statistics, so
+    // after a batch none may move: checked here, before any shard is touched.
+    const int kept = sg_local_load_flow_rules(nd->front, rules, n, n_origins, n_contexts);
+    if (kept < 0) return node_child(nd, nd->front, kept);
+    std::vector<uint32_t> own;
+    int rc = node_local_owners(nd, own);
+    if (rc) {
+        node_local_front_rollback(nd);
+        return rc;
+    }
+    if (nd->l_batches > 0 && own != nd->l_owner) {
+        node_local_front_rollback(nd);
+        return nfail(nd, SG_E_UNSUPPORTED, "the new rules' key groups move a resource to another shard after the node "
+                                           "decided a local batch (its statistics live on its owner)");
+    }
+    for (sg_handle* h : nd->shards) {
+        rc = sg_local_load_flow_rules(h, rules, n, n_origins, n_contexts);
+        if (rc < 0) return node_child(nd, h, rc);
+    }
+    rc = node_local_set_owners(nd, own);
+    if (rc) return rc;
+    nd->l_frules.assign(rules, rules + n);
+    nd->l_has_frules = true;
+    nd->l_n_origins = n_origins;
+    nd->l_n_contexts = n_contexts;
+    return kept;
+}
+
+int sg_node_local_set_entry_types(sg_node* nd, const uint8_t* inbound, uint32_t n) {
+    if (!nd || (!inbound && n)) return SG_E_INVAL;
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    node_drain(nd);
+    int rc = sg_local_set_entry_types(nd->front, inbound, n);
+    if (rc) return node_child(nd, nd->front, rc);
+    for (sg_handle* h : nd->shards) {
+        rc = sg_local_set_entry_types(h, inbound, n);
+        if (rc) return node_child(nd, h, rc);
+    }
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    return SG_OK;
+}
+
+int sg_node_local_owner_of(const sg_node* nd, uint32_t resource, uint32_t* shard) {
+    if (!nd || !shard || !nd->l_loaded || resource >= nd->l_owner.size()) return SG_E_INVAL;
+    *shard = nd->l_owner[resource];
+    return SG_OK;
+}
+
+int sg_node_local_decide_batch(sg_node* nd, const sg_local_event* ev, uint64_t n, sg_local_result* out, void* stream) {
+    if (!nd) return SG_E_INVAL;
+    if (n == 0) return SG_OK;
+    if (!ev || !out) return nfail(nd, SG_E_INVAL, "null buffer");
+    if (n > nd->cfg.max_batch) return nfail(nd, SG_E_CAPACITY, "batch larger than max_batch");
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    node_drain(nd);
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    const uint32_t G = (uint32_t)nd->shards.size();
+    if (!nd->d_lsub_ev && (hipMalloc(&nd->d_lsub_ev, sizeof(sg_local_event) * nd->cfg.max_batch) != hipSuccess ||
+                           hipMalloc(&nd->d_lsub_out, sizeof(sg_local_result) * nd->cfg.max_batch) != hipSuccess))
+        return nfail(nd, SG_E_NOMEM, "node local slices");
+    NHIP(nd, hipStreamSynchronize((hipStream_t)stream));  // the caller's batch is in place (synchronous call)
+    // 1. the batch validated as a whole and split by owner: a refused batch reaches no shard
+    LRouteArgs r{};
+    r.ev = ev;
+    r.n = n;
+    r.K = (uint32_t)nd->l_rules.size();
+    r.owner = nd->d_l_owner;
+    r.G = (int)G;
+    r.tile_cnt = nd->d_tile_cnt;
+    r.shard_base = nd->d_base;
+    r.shard_tot = nd->d_base + kMaxShards + 1;
+    r.sub_ev = nd->d_lsub_ev;
+    r.sub_pos = nd->d_sub_pos;
+    r.err = nd->d_lerr;
+    r.last_ts = nd->l_last_ts;
+    r.n_origins = nd->l_n_origins;
+    r.n_wl = std::min(nd->front->l_n_wl, 2);
+    for (int w = 0; w < r.n_wl; ++w) r.wl[w] = nd->front->l_wl[w];
+    NHIP(nd, hipMemsetAsync(nd->d_lerr, 0, sizeof(int), nd->s0));
+    NHIP(nd, launch_lroute(r, nd->s0));
+    int64_t last = 0;
+    NHIP(nd, hipMemcpyAsync(nd->h_base, nd->d_base, sizeof(uint32_t) * (2 * kMaxShards + 1), hipMemcpyDeviceToHost, nd->s0));
+    NHIP(nd, hipMemcpyAsync(nd->h_front_err, nd->d_lerr, sizeof(int), hipMemcpyDeviceToHost, nd->s0));
+    NHIP(nd, hipMemcpyAsync(&last, &ev[n - 1].ts_ms, sizeof(int64_t), hipMemcpyDeviceToHost, nd->s0));
+    NHIP(nd, hipStreamSynchronize(nd->s0));
+    const int err = *nd->h_front_err;
+    if (err & kErrTime)
+        return nfail(nd, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than the node's earlier batches");
+    if (err & kErrPeriods) return nfail(nd, SG_E_UNSUPPORTED, "batch spans more than 65536 window periods");
+    if (err & kErrBounds) return nfail(nd, SG_E_INVAL, "an event's origin id lies outside 0..n_origins");
+    std::vector<uint64_t> base(G), cnt(G), zero(G, 0);
+    for (uint32_t g = 0; g < G; ++g) {
+        base[g] = nd->h_base[g];
+        cnt[g] = nd->h_base[kMaxShards + 1 + g];
+    }
+    // 2. every shard with work decides its slice (its own host thread and stream; peer copies off devices[0])
+    int rc = node_run_shards(nd, base, cnt, zero, zero, sizeof(sg_local_event), sizeof(sg_local_result), nd->d_lsub_ev,
+                             nd->d_lsub_out,
+                             [](sg_handle* h, const void* e, const uint64_t*, uint64_t, uint64_t c, void* o, hipStream_t st) {
+                                 return sg_local_decide_batch(h, static_cast<const sg_local_event*>(e), c,
+                                                              static_cast<sg_local_result*>(o), st);
+                             });
+    if (rc) return rc;
+    // 3. the results back in caller order
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    NHIP(nd, launch_route_gather8(nd->d_lsub_out, nd->d_sub_pos, n, out, nd->s0));
+    NHIP(nd, hipStreamSynchronize(nd->s0));
+    nd->l_last_ts = last;
+    ++nd->l_batches;
+    return SG_OK;
+}
+
+int sg_node_local_decide_batch_host(sg_node* nd, const sg_local_event* ev, uint64_t n, sg_local_result* out) {
+    if (!nd) return SG_E_INVAL;
+    if (n == 0) return SG_OK;
+    if (!ev || !out) return nfail(nd, SG_E_INVAL, "null buffer");
+    if (n > nd->cfg.max_batch) return nfail(nd, SG_E_CAPACITY, "batch larger than max_batch");
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    node_drain(nd);
+    if (!nd->d_lev_h && (hipMalloc(&nd->d_lev_h, sizeof(sg_local_event) * nd->cfg.max_batch) != hipSuccess ||
+                         hipMalloc(&nd->d_lout_h, sizeof(sg_local_result) * nd->cfg.max_batch) != hipSuccess))
+        return nfail(nd, SG_E_NOMEM, "node host-path buffers");
+    NHIP(nd, hipMemcpy(nd->d_lev_h, ev, sizeof(sg_local_event) * n, hipMemcpyHostToDevice));
+    const int rc = sg_node_local_decide_batch(nd, nd->d_lev_h, n, nd->d_lout_h, nullptr);
+    if (rc) return rc;
+    NHIP(nd, hipMemcpy(out, nd->d_lout_h, sizeof(sg_local_result) * n, hipMemcpyDeviceToHost));
+    return SG_OK;
+}
+
+int sg_node_local_read_state(sg_node* nd, uint32_t res, int64_t* second, int64_t* borrow, int64_t* minute, int64_t* head) {
+    if (!nd) return SG_E_INVAL;
+    if (!nd->l_loaded || res >= nd->l_owner.size()) return nfail(nd, SG_E_INVAL, "no such resource");
+    node_drain(nd);
+    sg_handle* h = nd->shards[nd->l_owner[res]];
+    const int rc = node_child(nd, h, sg_local_read_state(h, res, second, borrow, minute, head));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* out, uint64_t cap, uint64_t* n_rows) {
+    return node_local_metrics(nd, now_ms, nullptr, out, cap, n_rows);
+}
+
+int sg_node_local_metrics_device(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, uint64_t cap, uint64_t* n_rows) {
+    return node_local_metrics(nd, now_ms, d_out, nullptr, cap, n_rows);
+}
+
+int sg_node_local_merge_rows(sg_node* nd, const sg_metric_node* d_rows, uint64_t n, sg_metric_node* d_out, uint64_t cap,
+                             uint64_t* n_out, void* stream) {
+    if (!nd || !n_out || (!d_rows && n) || (!d_out && cap)) return SG_E_INVAL;
+    *n_out = 0;
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    node_drain(nd);
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    return node_merge_rows(nd, d_rows, n, d_out, cap, n_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

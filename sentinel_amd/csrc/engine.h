@@ -857,6 +857,56 @@ hipError_t launch_nsnap_scatter(const double* part, const uint32_t* node_key, ui
 hipError_t launch_nconc_scatter(const sg_conc_result* sub_out, const uint32_t* sub_pos, const sg_conc_req* sub_req,
                                 uint64_t base, uint64_t cnt, uint32_t g, uint32_t G, sg_conc_result* out,
                                 hipStream_t stream);
+// The local slot chain over the node (node.hip k_lroute_*, sg_node_local_*): the node batch's events split stably by
+// the owner of their resource — the shards load the node's rules under the node's indices, so an event moves
+// unchanged — with the whole batch's validation (time order, origin ids, period span) folded into the count pass.
+struct LRouteArgs {
+    const sg_local_event* ev;  // the node batch (caller order)
+    uint64_t n;
+    uint32_t K;                // node resources; an event of a resource >= K goes to shard 0, which answers it
+    const uint8_t* owner;      // [K] owner shard of each resource (sg_local_owners of the node's rules)
+    int G;
+    uint32_t* tile_cnt;        // [tiles][kMaxShards]
+    uint32_t* shard_base;      // [G + 1]
+    uint32_t* shard_tot;       // [G]
+    sg_local_event* sub_ev;    // [n] the shards' slices, one after the other
+    uint32_t* sub_pos;         // [n] caller position of each routed event
+    int* err;                  // kErrTime | kErrBounds | kErrPeriods (zeroed before)
+    int64_t last_ts;           // the node's previous local batch: its last timestamp (-1: none)
+    int32_t n_origins;         // origin ids 0..n_origins
+    int n_wl;                  // window lengths of the shards' period tables (k_local_prep's kErrPeriods)
+    int32_t wl[2];
+};
+hipError_t launch_lroute(const LRouteArgs& r, hipStream_t stream);
+hipError_t launch_route_gather8(const sg_local_result* sub_out, const uint32_t* sub_pos, uint64_t total,
+                                sg_local_result* out, hipStream_t stream);
+// The node's metric-row merge (node.hip k_merge_*, cluster.merge_metric_rows without a sort): every row of one fetch
+// lies in the minute before now, so the slot (ts / 1000) % 60 names its second, and a resource's row of a second
+// comes from its owner alone — a bitmap [60][W] of (second, resource) places every resource row exactly.
+constexpr uint64_t kMergeNoTs = ~0ull;   // a slot no row has named yet (timestamps are >= 0)
+constexpr int kMergeBad = 1;             // the input breaks the contract (SG_E_INVAL)
+constexpr int kMergeCap = 2;             // more merged rows than the caller's capacity (SG_E_CAPACITY)
+struct MergeSlots {
+    unsigned long long ts[kMinuteS];       // the slot's timestamp
+    unsigned long long acc[kMinuteS][5];   // ENTRY_NODE sums: pass, block, success, exception, rt
+    unsigned long long base[kMinuteS];     // first output row of the slot's second
+    uint32_t res_cnt[kMinuteS];            // resource rows of the slot
+    uint32_t has_entry[kMinuteS];
+    unsigned long long n_out;
+    unsigned long long n_res;              // resource rows seen (against the bits set: duplicates)
+    int err;
+};
+struct MergeArgs {
+    const sg_metric_node* rows;
+    uint64_t n;
+    uint32_t K, W;                 // node resources, bitmap words per slot (ceil(K / 64))
+    unsigned long long* bits;      // [60][W] (zeroed before)
+    uint32_t* pre;                 // [60][W] exclusive popcount scan of each slot's words
+    MergeSlots* st;
+    sg_metric_node* out;
+    uint64_t cap;
+};
+hipError_t launch_merge_rows(const MergeArgs& m, hipStream_t stream);
 // sort.hip: stable LSD radix sort of records on bits [lo_bit, hi_bit); result buffer is a or b.
 size_t radix_hist_words(uint64_t n);
 int radix_digit_bits(int bits);  // digit width radix_sort_records uses for `bits` key bits (8 or 10)

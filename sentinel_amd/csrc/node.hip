@@ -516,4 +516,397 @@ hipError_t launch_nconc_scatter(const sg_conc_result* sub_out, const uint32_t* s
     return hipGetLastError();
 }
 
+// ---- the local slot chain over the node (sg_node_local_*) ----
+//
+// StatisticSlot → FlowSlot → DegradeSlot for the whole node: every shard holds the node's rules under the node's
+// resource indices and decides the events of the resources it owns (sg_local_owners: key groups on one owner), so
+// routing is a stable multisplit of the 32-byte events by owner[resource], the events unchanged:
+//   k_lroute_count    per 4096-event tile: events per shard, and the whole batch's validation — a slice of an
+//                     unsorted batch can itself be sorted and spans less time than the batch, so the shards cannot
+//                     see what one handle refuses from the events alone (time order, origin ids, the period span)
+//   k_route_scan / k_route_bases   as for the token batches
+//   k_lroute_scatter  per tile: each wave ranks its 64-event rounds by shard (match ballots) and moves the event and
+//                     its caller position; arrival order within a slice is kept (an exit may share its entry's ms)
+//   k_route_gather8   out[pos[j]] = sub_out[j] for the 8-byte results
+// HBM-bound byte work: 32 B read (count), 32 B read + 32 B + 4 B written (scatter), 8 B + 4 B read and 8 B written
+// (gather) per event; no MFMA.
+
+namespace {
+__device__ __forceinline__ uint32_t lroute_shard(const LRouteArgs& r, uint32_t resource) {
+    const uint32_t k = resource & SG_KEY_INDEX;
+    return k < r.K ? (uint32_t)r.owner[k] : 0u;
+}
+}  // namespace
+
+__global__ void __launch_bounds__(kRouteThreads) k_lroute_count(LRouteArgs r) {
+    __shared__ uint32_t cnt[kMaxShards];
+    const int tid = threadIdx.x;
+    if (tid < kMaxShards) cnt[tid] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kRouteTile;
+    const int64_t t0 = r.ev[0].ts_ms;
+    // the period span k_local_prep refuses: some window's period index reaches kMaxPeriods past the first event's
+    // (only an event at least that many of the shortest windows after it can; the divisions are for those alone)
+    int64_t span = INT64_MAX;
+    for (int w = 0; w < r.n_wl; ++w) {
+        const int64_t s = (int64_t)(kMaxPeriods - 1) * r.wl[w];
+        span = s < span ? s : span;
+    }
+    int bad = 0;
+#pragma unroll 4
+    for (int it = 0; it < kRouteRounds; ++it) {
+        const uint64_t i = base + (uint64_t)it * kRouteThreads + tid;
+        if (i >= r.n) break;
+        const int64_t t = r.ev[i].ts_ms;
+        const int64_t tp = i ? r.ev[i - 1].ts_ms : r.last_ts;  // the predecessor: the node's previous batch for the first
+        const uint32_t res = r.ev[i].resource;
+        const int32_t origin = r.ev[i].origin;
+        if (t < 0 || t < tp) bad |= kErrTime;
+        if (origin < 0 || origin > r.n_origins) bad |= kErrBounds;
+        if (t >= t0 && t - t0 >= span)
+            for (int w = 0; w < r.n_wl; ++w)
+                if (t / r.wl[w] - t0 / r.wl[w] >= (int64_t)kMaxPeriods) bad |= kErrPeriods;
+        atomicAdd(&cnt[lroute_shard(r, res)], 1u);
+    }
+    if (bad) atomicOr(r.err, bad);
+    __syncthreads();
+    if (tid < r.G) r.tile_cnt[(size_t)blockIdx.x * kMaxShards + tid] = cnt[tid];
+}
+
+__global__ void __launch_bounds__(kRouteThreads) k_lroute_scatter(LRouteArgs r) {
+    __shared__ uint32_t wrun[kRouteThreads / 64][kMaxShards];  // each wave's running count per shard in its range
+    __shared__ uint32_t wtot[kRouteThreads / 64][kMaxShards];  // each wave's total per shard (its range's prefix)
+    const int tid = threadIdx.x, lane = route_lane(), wave = tid >> 6;
+    const uint64_t base = (uint64_t)blockIdx.x * kRouteTile;
+    const uint64_t w0 = base + (uint64_t)wave * kRouteWaveRecs;  // the wave's contiguous events
+    for (int x = lane; x < kMaxShards; x += 64) {
+        wrun[wave][x] = 0;
+        wtot[wave][x] = 0;
+    }
+    // every resource word, then every owner, loaded before any is used; the events themselves are read again when
+    // they move (16 of them would not fit the registers; the tile's 128 KB are in the cache by then)
+    constexpr int kR = kRouteWaveRecs / 64;
+    uint32_t res[kR], sh[kR];
+#pragma unroll
+    for (int it = 0; it < kR; ++it) {
+        const uint64_t i = w0 + (uint64_t)it * 64 + lane;
+        res[it] = i < r.n ? r.ev[i].resource : 0u;
+    }
+#pragma unroll
+    for (int it = 0; it < kR; ++it) {
+        const uint64_t i = w0 + (uint64_t)it * 64 + lane;
+        sh[it] = i < r.n ? lroute_shard(r, res[it]) : (uint32_t)kRouteNone;
+    }
+    // 1. per wave: events per shard over its range (the tile's stable order is wave 0's events, then wave 1's …)
+#pragma unroll
+    for (int it = 0; it < kR; ++it) {
+        const uint32_t s = sh[it];
+        const uint64_t peers = match_shard(s);
+        if (s < (uint32_t)r.G && (peers & ((1ull << lane) - 1ull)) == 0) wtot[wave][s] += (uint32_t)__popcll(peers);
+        __builtin_amdgcn_sched_barrier(0);  // round by round, as k_route_scatter
+    }
+    __syncthreads();
+    // 2. place: position = shard base + the tile's offset + earlier waves of the tile + earlier rounds + rank in round
+#pragma unroll
+    for (int it = 0; it < kR; ++it) {
+        const uint64_t i = w0 + (uint64_t)it * 64 + lane;
+        const uint32_t s = sh[it];
+        const uint64_t peers = match_shard(s);
+        const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+        if (s < (uint32_t)r.G) {
+            uint32_t before = 0;
+            for (int w = 0; w < wave; ++w) before += wtot[w][s];
+            const uint32_t pos = r.shard_base[s] + r.tile_cnt[(size_t)blockIdx.x * kMaxShards + s] + before +
+                                 wrun[wave][s] + rank;
+            r.sub_ev[pos] = r.ev[i];
+            r.sub_pos[pos] = (uint32_t)i;
+        }
+        if (s < (uint32_t)r.G && rank == 0) wrun[wave][s] += (uint32_t)__popcll(peers);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_route_gather8(const sg_local_result* sub_out, const uint32_t* sub_pos,
+                                                       uint64_t total, sg_local_result* out) {
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x)
+        out[sub_pos[j]] = sub_out[j];
+}
+
+hipError_t launch_lroute(const LRouteArgs& r, hipStream_t stream) {
+    const uint32_t tiles = (uint32_t)((r.n + kRouteTile - 1) / kRouteTile);
+    if (tiles == 0) return hipSuccess;
+    RouteArgs s{};  // the scan and the bases read the counts alone
+    s.G = r.G;
+    s.tile_cnt = r.tile_cnt;
+    s.shard_base = r.shard_base;
+    s.shard_tot = r.shard_tot;
+    lds_poison(stream);
+    hipLaunchKernelGGL(k_lroute_count, dim3(tiles), dim3(kRouteThreads), 0, stream, r);
+    hipLaunchKernelGGL(k_route_scan, dim3((unsigned)r.G), dim3(kScanThreads), 0, stream, s, tiles);
+    hipLaunchKernelGGL(k_route_bases, dim3(1), dim3(64), 0, stream, s);
+    lds_poison(stream);
+    hipLaunchKernelGGL(k_lroute_scatter, dim3(tiles), dim3(kRouteThreads), 0, stream, r);
+    return hipGetLastError();
+}
+
+hipError_t launch_route_gather8(const sg_local_result* sub_out, const uint32_t* sub_pos, uint64_t total,
+                                sg_local_result* out, hipStream_t stream) {
+    if (total == 0) return hipSuccess;
+    uint64_t g = (total + 255) / 256;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(k_route_gather8, dim3((unsigned)g), dim3(256), 0, stream, sub_out, sub_pos, total, out);
+    return hipGetLastError();
+}
+
+// ---- the node's metric rows merged (sg_node_local_merge_rows; cluster.merge_metric_rows on the device, no sort) ----
+//
+// MetricTimerListener.run for the node: the shards' raw rows of one fetch at now — timestamps multiples of 1000 in
+// the minute before now, so the slot (ts / 1000) % 60 names a row's second (at most 59 of them), and a resource's row
+// of a second comes from its owner alone.
+//   k_merge_mark   per row: a resource row sets bit `resource` of bits[slot][W] (one 64-bit atomic OR per (slot,
+//                  word) present in the wave, nothing returned; the resource rows are counted, and fewer bits than
+//                  rows in the end is a duplicated row); an ENTRY_NODE row adds its five
+//                  counters to the slot's sums (a few rows per shard: global adds). The slot's timestamp is claimed by
+//                  the first row (compare-and-swap); another timestamp in it, one that is no multiple of 1000, or a
+//                  resource that is neither below K nor the ENTRY_NODE's breaks the contract.
+//   k_merge_scan   one block per slot a row named: the exclusive popcount scan of its words, 512 words a pass
+//   k_merge_bases  one wave: the slots' bases in ascending timestamp order (the minute ring wraps), each second's
+//                  ENTRY_NODE row — rt = Σrt / Σsuccess, kept when isValidMetricNode — after its resource rows (the
+//                  largest resource id), the row count; any contract error or a table larger than the caller's
+//                  buffer: nothing is written
+//   k_merge_place  per row: a resource row to base[slot] + pre[slot][word] + popc(word & lower bits), rt = rt /
+//                  success when success != 0
+// The table is exact and its order deterministic. 64 B read twice and 64 B written per row, 8 B + 4 B of bitmap and
+// prefix per row from the cache.
+
+constexpr int kMergeScanThreads = 256;
+constexpr int kMergeScanPer = 2;
+constexpr uint32_t kMergeScanPass = kMergeScanThreads * kMergeScanPer;
+static_assert(sizeof(sg_metric_node) == 64 && offsetof(sg_metric_node, rt) == 40 && offsetof(sg_metric_node, resource) == 56,
+              "k_merge_place moves a row as eight 64-bit words");
+
+__global__ void __launch_bounds__(64) k_merge_reset(MergeSlots* st) {
+    const int j = threadIdx.x;
+    if (j < kMinuteS) {
+        st->ts[j] = kMergeNoTs;
+        for (int c = 0; c < 5; ++c) st->acc[j][c] = 0;
+        st->base[j] = 0;
+        st->res_cnt[j] = 0;
+        st->has_entry[j] = 0;
+    }
+    if (j == 0) {
+        st->n_out = 0;
+        st->n_res = 0;
+        st->err = 0;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_merge_mark(MergeArgs m) {
+    const int lane = route_lane();
+    int bad = 0;
+    uint32_t n_res = 0;  // this thread's resource rows
+    // the loop runs block-uniformly (the bitmap writes below are wave-wide)
+    for (uint64_t b0 = (uint64_t)blockIdx.x * 256; b0 < m.n; b0 += (uint64_t)gridDim.x * 256) {
+        const uint64_t i = b0 + threadIdx.x;
+        bool todo = false;
+        uint64_t key = 0;
+        unsigned long long bit = 0;
+        // the row's timestamp and resource; `claim`: the row passed the checks that need no other row
+        int64_t ts = 0;
+        uint32_t res = 0;
+        int slot = 0;
+        bool claim = false;
+        if (i < m.n) {
+            ts = m.rows[i].timestamp;
+            res = m.rows[i].resource;
+            if (ts < 0 || ts % 1000 != 0 || (res >= m.K && res != SG_ENTRY_NODE_RESOURCE)) {
+                bad = 1;
+            } else {
+                slot = (int)((ts / 1000) % kMinuteS);
+                claim = true;
+            }
+        }
+        // the slot's timestamp, claimed by its first row (compare-and-swap): one lane per timestamp present in the
+        // wave asks (every lane asking was a pile-up of compare-and-swaps on a slot's word while the first waves all
+        // found it unclaimed: 0.8 ms of a 2M-row pass)
+        bool same = false;
+        for (bool ask = claim; __ballot(ask);) {
+            const int first = __builtin_ctzll(__ballot(ask));
+            const int64_t t0 = (int64_t)__shfl((long long)ts, first, 64);
+            const bool mine = ask && ts == t0;
+            unsigned long long seen = 0;
+            if (lane == first) {
+                seen = __hip_atomic_load(&m.st->ts[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (seen == kMergeNoTs) {
+                    seen = atomicCAS(&m.st->ts[slot], (unsigned long long)kMergeNoTs, (unsigned long long)ts);
+                    if (seen == kMergeNoTs) seen = (unsigned long long)ts;
+                }
+            }
+            seen = (unsigned long long)__shfl((long long)seen, first, 64);
+            if (mine) same = seen == (unsigned long long)t0;
+            ask = ask && !mine;
+        }
+        if (claim && !same) {
+            bad = 1;  // two seconds in one slot: rows 60 s or more apart
+        } else if (claim && res == SG_ENTRY_NODE_RESOURCE) {
+            const sg_metric_node r = m.rows[i];
+            const int64_t v[5] = {r.pass_qps, r.block_qps, r.success_qps, r.exception_qps, r.rt};
+            for (int c = 0; c < 5; ++c)
+                if (v[c]) atomicAdd(&m.st->acc[slot][c], (unsigned long long)v[c]);
+            m.st->has_entry[slot] = 1;
+        } else if (claim) {
+            todo = true;
+            key = (uint64_t)slot * m.W + (res >> 6);
+            bit = 1ull << (res & 63u);
+        }
+        // per (slot, word) present in the wave: one OR of its lanes' bits (a shard's rows come resource by resource,
+        // so a wave holds a few words; rows in any order fall back to one atomic each after eight rounds). The ORs
+        // return nothing — a wave does not wait for them; a duplicated (timestamp, resource) shows as fewer bits set
+        // than resource rows counted (k_merge_bases compares the two).
+        n_res += todo ? 1u : 0u;
+        for (int round = 0; __ballot(todo); ++round) {
+            if (round == 8) {
+                if (todo) atomicOr(&m.bits[key], bit);
+                break;
+            }
+            const int first = __builtin_ctzll(__ballot(todo));
+            const uint64_t k0 = (uint64_t)__shfl((long long)key, first, 64);
+            const bool mine = todo && key == k0;
+            unsigned long long v = mine ? bit : 0ull;
+            for (int o = 32; o > 0; o >>= 1) v |= (unsigned long long)__shfl_xor((long long)v, o, 64);
+            if (lane == first) atomicOr(&m.bits[k0], v);
+            todo = todo && !mine;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) n_res += (uint32_t)__shfl_xor((int)n_res, o, 64);
+    if (lane == 0 && n_res) atomicAdd(&m.st->n_res, (unsigned long long)n_res);
+    if (bad) atomicOr(&m.st->err, kMergeBad);
+}
+
+__global__ void __launch_bounds__(kMergeScanThreads) k_merge_scan(MergeArgs m) {
+    __shared__ uint32_t wsum[kMergeScanThreads / 64];
+    const int slot = blockIdx.x, tid = threadIdx.x, lane = route_lane(), wave = tid >> 6;
+    if (m.st->ts[slot] == kMergeNoTs) return;  // no row named the slot (the whole block leaves)
+    const unsigned long long* bits = m.bits + (size_t)slot * m.W;
+    uint32_t* pre = m.pre + (size_t)slot * m.W;
+    uint32_t carry = 0;
+    for (uint32_t p0 = 0; p0 < m.W; p0 += kMergeScanPass) {
+        const uint32_t w = p0 + (uint32_t)tid * kMergeScanPer;
+        uint32_t c[kMergeScanPer], mine = 0;
+#pragma unroll
+        for (int u = 0; u < kMergeScanPer; ++u) {
+            c[u] = w + u < m.W ? (uint32_t)__popcll(bits[w + u]) : 0u;
+            mine += c[u];
+        }
+        uint32_t x = mine;  // inclusive scan within the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)x, (unsigned)o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wsum[wave] = x;
+        __syncthreads();
+        uint32_t run = carry + x - mine, total = 0;
+        for (int v = 0; v < kMergeScanThreads / 64; ++v) {
+            if (v < wave) run += wsum[v];
+            total += wsum[v];
+        }
+#pragma unroll
+        for (int u = 0; u < kMergeScanPer; ++u) {
+            if (w + u < m.W) pre[w + u] = run;
+            run += c[u];
+        }
+        carry += total;
+        __syncthreads();  // wsum is written again by the next pass
+    }
+    if (tid == 0) m.st->res_cnt[slot] = carry;
+}
+
+__global__ void __launch_bounds__(64) k_merge_bases(MergeArgs m) {
+    const int j = route_lane();
+    MergeSlots* st = m.st;
+    const bool in = j < kMinuteS;
+    const unsigned long long ts = in ? st->ts[j] : kMergeNoTs;
+    const bool used = ts != kMergeNoTs;
+    const uint32_t rc = used ? st->res_cnt[j] : 0u;
+    int64_t v[5] = {0, 0, 0, 0, 0};
+    bool entry = false;
+    if (used && st->has_entry[j]) {
+        for (int c = 0; c < 5; ++c) v[c] = (int64_t)st->acc[j][c];
+        if (v[2] != 0) v[4] /= v[2];  // rt = Σrt / Σsuccess (ArrayMetric.fromBucket on the sums)
+        entry = v[0] > 0 || v[1] > 0 || v[2] > 0 || v[3] > 0 || v[4] > 0;  // isValidMetricNode
+    }
+    const unsigned long long cnt = (unsigned long long)rc + (entry ? 1u : 0u);
+    // rows of the earlier seconds (ascending timestamp, not slot order: the ring wraps); unused slots sort last
+    unsigned long long base = 0, total = 0, placed = 0;
+    for (int i = 0; i < kMinuteS; ++i) {
+        const unsigned long long ti = (unsigned long long)__shfl((long long)ts, i, 64);
+        const unsigned long long ci = (unsigned long long)__shfl((long long)cnt, i, 64);
+        placed += (uint32_t)__shfl((int)rc, i, 64);
+        if (ti < ts) base += ci;
+        total += ci;
+    }
+    int err = st->err;
+    if (placed != st->n_res) err |= kMergeBad;  // fewer bits than resource rows: a (timestamp, resource) came twice
+    if (total > m.cap) err |= kMergeCap;
+    if (used) st->base[j] = base;
+    if (j == 0) {
+        st->n_out = total;
+        st->err = err;
+    }
+    if (!err && entry) {
+        sg_metric_node r;
+        r.timestamp = (int64_t)ts;
+        r.pass_qps = v[0];
+        r.block_qps = v[1];
+        r.success_qps = v[2];
+        r.exception_qps = v[3];
+        r.rt = v[4];
+        r.occupied_pass_qps = 0;
+        r.resource = SG_ENTRY_NODE_RESOURCE;
+        r.concurrency = 0;
+        m.out[base + rc] = r;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_merge_place(MergeArgs m) {
+    if (m.st->err) return;  // a contract error or too small a buffer: the caller's table stays untouched
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < m.n; i += (uint64_t)gridDim.x * 256) {
+        // the row as its eight 64-bit words (timestamp, pass, block, success, exception, rt, occupied pass,
+        // resource | concurrency << 32), kept in registers
+        const long long* src = reinterpret_cast<const long long*>(m.rows + i);
+        const long long w0 = src[0], w1 = src[1], w2 = src[2], w3 = src[3], w4 = src[4], w5 = src[5], w6 = src[6],
+                        w7 = src[7];
+        const uint32_t res = (uint32_t)w7;
+        if (res == SG_ENTRY_NODE_RESOURCE) continue;  // written once per second from the sums
+        const int slot = (int)((w0 / 1000) % kMinuteS);
+        const size_t word = (size_t)slot * m.W + (res >> 6);
+        const unsigned long long below = m.bits[word] & ((1ull << (res & 63u)) - 1ull);
+        const unsigned long long pos = m.st->base[slot] + m.pre[word] + (unsigned long long)__popcll(below);
+        long long* dst = reinterpret_cast<long long*>(m.out + pos);
+        dst[0] = w0;
+        dst[1] = w1;
+        dst[2] = w2;
+        dst[3] = w3;
+        dst[4] = w4;
+        dst[5] = w3 != 0 ? w5 / w3 : w5;  // rt / success (ArrayMetric.fromBucket)
+        dst[6] = w6;
+        dst[7] = w7;
+    }
+}
+
+hipError_t launch_merge_rows(const MergeArgs& m, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(m.bits, 0, sizeof(unsigned long long) * kMinuteS * (size_t)(m.W ? m.W : 1), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_merge_reset, dim3(1), dim3(64), 0, stream, m.st);
+    uint64_t g = (m.n + 255) / 256;
+    if (g > 4096) g = 4096;
+    if (g) hipLaunchKernelGGL(k_merge_mark, dim3((unsigned)g), dim3(256), 0, stream, m);
+    lds_poison(stream);
+    if (g) hipLaunchKernelGGL(k_merge_scan, dim3(kMinuteS), dim3(kMergeScanThreads), 0, stream, m);
+    hipLaunchKernelGGL(k_merge_bases, dim3(1), dim3(64), 0, stream, m);
+    if (g) hipLaunchKernelGGL(k_merge_place, dim3((unsigned)g), dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
 }  // namespace sg

@@ -36,7 +36,11 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_node_cparam_decide_batch", "sg_node_cparam_decide_batch_host", "sg_node_cparam_read_sum",
            "sg_node_cparam_top_values", "sg_node_conc_set_rule_timeouts", "sg_node_conc_decide_batch",
            "sg_node_conc_decide_batch_host", "sg_node_conc_expire", "sg_node_conc_read_state",
-           "sg_local_metrics_raw_device", "sg_local_metrics_raw_enqueue"]
+           "sg_local_metrics_raw_device", "sg_local_metrics_raw_enqueue",
+           "sg_node_local_load_rules", "sg_node_local_load_flow_rules", "sg_node_local_set_entry_types",
+           "sg_node_local_owner_of", "sg_node_local_decide_batch", "sg_node_local_decide_batch_host",
+           "sg_node_local_read_state", "sg_node_local_metrics", "sg_node_local_metrics_device",
+           "sg_node_local_merge_rows"]
 
 _lib = None
 
@@ -156,6 +160,16 @@ def load_library():
         "sg_node_conc_decide_batch_host": (C.c_int, [vp, vp, u64, vp]),
         "sg_node_conc_expire": (C.c_int, [vp, i64, vp, u32, C.POINTER(u64)]),
         "sg_node_conc_read_state": (C.c_int, [vp, u32, C.POINTER(C.c_int32), C.POINTER(u64)]),
+        "sg_node_local_load_rules": (C.c_int, [vp, vp, vp, u32]),
+        "sg_node_local_load_flow_rules": (C.c_int, [vp, vp, u32, C.c_int32, C.c_int32]),
+        "sg_node_local_set_entry_types": (C.c_int, [vp, vp, u32]),
+        "sg_node_local_owner_of": (C.c_int, [vp, u32, C.POINTER(C.c_uint32)]),
+        "sg_node_local_decide_batch": (C.c_int, [vp, vp, u64, vp, vp]),
+        "sg_node_local_decide_batch_host": (C.c_int, [vp, vp, u64, vp]),
+        "sg_node_local_read_state": (C.c_int, [vp, u32, vp, vp, vp, vp]),
+        "sg_node_local_metrics": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64)]),
+        "sg_node_local_metrics_device": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64)]),
+        "sg_node_local_merge_rows": (C.c_int, [vp, vp, u64, vp, u64, C.POINTER(u64), vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("SG_LIB_PATH") and not hasattr(L, name):
@@ -302,6 +316,94 @@ class NodeEngine:
         now, live = C.c_int32(), C.c_uint64()
         self._check(self._L.sg_node_conc_read_state(self.h, key, C.byref(now), C.byref(live)))
         return now.value, live.value
+
+    # ---- the local slot chain over the node (sg_node_local_*): routing by resource owner and the metric-row merge
+    # inside the library
+    def local_load_rules(self, rules: np.ndarray, sample_count=2, interval_ms=1000, occupy_timeout_ms=500,
+                         cold_factor=3):
+        rules = np.ascontiguousarray(rules, dtype=abi.LOCAL_RULE_DTYPE).reshape(-1)
+        cfg = abi.sg_local_config(sample_count=sample_count, interval_ms=interval_ms,
+                                  occupy_timeout_ms=occupy_timeout_ms, cold_factor=cold_factor)
+        self._check(self._L.sg_node_local_load_rules(self.h, C.byref(cfg), abi.ptr(rules), len(rules)))
+        self.local_S = sample_count
+        self.local_K = len(rules)
+
+    def local_load_flow_rules(self, rules: np.ndarray, n_origins=0, n_contexts=0) -> int:
+        """sg_node_local_load_flow_rules; returns the number of rules kept."""
+        rules = np.ascontiguousarray(rules, dtype=abi.LOCAL_FLOW_RULE_DTYPE).reshape(-1)
+        rc = self._L.sg_node_local_load_flow_rules(self.h, abi.ptr(rules), len(rules), n_origins, n_contexts)
+        self._check(min(rc, 0))
+        return rc
+
+    def local_set_entry_types(self, inbound):
+        v = np.ascontiguousarray(inbound, dtype=np.uint8)
+        self._check(self._L.sg_node_local_set_entry_types(self.h, abi.ptr(v), len(v)))
+
+    def local_owner_of(self, resource) -> int:
+        s = C.c_uint32()
+        rc = self._L.sg_node_local_owner_of(self.h, resource, C.byref(s))
+        if rc != 0:
+            raise EngineError(rc, "no such resource (or the node's local rules are not loaded)")
+        return s.value
+
+    def local_decide_host(self, ev: np.ndarray) -> np.ndarray:
+        ev = np.ascontiguousarray(ev, dtype=abi.LOCAL_EVENT_DTYPE).reshape(-1)
+        out = np.zeros(len(ev), abi.LOCAL_RES_DTYPE)
+        self._check(self._L.sg_node_local_decide_batch_host(self.h, abi.ptr(ev), len(ev), abi.ptr(out)))
+        return out
+
+    def local_decide_device(self, ev_ptr: int, n: int, out_ptr: int, stream_ptr: int = 0):
+        self._check(self._L.sg_node_local_decide_batch(self.h, C.c_void_p(ev_ptr), n, C.c_void_p(out_ptr),
+                                                       C.c_void_p(stream_ptr)))
+
+    def local_state(self, res):
+        """(second [S][8], borrow [S][2], minute [60][8], head[14]) of the resource on its owner shard."""
+        S = self.local_S
+        sec = np.zeros((S, 8), np.int64)
+        bor = np.zeros((S, 2), np.int64)
+        mnt = np.zeros((60, 8), np.int64)
+        head = np.zeros(14, np.int64)
+        self._check(self._L.sg_node_local_read_state(self.h, res, abi.ptr(sec), abi.ptr(bor), abi.ptr(mnt),
+                                                     abi.ptr(head)))
+        return sec, bor, mnt, head
+
+    def local_metrics(self, now_ms) -> np.ndarray:
+        """MetricTimerListener.run for the node: the merged, ordered rows (sg_metric_node)."""
+        n = C.c_uint64()
+        rc = self._L.sg_node_local_metrics(self.h, now_ms, None, 0, C.byref(n))
+        if rc not in (0, abi.SG_E_CAPACITY):
+            self._check(rc)
+        out = np.zeros(max(1, n.value), abi.METRIC_NODE_DTYPE)
+        self._check(self._L.sg_node_local_metrics(self.h, now_ms, abi.ptr(out), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def local_metrics_device(self, now_ms, out) -> int:
+        """sg_node_local_metrics_device into `out` (a device tensor on devices[0], int64 [cap, 8]); returns the row
+        count. Raises EngineError (SG_E_CAPACITY) when the shards' rows outnumber the tensor's; `.rows` of the error
+        is the sufficient capacity."""
+        n = C.c_uint64()
+        cap = out.numel() * out.element_size() // abi.METRIC_NODE_DTYPE.itemsize
+        rc = self._L.sg_node_local_metrics_device(self.h, now_ms, C.c_void_p(out.data_ptr()), cap, C.byref(n))
+        if rc != 0:
+            e = EngineError(rc, self._L.sg_node_last_error(self.h).decode())
+            e.rows = n.value
+            raise e
+        return n.value
+
+    def local_merge_rows(self, rows, out, stream_ptr: int = 0) -> int:
+        """sg_node_local_merge_rows: the raw rows of every GPU (device int64 [n, 8] on devices[0]) merged into `out`
+        (device int64 [cap, 8]); returns the row count."""
+        n = C.c_uint64()
+        n_in = rows.numel() * rows.element_size() // abi.METRIC_NODE_DTYPE.itemsize
+        cap = out.numel() * out.element_size() // abi.METRIC_NODE_DTYPE.itemsize
+        rc = self._L.sg_node_local_merge_rows(self.h, C.c_void_p(rows.data_ptr()) if n_in else None, n_in,
+                                              C.c_void_p(out.data_ptr()) if cap else None, cap, C.byref(n),
+                                              C.c_void_p(stream_ptr))
+        if rc != 0:
+            e = EngineError(rc, self._L.sg_node_last_error(self.h).decode())
+            e.rows = n.value
+            raise e
+        return n.value
 
 
 class FlowEngine:
