@@ -933,6 +933,86 @@ int sg_codec_decode_flow(sg_handle* h, const uint8_t* payload, const uint32_t* o
 int sg_codec_encode_flow(sg_handle* h, const int32_t* xid, const uint8_t* kind, const sg_result* res, uint64_t n,
                          uint8_t* frames_out, void* stream);
 
+/* ---------- param-flow wire codec and the value dictionary ----------
+ * MSG_TYPE_PARAM_FLOW data is [i64 flowId][i32 count][i32 amount] and then `amount` parameters, each one type byte
+ * (ClusterConstants.PARAM_TYPE_*) and its payload (ParamFlowRequestDataDecoder.java:35-90, written by
+ * ParamFlowRequestDataWriter.java:48-125): INTEGER i32, LONG i64, BYTE 1 byte, DOUBLE 8 bytes, FLOAT 4 bytes,
+ * SHORT i16, BOOLEAN 1 byte (non-zero is true), STRING [i32 length][bytes]; big-endian. Any other type byte takes
+ * that one byte and adds no parameter. Fewer than 16 data bytes or amount <= 0 decode to null data; a read past the
+ * frame's end or a negative string length throws in the Java decoder and no request reaches the service
+ * (SG_FRAME_MALFORMED; amount > the bytes left is answered so without looping, every parameter takes a byte). Unread
+ * trailing bytes are ignored. The response is the flow response frame with type 2 and waitInMs always 0
+ * (ParamFlowRequestProcessor.toResponse).
+ *
+ * Value dictionary (one per handle; the ValueDictionary of INTEGRATION.md §4c on the device). sg_cparam_* identify a
+ * parameter value by a u64; ClusterParamMetric identifies it by Java equals on the boxed object. The dictionary maps
+ * key = (type tag, canonical payload bytes) to dense ids 1, 2, 3, …: the payload as on the wire, except BOOLEAN
+ * 00 / 01, every DOUBLE NaN 7FF8000000000000 and every FLOAT NaN 7FC00000 (Double.equals / Float.equals compare
+ * doubleToLongBits / floatToIntBits: one NaN, +0.0 and -0.0 apart). Integer 5, Long 5, Short 5, Byte 5, "5",
+ * Float 5.0 and Double 5.0 are seven values. Strings are compared as their bytes: Java decodes them with the
+ * platform charset and folds malformed UTF-8 onto U+FFFD, so two malformed byte strings that Java would find equal
+ * are two values here. Ids are assigned in order of first appearance — frame order, then position in the frame; array
+ * order for sg_vdict_intern — and never change for the life of the handle, so they are a pure function of the input
+ * history. Lookups are exact (hash, then a byte compare).
+ *   sg_vdict_init    capacity 2^capacity_log2 values (1..28), arena_bytes for the payloads longer than 8 bytes,
+ *                    max_batch_values = the most values one sg_vdict_intern / sg_codec_decode_param call may carry
+ *                    (< 2^31). Once per handle: a second call is SG_E_UNSUPPORTED; a dictionary does not grow.
+ *   sg_vdict_intern  n values in HOST memory: types[n] (SG_PARAM_TYPE_*), offsets[n + 1] into bytes (the payload as
+ *                    on the wire, a STRING's bytes without the length; fixed types must have their size, else
+ *                    SG_E_INVAL) → ids_out[n]. How the shim names hot-item values (ParamFlowRuleUtil.parseHotItems,
+ *                    typed by classType) before sg_cparam_load_rules. It runs the decoder's device pipeline.
+ *   sg_vdict_lookup  ids[n] → types_out[n], offsets_out[n + 1], bytes_out (canonical payloads), HOST memory; for
+ *                    sg_cparam_top_values reporting. An id of 0 or above the value count is SG_E_INVAL; bytes_cap too
+ *                    small is SG_E_CAPACITY with offsets_out filled.
+ *   sg_vdict_size    values and arena bytes in use.
+ * All or nothing: a batch whose new values would exceed the capacity, or whose new long payloads the arena, returns
+ * SG_E_CAPACITY and leaves the dictionary as it was — size, ids and arena.
+ *
+ * sg_codec_decode_param: inputs as sg_codec_decode_flow (DEVICE payload, offsets[n + 1], ts_ms[n]; n <= max_batch);
+ * outputs DEVICE req_out[n], values_out[values_cap], xid_out[n], kind_out[n] and HOST *n_values. A
+ * SG_FRAME_PARAM frame gets key = the rule index of its flowId in the handle's sg_cparam_load_rules (unknown →
+ * SG_KEY_NO_RULE, flowId <= 0 → SG_KEY_BAD), acquire = count, and value_begin / value_count = the dictionary ids of
+ * its valid parameters, appended to values_out in frame order (the range contract of sg_cparam_decide_batch); a
+ * frame with no valid parameter keeps value_count 0 (BAD_REQUEST). Every other kind — under 5 bytes SG_FRAME_SHORT,
+ * null data SG_FRAME_NO_DATA, a throw SG_FRAME_MALFORMED, another message type (flow included) SG_FRAME_OTHER —
+ * gets key SG_KEY_BAD, acquire 0, value_count 0 and interns nothing; value_begin is the running total for every
+ * frame. A mixed stream is decoded by calling both decoders over the same payload. The call runs on `stream` and
+ * returns after it completed (it needs the total and the capacity verdict). *n_values is the number of values of
+ * the batch; when it exceeds values_cap or max_batch_values the call returns SG_E_CAPACITY with *n_values set and
+ * nothing interned. SG_E_CAPACITY from the dictionary: as above (the outputs are then undefined). A payload that is
+ * not 4-byte aligned is SG_E_INVAL.
+ * sg_codec_encode_param: as sg_codec_encode_flow for SG_FRAME_PARAM kinds, waitInMs 0 whatever res.wait_ms holds.
+ *
+ * Not covered: the node handle (sg_node_*), the concurrent-token message types 3 / 4 (the default server registers
+ * no decoder for them), growing a dictionary after sg_vdict_init. */
+#define SG_FRAME_PARAM     4   /* a param-flow token request, decoded                                    */
+#define SG_FRAME_MALFORMED 5   /* MSG_TYPE_PARAM_FLOW whose decoder would throw: no request is made       */
+#define SG_PARAM_TYPE_INTEGER 0
+#define SG_PARAM_TYPE_LONG    1
+#define SG_PARAM_TYPE_BYTE    2
+#define SG_PARAM_TYPE_DOUBLE  3
+#define SG_PARAM_TYPE_FLOAT   4
+#define SG_PARAM_TYPE_SHORT   5
+#define SG_PARAM_TYPE_BOOLEAN 6
+#define SG_PARAM_TYPE_STRING  7
+typedef struct sg_vdict_config {
+    int32_t  capacity_log2;     /* 2^capacity_log2 values                                */
+    int32_t  reserved;
+    uint64_t arena_bytes;       /* bytes of payloads longer than 8 bytes                 */
+    uint64_t max_batch_values;  /* values per intern / decode call                       */
+} sg_vdict_config;
+int sg_vdict_init(sg_handle* h, const sg_vdict_config* cfg);
+int sg_vdict_intern(sg_handle* h, const uint8_t* types, const uint32_t* offsets, const uint8_t* bytes, uint64_t n,
+                    uint64_t* ids_out);
+int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* types_out, uint32_t* offsets_out,
+                    uint8_t* bytes_out, uint64_t bytes_cap);
+int sg_vdict_size(sg_handle* h, uint64_t* n_values, uint64_t* arena_used);
+int sg_codec_decode_param(sg_handle* h, const uint8_t* payload, const uint32_t* offsets, const int64_t* ts_ms,
+                          uint64_t n, sg_cparam_req* req_out, uint64_t* values_out, uint64_t values_cap,
+                          uint64_t* n_values, int32_t* xid_out, uint8_t* kind_out, void* stream);
+int sg_codec_encode_param(sg_handle* h, const int32_t* xid, const uint8_t* kind, const sg_result* res, uint64_t n,
+                          uint8_t* frames_out, void* stream);
+
 /* ---------- Envoy rate-limit service ----------
  * SentinelEnvoyRlsServiceImpl.shouldRateLimit (sentinel-cluster/sentinel-cluster-server-envoy-rls/.../service/v3/
  * SentinelEnvoyRlsServiceImpl.java:34-85) for a time-ordered batch of n RateLimitRequests on a handle whose flow

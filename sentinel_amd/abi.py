@@ -36,6 +36,11 @@ KEY_PRIO = 0x80000000
 MSG_TYPE_PING, MSG_TYPE_FLOW, MSG_TYPE_PARAM_FLOW = 0, 1, 2
 FRAME_FLOW, FRAME_SHORT, FRAME_NO_DATA, FRAME_OTHER = 0, 1, 2, 3
 RESPONSE_FRAME_BYTES = 16
+# param-flow frames (SG_FRAME_PARAM / _MALFORMED) and ClusterConstants.PARAM_TYPE_* (SG_PARAM_TYPE_*)
+FRAME_PARAM, FRAME_MALFORMED = 4, 5
+(PARAM_TYPE_INTEGER, PARAM_TYPE_LONG, PARAM_TYPE_BYTE, PARAM_TYPE_DOUBLE, PARAM_TYPE_FLOAT, PARAM_TYPE_SHORT,
+ PARAM_TYPE_BOOLEAN, PARAM_TYPE_STRING) = range(8)
+PARAM_TYPE_SIZE = (4, 8, 1, 8, 4, 2, 1, None)   # payload bytes per type (STRING: [i32 length][bytes])
 KEY_INDEX = 0x7FFFFFFF
 KEY_NO_RULE = 0x7FFFFFFF
 KEY_BAD = 0x7FFFFFFE
@@ -67,6 +72,11 @@ class sg_req(C.Structure):
 
 class sg_result(C.Structure):
     _fields_ = [("status", C.c_int32), ("remaining", C.c_int32), ("wait_ms", C.c_int32)]
+
+
+class sg_vdict_config(C.Structure):
+    _fields_ = [("capacity_log2", C.c_int32), ("reserved", C.c_int32), ("arena_bytes", C.c_uint64),
+                ("max_batch_values", C.c_uint64)]
 
 
 class sg_batch_stats(C.Structure):
@@ -168,6 +178,7 @@ assert RES_DTYPE.itemsize == C.sizeof(sg_result) == 12
 assert RULE_DTYPE.itemsize == C.sizeof(sg_flow_rule) == 32
 assert NS_DTYPE.itemsize == C.sizeof(sg_namespace) == 16
 assert CPARAM_RULE_DTYPE.itemsize == 40 and CPARAM_REQ_DTYPE.itemsize == 24
+assert C.sizeof(sg_vdict_config) == 24
 assert DEGRADE_RULE_DTYPE.itemsize == 32 and LOCAL_RULE_DTYPE.itemsize == 80
 assert LOCAL_EVENT_DTYPE.itemsize == 32 and LOCAL_RES_DTYPE.itemsize == 8
 assert LOCAL_FLOW_RULE_DTYPE.itemsize == 56 and SLOT_EXT_DTYPE.itemsize == 16

@@ -161,6 +161,28 @@ struct sg_handle {
     uint64_t cpval_cap = 0;
     sg_result* d_cpout_h = nullptr;
 
+    // param-flow wire codec: flowId → cluster param rule index, and the value dictionary (pcodec.hip)
+    FidSlot* d_cpfid = nullptr;
+    uint64_t cpfid_mask = 0;
+    struct VDict {
+        bool on = false;
+        uint64_t capacity = 0, arena_bytes = 0, max_batch = 0;
+        uint64_t count = 0, arena_used = 0;   // the device state's size: every batch ends with the host knowing it
+        uint64_t* tab = nullptr;
+        uint64_t tab_mask = 0;
+        VEntry* entries = nullptr;
+        uint8_t* arena = nullptr;
+        VDesc* desc = nullptr;                // batch scratch, max_batch values
+        uint64_t* hash = nullptr;
+        uint32_t* slot_of = nullptr;
+        uint32_t* dedupe = nullptr;           // dedupe_slots >= 2 * max_batch
+        uint64_t dedupe_slots = 0;
+        uint64_t* scan = nullptr;
+        uint64_t* sums = nullptr;             // scan workspace for max(max_batch values, cfg.max_batch frames)
+        uint64_t* cnt = nullptr;              // [cfg.max_batch] values per frame / value_begin
+        uint64_t* totals = nullptr;           // [2] device: scan total, miss count
+    } vd;
+
     // local slot chain
     sg_local_config lcfg{2, 1000, 500, 0};
     std::vector<LRule> ltab;          // [K] the resources (sg_local_load_rules), origin nodes not included
@@ -359,6 +381,7 @@ int local_apply_groups(sg_handle* h);  // below: key groups of the local chain
 
 extern "C" {
 static int upload_fid_table(sg_handle* h);  // flowId → rule index for the wire codec (defined below)
+static int upload_cp_fid_table(sg_handle* h, const sg_cparam_rule* rules, uint32_t n);  // the same for param rules
 }
 
 namespace {
@@ -689,6 +712,18 @@ void sg_destroy(sg_handle* h) {
     dfree(h->d_cpreq_h);
     dfree(h->d_cpval_h);
     dfree(h->d_cpout_h);
+    dfree(h->d_cpfid);
+    dfree(h->vd.tab);
+    dfree(h->vd.entries);
+    dfree(h->vd.arena);
+    dfree(h->vd.desc);
+    dfree(h->vd.hash);
+    dfree(h->vd.slot_of);
+    dfree(h->vd.dedupe);
+    dfree(h->vd.scan);
+    dfree(h->vd.sums);
+    dfree(h->vd.cnt);
+    dfree(h->vd.totals);
     dfree(h->d_lrules);
     dfree(h->d_lfrules);
     dfree(h->d_lctl);
@@ -1180,6 +1215,291 @@ int sg_codec_encode_flow(sg_handle* h, const int32_t* xid, const uint8_t* kind, 
     c.res = res;
     c.frames = frames_out;
     HIP_TRY(h, launch_codec_encode(c, (hipStream_t)stream));
+    return SG_OK;
+}
+
+// ------------------------------------------------- param-flow wire codec and the value dictionary (pcodec.hip)
+
+static int upload_cp_fid_table(sg_handle* h, const sg_cparam_rule* rules, uint32_t n) {
+    uint64_t cap = 2;
+    while (cap < 2ull * n) cap <<= 1;
+    std::vector<FidSlot> tab(cap, FidSlot{0, 0, 0});
+    for (uint32_t k = 0; k < n; ++k) {  // flowIds are > 0 and unique (validated by sg_cparam_load_rules)
+        uint64_t p = host_fid_hash(rules[k].flow_id) & (cap - 1);
+        while (tab[p].fid != 0) p = (p + 1) & (cap - 1);
+        tab[p] = FidSlot{rules[k].flow_id, k, 0};
+    }
+    FidSlot* d = nullptr;
+    if (hipMalloc(&d, sizeof(FidSlot) * cap) != hipSuccess) return fail(h, SG_E_NOMEM, "param flowId table");
+    if (hipMemcpy(d, tab.data(), sizeof(FidSlot) * cap, hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(d);
+        return fail(h, SG_E_DEVICE, "param flowId table upload");
+    }
+    dfree(h->d_cpfid);
+    h->d_cpfid = d;
+    h->cpfid_mask = cap - 1;
+    return SG_OK;
+}
+
+int sg_vdict_init(sg_handle* h, const sg_vdict_config* cfg) {
+    if (!h || !cfg) return SG_E_INVAL;
+    if (h->vd.on) return fail(h, SG_E_UNSUPPORTED, "the handle already has a value dictionary");
+    if (cfg->capacity_log2 < 1 || cfg->capacity_log2 > 28) return fail(h, SG_E_INVAL, "capacity_log2 must be in [1, 28]");
+    if (cfg->max_batch_values == 0 || cfg->max_batch_values >= (1ull << 31))
+        return fail(h, SG_E_INVAL, "max_batch_values must be in [1, 2^31)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    auto& v = h->vd;
+    v.capacity = 1ull << cfg->capacity_log2;
+    v.arena_bytes = cfg->arena_bytes;
+    v.max_batch = cfg->max_batch_values;
+    const uint64_t slots = 2 * v.capacity;  // at most half full: a probe always ends
+    v.tab_mask = slots - 1;
+    v.dedupe_slots = 64;
+    while (v.dedupe_slots < 2 * v.max_batch) v.dedupe_slots <<= 1;
+    const uint64_t frames = h->cfg.max_batch ? h->cfg.max_batch : 1;
+    const uint64_t mb = v.max_batch;
+    if (hipMalloc(&v.tab, 8 * slots) != hipSuccess || hipMalloc(&v.entries, sizeof(VEntry) * (v.capacity + 1)) != hipSuccess ||
+        hipMalloc(&v.arena, v.arena_bytes ? v.arena_bytes : 1) != hipSuccess ||
+        hipMalloc(&v.desc, sizeof(VDesc) * mb) != hipSuccess || hipMalloc(&v.hash, 8 * mb) != hipSuccess ||
+        hipMalloc(&v.slot_of, 4 * mb) != hipSuccess || hipMalloc(&v.dedupe, 4 * v.dedupe_slots) != hipSuccess ||
+        hipMalloc(&v.scan, 8 * mb) != hipSuccess ||
+        hipMalloc(&v.sums, 8 * (scan_blocks(std::max(mb, frames)) + 1)) != hipSuccess ||
+        hipMalloc(&v.cnt, 8 * frames) != hipSuccess || hipMalloc(&v.totals, 16) != hipSuccess ||
+        hipMemset(v.tab, 0, 8 * slots) != hipSuccess) {
+        dfree(v.tab);
+        dfree(v.entries);
+        dfree(v.arena);
+        dfree(v.desc);
+        dfree(v.hash);
+        dfree(v.slot_of);
+        dfree(v.dedupe);
+        dfree(v.scan);
+        dfree(v.sums);
+        dfree(v.cnt);
+        dfree(v.totals);
+        return fail(h, SG_E_NOMEM, "value dictionary allocation");
+    }
+    HIP_TRY(h, hipDeviceSynchronize());
+    v.on = true;
+    return SG_OK;
+}
+
+namespace {
+
+VDictArgs vd_args(sg_handle* h, uint64_t m, const uint8_t* src, uint64_t* ids) {
+    const auto& v = h->vd;
+    VDictArgs a{};
+    a.tab = v.tab;
+    a.tab_mask = v.tab_mask;
+    a.entries = v.entries;
+    a.arena = v.arena;
+    a.count = v.count;
+    a.arena_used = v.arena_used;
+    a.m = m;
+    a.src = src;
+    a.desc = v.desc;
+    a.hash = v.hash;
+    a.ids = ids;
+    a.slot_of = v.slot_of;
+    a.dedupe = v.dedupe;
+    a.dedupe_mask = v.dedupe_slots - 1;
+    a.scan = v.scan;
+    a.n_miss = reinterpret_cast<unsigned long long*>(v.totals + 1);
+    return a;
+}
+
+// After the lookup pass of a batch of a.m values (ids 0 = miss, *a.n_miss counted): dedupe the misses, rank the
+// first occurrences, check the capacity, then append and insert. Returns with the stream idle.
+int vd_finish(sg_handle* h, VDictArgs a, hipStream_t stream) {
+    auto& v = h->vd;
+    uint64_t misses = 0;
+    HIP_TRY(h, hipMemcpyAsync(&misses, v.totals + 1, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    if (misses == 0) return SG_OK;
+    uint64_t slots = 64;
+    while (slots < 2 * misses) slots <<= 1;  // <= dedupe_slots: misses <= m <= max_batch
+    a.dedupe_mask = slots - 1;
+    HIP_TRY(h, hipMemsetAsync(v.dedupe, 0xFF, 4 * slots, stream));
+    HIP_TRY(h, launch_vd_dedupe(a, stream));
+    HIP_TRY(h, launch_scan_u64(v.scan, a.m, v.sums, v.totals, stream));
+    uint64_t total = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, v.totals, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    const uint64_t fresh = total >> 32, bytes = total & 0xFFFFFFFFull;
+    if (v.count + fresh > v.capacity) return fail(h, SG_E_CAPACITY, "value dictionary full");
+    if (v.arena_used + bytes > v.arena_bytes) return fail(h, SG_E_CAPACITY, "value dictionary arena full");
+    HIP_TRY(h, launch_vd_commit(a, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    v.count += fresh;
+    v.arena_used += bytes;
+    return SG_OK;
+}
+
+constexpr uint32_t kParamTypeSize[8] = {4, 8, 1, 8, 4, 2, 1, 0};  // SG_PARAM_TYPE_* payload bytes (STRING: any)
+
+}  // namespace
+
+int sg_vdict_intern(sg_handle* h, const uint8_t* types, const uint32_t* offsets, const uint8_t* bytes, uint64_t n,
+                    uint64_t* ids_out) {
+    if (!h) return SG_E_INVAL;
+    if (!h->vd.on) return fail(h, SG_E_INVAL, "sg_vdict_init first");
+    if (n == 0) return SG_OK;
+    if (!types || !offsets || !ids_out) return fail(h, SG_E_INVAL, "null buffer");
+    if (n > h->vd.max_batch) return fail(h, SG_E_CAPACITY, "more values than max_batch_values");
+    for (uint64_t j = 0; j < n; ++j) {
+        if (types[j] > SG_PARAM_TYPE_STRING || offsets[j + 1] < offsets[j]) return fail(h, SG_E_INVAL, "bad value record");
+        const uint32_t len = offsets[j + 1] - offsets[j];
+        if (types[j] != SG_PARAM_TYPE_STRING && len != kParamTypeSize[types[j]])
+            return fail(h, SG_E_INVAL, "payload size does not match the type");
+        if (len >= (1u << 24)) return fail(h, SG_E_INVAL, "payload of 16 MiB or more");
+    }
+    const uint64_t nbytes = offsets[n];
+    if (nbytes && !bytes) return fail(h, SG_E_INVAL, "null buffer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    uint8_t *d_types = nullptr, *d_bytes = nullptr;
+    uint32_t* d_off = nullptr;
+    uint64_t* d_ids = nullptr;
+    int rc = SG_OK;
+    auto run = [&]() -> int {
+        if (hipMalloc(&d_types, n) != hipSuccess || hipMalloc(&d_off, 4 * (n + 1)) != hipSuccess ||
+            hipMalloc(&d_bytes, nbytes ? nbytes : 1) != hipSuccess || hipMalloc(&d_ids, 8 * n) != hipSuccess)
+            return fail(h, SG_E_NOMEM, "intern buffers");
+        HIP_TRY(h, hipMemcpy(d_types, types, n, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(d_off, offsets, 4 * (n + 1), hipMemcpyHostToDevice));
+        if (nbytes) HIP_TRY(h, hipMemcpy(d_bytes, bytes, nbytes, hipMemcpyHostToDevice));
+        VDictArgs a = vd_args(h, n, d_bytes, d_ids);
+        a.types = d_types;
+        a.offsets = d_off;
+        HIP_TRY(h, hipMemsetAsync(h->vd.totals, 0, 16, nullptr));
+        HIP_TRY(h, launch_vd_host_lookup(a, nullptr));
+        const int frc = vd_finish(h, a, nullptr);
+        if (frc) return frc;
+        HIP_TRY(h, hipMemcpy(ids_out, d_ids, 8 * n, hipMemcpyDeviceToHost));
+        return SG_OK;
+    };
+    rc = run();
+    (void)hipDeviceSynchronize();
+    dfree(d_types);
+    dfree(d_off);
+    dfree(d_bytes);
+    dfree(d_ids);
+    return rc;
+}
+
+int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* types_out, uint32_t* offsets_out,
+                    uint8_t* bytes_out, uint64_t bytes_cap) {
+    if (!h) return SG_E_INVAL;
+    if (!h->vd.on) return fail(h, SG_E_INVAL, "sg_vdict_init first");
+    if (!offsets_out) return fail(h, SG_E_INVAL, "null buffer");
+    offsets_out[0] = 0;
+    if (n == 0) return SG_OK;
+    if (!ids || !types_out) return fail(h, SG_E_INVAL, "null buffer");
+    for (uint64_t j = 0; j < n; ++j)
+        if (ids[j] == 0 || ids[j] > h->vd.count) return fail(h, SG_E_INVAL, "unknown value id");
+    HIP_TRY(h, hipSetDevice(h->device));
+    uint64_t* d_ids = nullptr;
+    VEntry* d_e = nullptr;
+    uint32_t* d_off = nullptr;
+    uint8_t* d_bytes = nullptr;
+    std::vector<VEntry> e(n);
+    auto run = [&]() -> int {
+        if (hipMalloc(&d_ids, 8 * n) != hipSuccess || hipMalloc(&d_e, sizeof(VEntry) * n) != hipSuccess ||
+            hipMalloc(&d_off, 4 * (n + 1)) != hipSuccess)
+            return fail(h, SG_E_NOMEM, "lookup buffers");
+        HIP_TRY(h, hipMemcpy(d_ids, ids, 8 * n, hipMemcpyHostToDevice));
+        HIP_TRY(h, launch_vd_gather(h->vd.entries, d_ids, n, d_e, nullptr));
+        HIP_TRY(h, hipMemcpy(e.data(), d_e, sizeof(VEntry) * n, hipMemcpyDeviceToHost));
+        uint64_t total = 0;
+        for (uint64_t j = 0; j < n; ++j) {
+            types_out[j] = (uint8_t)e[j].type;
+            total += e[j].len;
+            if (total >= (1ull << 32)) return fail(h, SG_E_CAPACITY, "more than 2^32 payload bytes");
+            offsets_out[j + 1] = (uint32_t)total;
+        }
+        if (total > bytes_cap) return fail(h, SG_E_CAPACITY, "bytes_out too small");
+        if (total == 0) return SG_OK;
+        if (!bytes_out) return fail(h, SG_E_INVAL, "null buffer");
+        if (hipMalloc(&d_bytes, total) != hipSuccess) return fail(h, SG_E_NOMEM, "lookup buffers");
+        HIP_TRY(h, hipMemcpy(d_off, offsets_out, 4 * (n + 1), hipMemcpyHostToDevice));
+        HIP_TRY(h, launch_vd_bytes(d_e, d_off, n, h->vd.arena, d_bytes, nullptr));
+        HIP_TRY(h, hipMemcpy(bytes_out, d_bytes, total, hipMemcpyDeviceToHost));
+        return SG_OK;
+    };
+    const int rc = run();
+    (void)hipDeviceSynchronize();
+    dfree(d_ids);
+    dfree(d_e);
+    dfree(d_off);
+    dfree(d_bytes);
+    return rc;
+}
+
+int sg_vdict_size(sg_handle* h, uint64_t* n_values, uint64_t* arena_used) {
+    if (!h) return SG_E_INVAL;
+    if (!h->vd.on) return fail(h, SG_E_INVAL, "sg_vdict_init first");
+    if (n_values) *n_values = h->vd.count;
+    if (arena_used) *arena_used = h->vd.arena_used;
+    return SG_OK;
+}
+
+int sg_codec_decode_param(sg_handle* h, const uint8_t* payload, const uint32_t* offsets, const int64_t* ts_ms,
+                          uint64_t n, sg_cparam_req* req_out, uint64_t* values_out, uint64_t values_cap,
+                          uint64_t* n_values, int32_t* xid_out, uint8_t* kind_out, void* stream) {
+    if (!h) return SG_E_INVAL;
+    if (!n_values) return fail(h, SG_E_INVAL, "null buffer");
+    *n_values = 0;
+    if (!h->vd.on) return fail(h, SG_E_INVAL, "sg_vdict_init first");
+    if (n == 0) return SG_OK;
+    if (!payload || !offsets || !ts_ms || !req_out || !xid_out || !kind_out || (!values_out && values_cap))
+        return fail(h, SG_E_INVAL, "null buffer");
+    if (((uintptr_t)payload & 3u) != 0) return fail(h, SG_E_INVAL, "payload must be 4-byte aligned");
+    if (n > h->cfg.max_batch) return fail(h, SG_E_CAPACITY, "more frames than max_batch");
+    if (!h->d_cpfid) {
+        int rc = upload_cp_fid_table(h, nullptr, 0);  // no param rules loaded yet: every flowId is unknown
+        if (rc) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    auto& v = h->vd;
+    PCodecArgs c{};
+    c.n = n;
+    c.payload = payload;
+    c.offsets = offsets;
+    c.ts = ts_ms;
+    c.req = req_out;
+    c.xid = xid_out;
+    c.kind = kind_out;
+    c.fid_tab = h->d_cpfid;
+    c.fid_mask = h->cpfid_mask;
+    c.cnt = v.cnt;
+    HIP_TRY(h, launch_pcodec_count(c, st));
+    HIP_TRY(h, launch_scan_u64(v.cnt, n, v.sums, v.totals, st));
+    HIP_TRY(h, hipMemsetAsync(v.totals + 1, 0, 8, st));
+    uint64_t total = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, v.totals, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    *n_values = total;
+    if (total > values_cap) return fail(h, SG_E_CAPACITY, "values_out too small");
+    if (total > v.max_batch) return fail(h, SG_E_CAPACITY, "more values than max_batch_values");
+    c.vd = vd_args(h, total, payload, values_out);
+    HIP_TRY(h, launch_pcodec_emit(c, st));
+    return vd_finish(h, c.vd, st);
+}
+
+int sg_codec_encode_param(sg_handle* h, const int32_t* xid, const uint8_t* kind, const sg_result* res, uint64_t n,
+                          uint8_t* frames_out, void* stream) {
+    if (!h) return SG_E_INVAL;
+    if (n == 0) return SG_OK;
+    if (!xid || !kind || !res || !frames_out) return fail(h, SG_E_INVAL, "null buffer");
+    if (((uintptr_t)frames_out & 15u) != 0) return fail(h, SG_E_INVAL, "frames_out must be 16-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->device));
+    PCodecArgs c{};
+    c.n = n;
+    c.xid_in = xid;
+    c.kind_in = kind;
+    c.res = res;
+    c.frames = frames_out;
+    HIP_TRY(h, launch_pcodec_encode(c, (hipStream_t)stream));
     return SG_OK;
 }
 
@@ -2462,7 +2782,7 @@ int sg_cparam_load_rules(sg_handle* h, const sg_cparam_rule* rules, uint32_t n, 
         const int64_t neg = -1;
         HIP_TRY(h, hipMemcpy(h->d_cplast_ts, &neg, sizeof(neg), hipMemcpyHostToDevice));
     }
-    return SG_OK;
+    return upload_cp_fid_table(h, rules, n);  // sg_codec_decode_param's flowId lookup
 }
 
 static CPArgs cp_args(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint64_t* values, uint64_t n_values,

@@ -978,4 +978,80 @@ struct CodecArgs {
 hipError_t launch_codec_decode(const CodecArgs& c, hipStream_t stream);
 hipError_t launch_codec_encode(const CodecArgs& c, hipStream_t stream);
 
+// ---- param-flow wire codec and the value dictionary (pcodec.hip) ----
+
+struct alignas(8) VEntry {  // entries[id]: reverse lookup is an array read
+    uint64_t hash;
+    uint64_t data;          // len <= 8: the payload, byte k in bits [8k, 8k + 8); else its offset in the arena
+    uint32_t len;
+    uint32_t type;          // SG_PARAM_TYPE_*
+};
+static_assert(sizeof(VEntry) == 24, "VEntry layout");
+
+struct alignas(16) VDesc {  // one value of a batch: canonical payload (len <= 8) or where its bytes lie in the source
+    uint64_t inl;
+    uint32_t off;
+    uint32_t tl;            // len << 8 | type
+};
+static_assert(sizeof(VDesc) == 16, "VDesc layout");
+
+constexpr uint32_t kVdEmpty = 0xFFFFFFFFu;  // a free slot of the per-batch dedupe table
+
+struct VDictArgs {
+    // the dictionary
+    uint64_t* tab;          // main table: hash[63:32] << 32 | id, 0 = empty
+    uint64_t tab_mask;
+    VEntry* entries;        // [capacity + 1], entry 0 unused
+    uint8_t* arena;
+    uint64_t count;         // values before this batch
+    uint64_t arena_used;
+    // the batch
+    uint64_t m;             // values
+    const uint8_t* src;     // the bytes VDesc.off points into
+    VDesc* desc;            // [m]
+    uint64_t* hash;         // [m]
+    uint64_t* ids;          // [m] out: 0 while a value is a miss
+    uint32_t* slot_of;      // [m] dedupe slot of a miss
+    uint32_t* dedupe;       // per-batch table of batch positions
+    uint64_t dedupe_mask;
+    uint64_t* scan;         // [m] representative flags (count << 32 | arena bytes), then their exclusive scan
+    unsigned long long* n_miss;
+    // host intern: the uploaded arrays
+    const uint8_t* types;
+    const uint32_t* offsets;
+};
+
+struct PCodecArgs {
+    uint64_t n;
+    const uint8_t* payload;
+    const uint32_t* offsets;  // [n + 1]
+    const int64_t* ts;
+    sg_cparam_req* req;
+    int32_t* xid;
+    uint8_t* kind;
+    const FidSlot* fid_tab;   // flowId → cparam rule index
+    uint64_t fid_mask;
+    uint64_t* cnt;            // [n] values per frame, then their exclusive scan (value_begin)
+    VDictArgs vd;
+    // encode
+    const int32_t* xid_in;
+    const uint8_t* kind_in;
+    const sg_result* res;
+    uint8_t* frames;
+};
+
+constexpr uint32_t kScanTile = 2048;  // elements per block of the u64 scan
+inline uint64_t scan_blocks(uint64_t n) { return (n + kScanTile - 1) / kScanTile; }
+// In-place exclusive scan of v[n] (u64 adds); *total (device) gets the sum. sums: scan_blocks(n) u64 of workspace.
+hipError_t launch_scan_u64(uint64_t* v, uint64_t n, uint64_t* sums, uint64_t* total, hipStream_t stream);
+hipError_t launch_pcodec_count(const PCodecArgs& c, hipStream_t stream);
+hipError_t launch_pcodec_emit(const PCodecArgs& c, hipStream_t stream);
+hipError_t launch_pcodec_encode(const PCodecArgs& c, hipStream_t stream);
+hipError_t launch_vd_host_lookup(const VDictArgs& v, hipStream_t stream);
+hipError_t launch_vd_dedupe(const VDictArgs& v, hipStream_t stream);   // misses → dedupe table, representative flags
+hipError_t launch_vd_commit(const VDictArgs& v, hipStream_t stream);   // append + insert the new values, ids of all misses
+hipError_t launch_vd_gather(const VEntry* entries, const uint64_t* ids, uint64_t n, VEntry* out, hipStream_t stream);
+hipError_t launch_vd_bytes(const VEntry* e, const uint32_t* offsets, uint64_t n, const uint8_t* arena, uint8_t* out,
+                           hipStream_t stream);
+
 }  // namespace sg

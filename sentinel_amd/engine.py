@@ -24,6 +24,8 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_local_read_context_state", "sg_local_set_cluster_state", "sg_slot_decide_batch", "sg_local_set_entry_types",
            "sg_slot_decide_batch_host",
            "sg_codec_decode_flow", "sg_codec_encode_flow",
+           "sg_vdict_init", "sg_vdict_intern", "sg_vdict_lookup", "sg_vdict_size", "sg_codec_decode_param",
+           "sg_codec_encode_param",
            "sg_conc_set_rule_timeouts", "sg_conc_decide_batch", "sg_conc_decide_batch_host", "sg_conc_expire",
            "sg_conc_read_state", "sg_local_metrics", "sg_cparam_top_values", "sg_cparam_last_rounds",
            "sg_pslot_load_rules", "sg_pslot_decide_batch", "sg_pslot_decide_batch_host", "sg_pslot_thread_count",
@@ -128,6 +130,12 @@ def load_library():
         "sg_conc_expire": (C.c_int, [vp, i64, vp, u32, C.POINTER(u64)]),
         "sg_conc_read_state": (C.c_int, [vp, u32, C.POINTER(C.c_int32), C.POINTER(u64)]),
         "sg_codec_encode_flow": (C.c_int, [vp, vp, vp, vp, u64, vp, vp]),
+        "sg_vdict_init": (C.c_int, [vp, C.POINTER(abi.sg_vdict_config)]),
+        "sg_vdict_intern": (C.c_int, [vp, vp, vp, vp, u64, vp]),
+        "sg_vdict_lookup": (C.c_int, [vp, vp, u64, vp, vp, vp, u64]),
+        "sg_vdict_size": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u64)]),
+        "sg_codec_decode_param": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64), vp, vp, vp]),
+        "sg_codec_encode_param": (C.c_int, [vp, vp, vp, vp, u64, vp, vp]),
         "sg_pace_load_rules": (C.c_int, [vp, vp, u32]),
         "sg_pace_decide_batch": (C.c_int, [vp, vp, u64, vp, vp]),
         "sg_pace_decide_batch_host": (C.c_int, [vp, vp, u64, vp]),
@@ -502,6 +510,65 @@ class FlowEngine:
         self._check(self._L.sg_codec_encode_flow(self.h, C.c_void_p(xid_ptr), C.c_void_p(kind_ptr),
                                                  C.c_void_p(res_ptr), n, C.c_void_p(frames_ptr),
                                                  C.c_void_p(stream_ptr)))
+
+    # ---- param-flow wire codec and the value dictionary (sg_vdict_*, sg_codec_*_param)
+    def vdict_init(self, capacity_log2: int, arena_bytes: int, max_batch_values: int):
+        """Once per engine: 2^capacity_log2 values, arena_bytes for payloads over 8 bytes, values per call."""
+        cfg = abi.sg_vdict_config(capacity_log2=capacity_log2, arena_bytes=arena_bytes,
+                                  max_batch_values=max_batch_values)
+        self._check(self._L.sg_vdict_init(self.h, C.byref(cfg)))
+
+    def vdict_intern(self, keys) -> np.ndarray:
+        """keys: [(type tag, payload bytes), ...] (param_wire.canonical_key) → their u64 ids, new ones in order."""
+        from .param_wire import pack_keys
+        types, offsets, data = pack_keys(keys)
+        ids = np.zeros(len(types), np.uint64)
+        self._check(self._L.sg_vdict_intern(self.h, abi.ptr(types), abi.ptr(offsets), abi.ptr(data), len(types),
+                                            abi.ptr(ids)))
+        return ids
+
+    def vdict_lookup(self, ids):
+        """ids → [(type tag, canonical payload bytes), ...] (param_wire.key_value turns one into a Python value)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        n = len(ids)
+        types = np.zeros(max(n, 1), np.uint8)
+        offsets = np.zeros(n + 1, np.uint32)
+        rc = self._L.sg_vdict_lookup(self.h, abi.ptr(ids), n, abi.ptr(types), abi.ptr(offsets), None, 0)
+        if rc not in (0, abi.SG_E_CAPACITY):
+            self._check(rc)
+        data = np.zeros(max(int(offsets[n]), 1), np.uint8)
+        self._check(self._L.sg_vdict_lookup(self.h, abi.ptr(ids), n, abi.ptr(types), abi.ptr(offsets), abi.ptr(data),
+                                            len(data)))
+        raw = data.tobytes()
+        return [(int(types[j]), raw[int(offsets[j]):int(offsets[j + 1])]) for j in range(n)]
+
+    def vdict_size(self):
+        """(values, arena bytes) in use."""
+        nv, na = C.c_uint64(), C.c_uint64()
+        self._check(self._L.sg_vdict_size(self.h, C.byref(nv), C.byref(na)))
+        return int(nv.value), int(na.value)
+
+    def codec_decode_param(self, payload_ptr: int, offsets_ptr: int, ts_ptr: int, n: int, req_ptr: int,
+                           values_ptr: int, values_cap: int, xid_ptr: int, kind_ptr: int, stream_ptr: int = 0) -> int:
+        """Device addresses: frame payloads, offsets[n + 1] (u32), arrival ms (i64) → sg_cparam_req, u64 value ids
+        (values_cap of them), xid (i32), kind (u8). Returns the batch's value count after the stream has completed;
+        an EngineError with code SG_E_CAPACITY carries the needed count in .n_values."""
+        nv = C.c_uint64()
+        rc = self._L.sg_codec_decode_param(self.h, C.c_void_p(payload_ptr), C.c_void_p(offsets_ptr), C.c_void_p(ts_ptr),
+                                           n, C.c_void_p(req_ptr), C.c_void_p(values_ptr), values_cap, C.byref(nv),
+                                           C.c_void_p(xid_ptr), C.c_void_p(kind_ptr), C.c_void_p(stream_ptr))
+        if rc != 0:
+            e = EngineError(rc, self._L.sg_last_error(self.h).decode())
+            e.n_values = int(nv.value)
+            raise e
+        return int(nv.value)
+
+    def codec_encode_param(self, xid_ptr: int, kind_ptr: int, res_ptr: int, n: int, frames_ptr: int,
+                           stream_ptr: int = 0):
+        """Device addresses: xid (i32), kind (u8), sg_result → n 16-byte param-flow response frames (waitInMs 0)."""
+        self._check(self._L.sg_codec_encode_param(self.h, C.c_void_p(xid_ptr), C.c_void_p(kind_ptr),
+                                                  C.c_void_p(res_ptr), n, C.c_void_p(frames_ptr),
+                                                  C.c_void_p(stream_ptr)))
 
     def decide_host(self, req: np.ndarray) -> np.ndarray:
         req = np.ascontiguousarray(req, dtype=abi.REQ_DTYPE)
