@@ -1,5 +1,5 @@
 // api.cpp — the C ABI of libsentinel_gpu.so (include/sentinel_gpu.h): handle, rule tables, batch
-// driver. Device work is in engine.hip.
+// driver. Device work is in the .hip files; device and pinned memory is owned through devmem.h's types.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,14 +14,36 @@
 #include <thread>
 #include <vector>
 
+#include "devmem.h"
 #include "engine.h"
 
 using namespace sg;
+
+bool sg::DevAlloc::alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
+void sg::DevAlloc::free(void* p) { (void)hipFree(p); }
+bool sg::PinnedAlloc::alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes) == hipSuccess; }
+void sg::PinnedAlloc::free(void* p) { (void)hipHostFree(p); }
+using Stream = UniqueHandle<hipStream_t, hipError_t, hipStreamDestroy>;
+using Event = UniqueHandle<hipEvent_t, hipError_t, hipEventDestroy>;
+
+// Host-path staging of a handle or a node: device copies of a _host entry point's inputs (slots 0, 2, 3) and of its
+// output (slot 1). The _host entry points are synchronous and none calls another while its staged data is live, so
+// they share the slots; each slot grows to its largest use.
+struct Staging {
+    DevBuf<uint8_t> slot[4];
+    template <class T>
+    bool get(int i, uint64_t n, T*& p) {
+        if (!slot[i].reserve(n * sizeof(T))) return false;
+        p = reinterpret_cast<T*>(slot[i].get());
+        return true;
+    }
+};
 
 constexpr int kAsyncSlots = 3;  // batches of one handle in flight on the host pipeline
 constexpr int kDevSlots = 4;    // device-buffer batches of one handle in flight (sg_flow_enqueue)
 
 struct sg_handle {
+    ~sg_handle();  // makes `device` current and drains the handle's streams before the members free their memory
     int device = 0;
     sg_config cfg{};
     std::string err;
@@ -34,153 +56,146 @@ struct sg_handle {
     int n_wl = 0;
     int32_t wl[kMaxWl]{};
 
-    Rule* d_rules = nullptr;
-    Bucket* d_ring = nullptr;
-    BucketHot* d_hot = nullptr;       // start / PASS / WAITING of every bucket (the short walkers' gather)
-    Occ* d_occ = nullptr;
-    uint32_t* d_seg_end = nullptr;   // [2K] end, then start (k_seg_mark) of each flowId's segment in the sorted records
-    // binned front half (engine.hip k_bin_sort): the hot flowIds of the previous batch and workspace 0's bin buffer
-    uint32_t* d_hot_key = nullptr;    // [kBinHot] flowId per hot slot, then the table [kHotTab] {flowId, slot}
+    DevBuf<Rule> d_rules;
+    DevBuf<Bucket> d_ring;
+    DevBuf<BucketHot> d_hot;          // start / PASS / WAITING of every bucket (the short walkers' gather)
+    DevBuf<Occ> d_occ;
+    // binned front half (engine.hip k_bin_sort): the hot flowIds of the previous batch
+    DevBuf<uint32_t> d_hot_key;       // [kBinHot] flowId per hot slot, then the table [kHotTab] {flowId, slot}
     uint64_t hot_gen = ~0ull;         // rules_gen the hot set was reset for
     uint64_t rules_gen = 0;           // flow rule loads so far (a reload renumbers flowIds: the hot set restarts)
-    uint64_t* d_bin_buf = nullptr;
     int bin_mode = 1;                 // env SG_BIN: 0 off, 1 on for >= 2^14 flowIds, 2 on whenever the records allow
     int prep_tiles = 4;               // env SG_PREP_TILES: sort tiles per k_prep block on the binned path
 
-    // batch workspace (sized for cfg.max_batch)
-    uint64_t* d_rec = nullptr;
-    uint64_t* d_rec_sorted = nullptr;
-    uint64_t* last_sorted = nullptr;  // whichever of d_rec / d_rec_sorted holds the last sort result
-    uint32_t* d_hist = nullptr;       // radix sort histogram workspace
-    uint32_t* d_bnd = nullptr;
-    int64_t* d_p0 = nullptr;
-    uint32_t* d_np = nullptr;
-    int* d_err = nullptr;
-    int64_t* d_last_ts = nullptr;
-    int64_t* d_front_ts = nullptr;    // pipelined limiter batches: last timestamp of the latest accepted front half
-    uint32_t* d_long_list = nullptr;
-    uint32_t* d_long_count = nullptr;  // [4]: long count, short count, work cursors (long, short)
-    uint32_t* d_short_list = nullptr;
-    uint32_t* d_short_key = nullptr;  // flowId of each d_short_list entry (cluster flow path)
-    uint32_t* d_short_end = nullptr;  // segment end of each d_short_list entry (cluster flow path)
-    uint32_t* d_long_key = nullptr;   // flowId of each d_long_list entry (cluster flow path)
-    uint32_t* d_long_end = nullptr;   // segment end of each d_long_list entry (cluster flow path)
-    uint32_t* d_long_pend = nullptr;
-    FidSlot* d_fid = nullptr;         // flowId → rule index (wire codec), 2^k slots
-    uint64_t fid_mask = 0;  // [kLongTab][kLongPeriods] period ends of the long segments
+    // A flow batch's workspace (flow_ws_alloc: sized for cfg.max_batch; seg_end for the loaded rules). Workspace 0
+    // serves every synchronous batch and every other pipelined one; the limiter, cparam, local, pace and node paths
+    // borrow its buffers. Workspace 1 is allocated on the first pipelined batch (pipe_setup).
+    struct FlowWs {
+        DevBuf<uint64_t> rec;
+        DevBuf<uint64_t> rec_sorted;
+        DevBuf<uint32_t> hist;        // radix sort histogram workspace
+        DevBuf<uint32_t> bnd;
+        DevBuf<int64_t> p0;
+        DevBuf<uint32_t> np;
+        DevBuf<int> err;
+        DevBuf<uint32_t> long_list;
+        DevBuf<uint32_t> long_key;    // flowId of each long_list entry (cluster flow path)
+        DevBuf<uint32_t> long_end;    // segment end of each long_list entry (cluster flow path)
+        DevBuf<uint32_t> long_pend;   // [kLongTab][kLongPeriods] period ends of the long segments
+        DevBuf<uint32_t> short_list;
+        DevBuf<uint32_t> short_key;   // flowId of each short_list entry (cluster flow path)
+        DevBuf<uint32_t> short_end;   // segment end of each short_list entry (cluster flow path)
+        DevBuf<uint32_t> counts;      // [1 + kClasses]: long count, short counts per class
+        DevBuf<uint4> skips;
+        DevBuf<uint32_t> skip_count;
+        DevBuf<uint32_t> seg_end;     // [2 * seg_cap] end, then start (k_seg_mark) of each flowId's segment in the
+        uint32_t seg_cap = 0;         // sorted records; seg_cap > K flowIds each (flow_seg_alloc), 0 without rules
+        uint32_t* seg_start = nullptr;  // seg_end + seg_cap, all 0xFFFFFFFF between batches
+        DevBuf<uint64_t> bin_buf;     // binned front half: the regular bins after the scatter (max_batch records)
+    };
+    FlowWs ws[2];
+    uint64_t* last_sorted = nullptr;  // whichever of ws[0].rec / ws[0].rec_sorted holds the last sort result
+    DevBuf<int64_t> d_last_ts;        // {last_ts, front_ts}
+    int64_t* d_front_ts = nullptr;    // d_last_ts + 1. Pipelined limiter batches: last timestamp of the latest accepted front half
+    DevBuf<FidSlot> d_fid;            // flowId → rule index (wire codec), 2^k slots
+    uint64_t fid_mask = 0;
     uint64_t class_off[kClasses]{};
-    unsigned long long* d_dbg = nullptr;   // [128] debug counters (SG_DEBUG & 64)
-    uint4* d_skips = nullptr;
-    uint32_t* d_skip_count = nullptr;
-    int* h_err = nullptr;       // pinned
-    uint32_t* h_long = nullptr; // pinned: long segment count, skipped range count
+    DevBuf<unsigned long long> d_dbg;      // [128] debug counters (SG_DEBUG & 64)
+    PinnedBuf<int> h_err;
+    PinnedBuf<uint32_t> h_long;       // long segment count, skipped range count
 
-    // host-buffer convenience path
-    sg_req* d_req_h = nullptr;
-    sg_result* d_out_h = nullptr;
+    Staging stage;                    // the _host entry points' device copies (host_batch)
 
     // namespace QPS limiters (GlobalRequestLimiter): slot per namespace, device rings and scratch
     std::vector<int> ns_slot;
     int n_lim = 0;
     double lim_qps[kMaxLim]{};
     int lim_wl_idx = -1;
-    LimRing* d_lim_ring = nullptr;
-    uint8_t* d_rule_lim = nullptr;
-    uint8_t* d_lim_slot = nullptr;
-    uint32_t* d_lim_tile = nullptr;   // tile totals then tile offsets
-    uint32_t* d_lim_period = nullptr; // arrivals, prefix, quota
+    DevBuf<LimRing> d_lim_ring;
+    DevBuf<uint8_t> d_rule_lim;
+    DevBuf<uint8_t> d_lim_slot;
+    DevBuf<uint32_t> d_lim_tile;      // tile totals then tile offsets
+    DevBuf<uint32_t> d_lim_period;    // arrivals, prefix, quota
 
     // hot-parameter flow control
     std::vector<sg_param_rule> prules;
     std::vector<PRule> ptab;
-    PRule* d_prules = nullptr;
-    sg_param_hot_item* d_phot = nullptr;
-    PSlot* d_ptable = nullptr;
+    DevBuf<PRule> d_prules;
+    DevBuf<sg_param_hot_item> d_phot;
+    DevBuf<PSlot> d_ptable;
     uint64_t ptotal = 0;             // slots over all rule sub-tables
-    int64_t* d_plast_ts = nullptr;
-    sg_param_req* d_preq_h = nullptr;
-    int32_t* d_pout_h = nullptr;
+    DevBuf<int64_t> d_plast_ts;
 
     // pace controller (RateLimiterController per FlowRule)
     std::vector<PaceRule> pace_tab;
-    PaceRule* d_pace_rules = nullptr;
-    int64_t* d_pace_latest = nullptr;
-    int64_t* d_pace_last_ts = nullptr;
-    sg_pace_req* d_pace_req_h = nullptr;
-    int32_t* d_pace_out_h = nullptr;
+    DevBuf<PaceRule> d_pace_rules;
+    DevBuf<int64_t> d_pace_latest;
+    DevBuf<int64_t> d_pace_last_ts;
 
     // cluster hot-parameter tokens
     std::vector<sg_cparam_rule> cprules;
     std::vector<CPRule> cptab;
-    CPRule* d_cprules = nullptr;
-    sg_param_hot_item* d_cphot = nullptr;
-    uint64_t* d_cpkeys = nullptr;
-    CPBucket* d_cpring = nullptr;
+    DevBuf<CPRule> d_cprules;
+    DevBuf<sg_param_hot_item> d_cphot;
+    DevBuf<uint64_t> d_cpkeys;
+    DevBuf<CPBucket> d_cpring;
     uint64_t cptotal = 0;
     int cpstride = 1;
-    int64_t* d_cplast_ts = nullptr;
+    DevBuf<int64_t> d_cplast_ts;
     // one-pipeline batch scratch (value-position records, fixed point over multi-value requests)
-    uint32_t* d_cp_owner = nullptr;
-    uint32_t* d_cp_pslot = nullptr;
-    uint32_t* d_cp_long = nullptr;    // segment lists over the value records (capacity cp_val_cap)
-    uint32_t* d_cp_short = nullptr;
+    DevBuf<uint32_t> d_cp_owner;
+    DevBuf<uint32_t> d_cp_pslot;
+    DevBuf<uint32_t> d_cp_long;       // segment lists over the value records (capacity cp_val_cap)
+    DevBuf<uint32_t> d_cp_short;
     uint64_t cp_class_off[kClasses]{};
-    uint32_t* d_p_msb = nullptr;      // hot-parameter batch: first request index of each millisecond
-    int64_t* d_p_mt = nullptr;        // its first timestamp, then the millisecond count (uint32)
-    uint16_t* d_p_mbk = nullptr;      // pace: the millisecond of every kPcBuckets-th request
+    DevBuf<uint32_t> d_p_msb;         // hot-parameter batch: first request index of each millisecond
+    DevBuf<int64_t> d_p_mt;           // its first timestamp, then the millisecond count (uint32)
+    DevBuf<uint16_t> d_p_mbk;         // pace: the millisecond of every kPcBuckets-th request
     std::vector<int32_t> cp_wls;      // distinct window lengths of the cluster param rules (CPRule::wl_idx)
-    uint32_t* d_cp_bnd = nullptr;     // [kMaxWl][kMaxPeriods] the batch's period tables (request index -> period)
-    int64_t* d_cp_p0 = nullptr;
-    uint32_t* d_cp_np = nullptr;
-    uint32_t* d_cp_slot_item = nullptr;  // [cptotal] work item of each touched slot (k_cp_items)
-    uint64_t cp_slot_item_cap = 0;
-    uint32_t* d_cp_items = nullptr;   // [4 * cp_val_cap] per work item: re-walk flag, segment start; re-walk lists x2
-    uint32_t* d_cp_counts = nullptr;  // [6]: re-walk list counts (2 buffers x {long, short}), multi-value count
-    uint32_t* d_cp_mlist = nullptr;   // [max_batch] multi-value requests
-    uint8_t* d_cp_chk = nullptr;
-    uint8_t* d_cp_assume = nullptr;
-    uint64_t* d_cp_rec = nullptr;
-    uint64_t* d_cp_rec2 = nullptr;
-    uint32_t* d_cp_hist = nullptr;
-    uint64_t cp_val_cap = 0;
-    CPBucket* d_cp_save = nullptr;
-    CPBucket* d_cp_ckpt = nullptr;    // hot-slot ring checkpoints, one per window period of the batch
-    uint64_t cp_ckpt_cap = 0;
-    uint2* d_cp_skips = nullptr;      // saturated ranges of the hot-slot walker (k_cp_skipfill), [cp_skip_cap]
-    uint32_t* d_cp_skip_count = nullptr;
-    uint64_t cp_skip_cap = 0;
-    uint64_t cp_save_cap = 0;
-    int* d_cp_changed = nullptr;
-    uint8_t* d_cp_rule_lim = nullptr; // [cparam rules] limiter slot of the rule's namespace (0xFF none)
+    DevBuf<uint32_t> d_cp_bnd;        // [kMaxWl][kMaxPeriods] the batch's period tables (request index -> period)
+    DevBuf<int64_t> d_cp_p0;
+    DevBuf<uint32_t> d_cp_np;
+    DevBuf<uint32_t> d_cp_slot_item;     // [cptotal] work item of each touched slot (k_cp_items)
+    DevBuf<uint32_t> d_cp_items;      // [4 * cp_val_cap] per work item: re-walk flag, segment start; re-walk lists x2
+    DevBuf<uint32_t> d_cp_counts;     // [6]: re-walk list counts (2 buffers x {long, short}), multi-value count
+    DevBuf<uint32_t> d_cp_mlist;      // [max_batch] multi-value requests
+    DevBuf<uint8_t> d_cp_chk;
+    DevBuf<uint8_t> d_cp_assume;
+    DevBuf<uint64_t> d_cp_rec;
+    DevBuf<uint64_t> d_cp_rec2;
+    DevBuf<uint32_t> d_cp_hist;
+    uint64_t cp_val_cap = 0;          // value positions the scratch above is laid out for (cp_class_off follows it)
+    DevBuf<CPBucket> d_cp_save;
+    DevBuf<CPBucket> d_cp_ckpt;       // hot-slot ring checkpoints, one per window period of the batch
+    DevBuf<uint2> d_cp_skips;         // saturated ranges of the hot-slot walker (k_cp_skipfill), [size()]
+    DevBuf<uint32_t> d_cp_skip_count;
+    DevBuf<int> d_cp_changed;
+    DevBuf<uint8_t> d_cp_rule_lim;    // [cparam rules] limiter slot of the rule's namespace (0xFF none)
     std::vector<uint8_t> cp_rule_lim_host;
     bool cp_any_lim = false;          // some cluster param rule's namespace has a limiter
     uint32_t cp_rounds = 0;           // fixed-point rounds of the last batch (stats / tests)
     uint32_t cp_max_rounds = 64;      // env SG_CP_MAX_ROUNDS overrides (tests force the serial fallback)
-    sg_cparam_req* d_cpreq_h = nullptr;
-    uint64_t* d_cpval_h = nullptr;
-    uint64_t cpval_cap = 0;
-    sg_result* d_cpout_h = nullptr;
 
     // param-flow wire codec: flowId → cluster param rule index, and the value dictionary (pcodec.hip)
-    FidSlot* d_cpfid = nullptr;
+    DevBuf<FidSlot> d_cpfid;
     uint64_t cpfid_mask = 0;
     struct VDict {
         bool on = false;
         uint64_t capacity = 0, arena_bytes = 0, max_batch = 0;
         uint64_t count = 0, arena_used = 0;   // the device state's size: every batch ends with the host knowing it
-        uint64_t* tab = nullptr;
+        DevBuf<uint64_t> tab;
         uint64_t tab_mask = 0;
-        VEntry* entries = nullptr;
-        uint8_t* arena = nullptr;
-        VDesc* desc = nullptr;                // batch scratch, max_batch values
-        uint64_t* hash = nullptr;
-        uint32_t* slot_of = nullptr;
-        uint32_t* dedupe = nullptr;           // dedupe_slots >= 2 * max_batch
+        DevBuf<VEntry> entries;
+        DevBuf<uint8_t> arena;
+        DevBuf<VDesc> desc;                   // batch scratch, max_batch values
+        DevBuf<uint64_t> hash;
+        DevBuf<uint32_t> slot_of;
+        DevBuf<uint32_t> dedupe;              // dedupe_slots >= 2 * max_batch
         uint64_t dedupe_slots = 0;
-        uint64_t* scan = nullptr;
-        uint64_t* sums = nullptr;             // scan workspace for max(max_batch values, cfg.max_batch frames)
-        uint64_t* cnt = nullptr;              // [cfg.max_batch] values per frame / value_begin
-        uint64_t* totals = nullptr;           // [2] device: scan total, miss count
+        DevBuf<uint64_t> scan;
+        DevBuf<uint64_t> sums;                // scan workspace for max(max_batch values, cfg.max_batch frames)
+        DevBuf<uint64_t> cnt;                 // [cfg.max_batch] values per frame / value_begin
+        DevBuf<uint64_t> totals;              // [2] device: scan total, miss count
     } vd;
 
     // local slot chain
@@ -190,41 +205,37 @@ struct sg_handle {
     int32_t l_n_origins = 0;
     bool l_has_cx = false;
     std::vector<int64_t> l_rule_slot; // loaded flow rule i → its LCtl index, -2 stateless fast-path rule, -1 ignored
-    LFlowRule* d_lfrules = nullptr;
-    LCtl* d_lctl = nullptr;
-    int64_t* d_llast_fetch = nullptr; // [K] StatisticNode.lastFetchTime
-    LRule* d_lrules = nullptr;
-    LHead* d_lhead = nullptr;
-    LBucket* d_lsec = nullptr;
-    LFuture* d_lbor = nullptr;
-    LBucket* d_lmin = nullptr;
-    int64_t* d_llast_ts = nullptr;
+    DevBuf<LFlowRule> d_lfrules;
+    DevBuf<LCtl> d_lctl;
+    DevBuf<int64_t> d_llast_fetch;    // [K] StatisticNode.lastFetchTime
+    DevBuf<LRule> d_lrules;
+    DevBuf<LHead> d_lhead;
+    DevBuf<LBucket> d_lsec;
+    DevBuf<LFuture> d_lbor;
+    DevBuf<LBucket> d_lmin;
+    DevBuf<int64_t> d_llast_ts;
     int l_n_wl = 0, l_wsec = 0, l_wmin = 0;
     int32_t l_wl[kMaxWl]{};
-    sg_local_event* d_lev_h = nullptr;
     struct LocalWs {                  // the local path's own batch buffers of a pipeline workspace (0: every local
-        int* flags = nullptr;         // batch; 1: every other sg_local_enqueue batch), sized for max_batch
-        uint32_t* exit_pos = nullptr;
-        uint32_t* exit_cnt = nullptr;
-        LSkip* skips = nullptr;
-        uint32_t* skip_count = nullptr;
-        uint64_t* pslot = nullptr;    // [max_batch] LArgs::pslot (param rules loaded and the cx wave walker on)
-        CxSide* cxside = nullptr;     // [max_batch] LArgs::cxside (with pslot)
-        uint32_t* cxw_next = nullptr; // LArgs::cxw_next
-        uint32_t* cx_list = nullptr;  // [max_batch + 1] LArgs::cx_list, then cx_count (cx resources loaded)
+        DevBuf<int> flags;            // batch; 1: every other sg_local_enqueue batch), sized for max_batch
+        DevBuf<uint32_t> exit_pos;
+        DevBuf<uint32_t> exit_cnt;
+        DevBuf<LSkip> skips;
+        DevBuf<uint32_t> skip_count;
+        DevBuf<uint64_t> pslot;       // [max_batch] LArgs::pslot (param rules loaded and the cx wave walker on)
+        DevBuf<CxSide> cxside;        // [max_batch] LArgs::cxside (with pslot)
+        DevBuf<uint32_t> cxw_next;    // LArgs::cxw_next
+        DevBuf<uint32_t> cx_list;     // [max_batch + 1] LArgs::cx_list, then cx_count (cx resources loaded)
     };
     LocalWs lws[2];
-    uint32_t lskip_cap = 0;
-    sg_local_result* d_lout_h = nullptr;
     // node pool (origin nodes, context DefaultNodes; created by the batches, kept across flow-rule reloads)
     uint32_t l_pool_cap = 0, l_pool_used = 0;
-    uint64_t* d_lnkeys = nullptr;     // map (resource, kind, id) → node, l_nmap_cap slots
-    uint32_t* d_lnvals = nullptr;
-    uint64_t l_nmap_cap = 0;
-    uint32_t* d_lnode_new = nullptr;  // pool nodes a batch created
-    uint32_t* h_lnode_new = nullptr;  // pinned
-    uint2* d_lev_node = nullptr;      // [max_batch] map slots of each event's nodes
-    uint32_t* d_ldyn = nullptr;       // [K] batch epoch of each resource's last origin event
+    DevBuf<uint64_t> d_lnkeys;        // map (resource, kind, id) → node, size() slots (a power of two)
+    DevBuf<uint32_t> d_lnvals;
+    DevBuf<uint32_t> d_lnode_new;     // pool nodes a batch created
+    PinnedBuf<uint32_t> h_lnode_new;  // pinned
+    DevBuf<uint2> d_lev_node;         // [max_batch] map slots of each event's nodes
+    DevBuf<uint32_t> d_ldyn;          // [K] batch epoch of each resource's last origin event
     uint32_t l_epoch = 0;
     uint64_t l_batches = 0;           // local batches decided since sg_local_load_rules
     int32_t l_n_contexts = 0;
@@ -234,22 +245,20 @@ struct sg_handle {
     std::vector<std::pair<uint32_t, uint32_t>> l_relate;        // RELATE (resource, referenced resource)
     std::vector<std::pair<uint32_t, uint32_t>> l_cluster_refs;  // cluster-mode rules: (resource, cluster_key)
     bool l_groups_stale = false;      // cluster rules / namespaces / cluster state changed: regroup before a batch
-    uint32_t* d_lgkey = nullptr;      // [K] RELATE key groups (record key of each resource), null without groups
+    DevBuf<uint32_t> d_lgkey;         // [K] RELATE key groups (record key of each resource), null without groups
     uint64_t l_ps_applied = 0;        // ps_gen whose param flags d_lrules carries (0: none)
     bool l_has_cx_ps = false;         // some resource is cx because of param rules
-    sg_slot_ext* d_lext_h = nullptr;  // host-path buffers of sg_slot_decide_batch_host
-    uint8_t* d_linbound = nullptr;    // [K] EntryType.IN resources (sg_local_set_entry_types), null = none
-    LBucket* d_lentry_acc = nullptr;  // [60] the ENTRY_NODE's buckets, summed per metric call
-    unsigned long long* d_lm_cnt = nullptr;  // the metric passes' row counter
-    int64_t* d_lentry_fetch = nullptr;// the ENTRY_NODE's lastFetchTime
+    DevBuf<uint8_t> d_linbound;       // [K] EntryType.IN resources (sg_local_set_entry_types), null = none
+    DevBuf<LBucket> d_lentry_acc;     // [60] the ENTRY_NODE's buckets, summed per metric call
+    DevBuf<unsigned long long> d_lm_cnt;     // the metric passes' row counter
+    DevBuf<int64_t> d_lentry_fetch;   // the ENTRY_NODE's lastFetchTime
 
     int kbits = 0, ibits = 0, abits = 0;
     int32_t shard_rank = 0, shard_world = 1;  // sg_set_shard: this handle's share of a node's flowIds
     // sg_lim_exchange: the node's gathered per-millisecond limiter arrivals for the next flow batch of a shard
-    uint32_t* d_xg_ws[2]{};           // the gathered arrivals a pipelined batch of workspace x reads (copied at enqueue)
-    uint64_t xg_ws_cap = 0;           // words per buffer
-    int* d_limx_err = nullptr;        // sg_lim_arrivals' own error word (the pipelined batches keep theirs)
-    int* h_limx_err = nullptr;        // pinned
+    DevBuf<uint32_t> d_xg_ws[2];         // the gathered arrivals a pipelined batch of workspace x reads (copied at enqueue)
+    DevBuf<int> d_limx_err;           // sg_lim_arrivals' own error word (the pipelined batches keep theirs)
+    PinnedBuf<int> h_limx_err;        // pinned
     const uint32_t* lim_xg = nullptr;
     int64_t lim_xt = 0;
     uint32_t lim_xn = 0;
@@ -257,34 +266,32 @@ struct sg_handle {
     // ParamFlowSlot chain (sg_pslot_*)
     uint32_t ps_nres = 0;
     bool ps_loaded = false;
-    uint32_t* d_ps_begin = nullptr;
-    uint32_t* d_ps_rules = nullptr;
-    int32_t* d_ps_grade = nullptr;
-    int32_t* d_ps_idx = nullptr;
-    int32_t* d_ps_init = nullptr;
-    PSThread* d_ps_tc = nullptr;
+    DevBuf<uint32_t> d_ps_begin;
+    DevBuf<uint32_t> d_ps_rules;
+    DevBuf<int32_t> d_ps_grade;
+    DevBuf<int32_t> d_ps_idx;
+    DevBuf<int32_t> d_ps_init;
+    DevBuf<PSThread> d_ps_tc;
     uint64_t ps_tc_slots = 0;
-    int64_t* d_ps_last_ts = nullptr;
+    DevBuf<int64_t> d_ps_last_ts;
     std::vector<uint32_t> ps_res_rules;  // param rules per resource
     uint64_t ps_gen = 0;              // sg_pslot_load_rules calls so far
-    int32_t* d_ps_cmode = nullptr;    // per rule: SG_CLUSTER_MODE_*
-    uint32_t* d_ps_ckey = nullptr;    // per rule: its flowId's cluster param rule index (embedded server)
+    DevBuf<int32_t> d_ps_cmode;       // per rule: SG_CLUSTER_MODE_*
+    DevBuf<uint32_t> d_ps_ckey;       // per rule: its flowId's cluster param rule index (embedded server)
     bool ps_cluster = false;          // some loaded param rule is a cluster-mode QPS rule
     std::vector<std::pair<uint32_t, uint32_t>> ps_cluster_refs;  // (resource, cluster_key) of those rules
-    uint32_t* d_ps_gkey = nullptr;    // [n_res] key groups of sg_pslot_decide_batch on an embedded server, or null
+    DevBuf<uint32_t> d_ps_gkey;       // [n_res] key groups of sg_pslot_decide_batch on an embedded server, or null
     bool ps_groups_stale = true;      // param rules / cluster param rules / namespaces / state changed
     // concurrent cluster tokens (sg_conc_*)
-    int32_t* d_cnow = nullptr;        // nowCalls per rule
-    double* d_cthr = nullptr;
-    int64_t* d_coff = nullptr;
-    int64_t* d_cres = nullptr;
-    int64_t* d_cfid = nullptr;
-    CTok* d_ctok = nullptr;
+    DevBuf<int32_t> d_cnow;           // nowCalls per rule
+    DevBuf<double> d_cthr;
+    DevBuf<int64_t> d_coff;
+    DevBuf<int64_t> d_cres;
+    DevBuf<int64_t> d_cfid;
+    DevBuf<CTok> d_ctok;
     uint64_t ctok_slots = 0, ctok_used = 0;  // table size; slots taken since the last rehash (upper bound)
-    uint8_t* d_calive = nullptr;
-    int64_t* d_clast_ts = nullptr;
-    sg_conc_req* d_creq_h = nullptr;
-    sg_conc_result* d_cout_h = nullptr;
+    DevBuf<uint8_t> d_calive;
+    DevBuf<int64_t> d_clast_ts;
     uint64_t conc_seq = 0;            // requests decided so far (token ids)
     bool conc_dirty = true;           // rules / namespaces / timeouts changed since the last upload
     bool cnow_pending = false;        // cnow_host holds the remapped counters of a rule reload
@@ -293,13 +300,13 @@ struct sg_handle {
     // asynchronous host pipeline (sg_flow_submit): H2D / compute / D2H streams, kAsyncSlots batches in flight
     struct Slot {
         uint64_t ticket = 0;            // 0 = free
-        sg_req* d_req = nullptr;
-        sg_result* d_out = nullptr;
-        int* h_err = nullptr;           // pinned: the batch's error flags
-        hipEvent_t h2d = nullptr, comp = nullptr, d2h = nullptr;
+        DevBuf<sg_req> d_req;
+        DevBuf<sg_result> d_out;
+        PinnedBuf<int> h_err;           // pinned: the batch's error flags
+        Event h2d, comp, d2h;
     };
     Slot slots[kAsyncSlots];
-    hipStream_t s_in = nullptr, s_comp = nullptr, s_out = nullptr;
+    Stream s_in, s_comp, s_out;
     uint64_t next_ticket = 1;
     std::unordered_map<uint64_t, int> finished;  // tickets completed while making room, not yet collected
     bool stats_on = false;
@@ -309,56 +316,33 @@ struct sg_handle {
     int l_cxw = 1;                    // env SG_CXW=0: long cx segments on the lane walker too (LArgs::cxw)
     uint32_t l_cxw_min = 0xFFFFFFFFu;          // env SG_CXW_MIN: shortest cx segment class the wave walker takes (LArgs::cxw_cls)
     bool wide_seen = false;           // some loaded rule allowed bucket counts >= 2^30 (sticky: the ring keeps them)
-    hipEvent_t ev[5]{};
+    Event ev[5];
     sg_batch_stats stats{};
-    hipStream_t aux = nullptr;        // second stream: the long-segment walker runs beside the short one
-    hipEvent_t fork = nullptr, join = nullptr;
+    Stream aux;        // second stream: the long-segment walker runs beside the short one
+    Event fork, join;
     // Pipelined flow batches (sg_flow_enqueue, sg_flow_submit): the front half of a batch (validation, sort,
-    // segments) runs on s_front while the previous batch's walkers run on s_back. Two workspaces alternate:
-    // workspace 0 is the handle's own batch buffers above, workspace 1 (pws) is allocated on first use.
-    struct FlowWs {
-        uint64_t* rec = nullptr;
-        uint64_t* rec_sorted = nullptr;
-        uint32_t* hist = nullptr;
-        uint32_t* bnd = nullptr;
-        int64_t* p0 = nullptr;
-        uint32_t* np = nullptr;
-        int* err = nullptr;
-        uint32_t* long_list = nullptr;
-        uint32_t* long_key = nullptr;
-        uint32_t* long_end = nullptr;
-        uint32_t* long_pend = nullptr;
-        uint32_t* short_list = nullptr;
-        uint32_t* short_key = nullptr;
-        uint32_t* counts = nullptr;   // [1 + kClasses]: long count, short counts per class
-        uint4* skips = nullptr;
-        uint32_t* skip_count = nullptr;
-        uint32_t* seg_end = nullptr;  // [K]
-        uint32_t* seg_start = nullptr;  // [K], all 0xFFFFFFFF between batches
-        uint32_t* short_end = nullptr;
-        uint64_t* bin_buf = nullptr;    // binned front half: the regular bins after the scatter (max_batch records)
-    };
-    FlowWs pws{};
-    uint32_t pws_segcap = 0;
-    hipStream_t s_front = nullptr, s_back = nullptr, s_aux2 = nullptr;
-    hipStream_t s_aux3 = nullptr;     // the length-class-0 walker beside the other two (SG_DEBUG & 128, tuning)
-    hipEvent_t tjoin = nullptr;
-    hipStream_t s_xcopy = nullptr;    // the sharded limiter exchange's copy into a pipeline workspace
-    hipEvent_t xcopy_done = nullptr;
-    hipEvent_t front_done[2]{}, back_done[2]{}, pfork = nullptr, pjoin = nullptr;
-    hipEvent_t lm_in = nullptr, lm_done = nullptr;  // sg_local_metrics_raw_enqueue: the caller's stream <-> s_back
-    int* d_lm_gate = nullptr;                        // its capacity gate (count <= cap)
+    // segments) runs on s_front while the previous batch's walkers run on s_back. The workspaces ws[0] / ws[1] alternate.
+    Stream s_front, s_back, s_aux2;
+    Stream s_aux3;     // the length-class-0 walker beside the other two (SG_DEBUG & 128, tuning)
+    Event tjoin;
+    Stream s_xcopy;    // the sharded limiter exchange's copy into a pipeline workspace
+    Event xcopy_done;
+    Event front_done[2], back_done[2], pfork, pjoin;
+    Event lm_in, lm_done;  // sg_local_metrics_raw_enqueue: the caller's stream <-> s_back
+    DevBuf<int> d_lm_gate;                           // its capacity gate (count <= cap)
     uint64_t pipe_seq = 0;            // batches put on the pipeline so far (workspace = seq % 2)
     bool d2h_kernel = false;          // sg_flow_submit: results to pinned host buffers by k_copy_out (env SG_D2H=1; the
                                       // copy engine measured faster: 2.64 vs 2.45 G decisions/s end to end)
     int d2h_blocks = 64;              // its workgroups (env SG_D2H_BLOCKS)
     int front_eighths = 4;            // CU partition of the pipeline streams (pipe_setup; round 6: the binned front half
                                       // (k_bin_sort) takes 4/8, -2.5 % against 3/8; the two-pass sort measures the same at 3 or 4)
+    bool cu_blocked = false;          // env SG_CU_BLOCKED=1 (tuning): the front half gets CUs i with i / (cus / 8) < k
+                                      // (contiguous eighths); both read once in sg_create
     int walk_cus = 0;                 // CUs of the walkers' streams when partitioned (0 = all)
     struct DevTicket {                // sg_flow_enqueue batches in flight
         uint64_t ticket = 0;
-        int* h_err = nullptr;         // pinned
-        hipEvent_t done = nullptr;
+        PinnedBuf<int> h_err;         // pinned
+        Event done;
         bool local = false;           // an sg_local_enqueue batch (its error flags map through local_status)
     };
     DevTicket dev[kDevSlots];
@@ -398,16 +382,33 @@ int fail(sg_handle* h, int code, const std::string& msg) {
             return fail((h), SG_E_DEVICE, std::string(#expr ": ") + hipGetErrorString(_e));     \
     } while (0)
 
+// A _host entry point after its argument checks, for a handle or a node `o` (device: where its staging lives):
+// n requests up, call(d_req, d_out) on the staged copies, n results down.
+template <class O, class Req, class Out, class Call>
+int host_batch(O* o, int device, const Req* req, uint64_t n, Out* out, Call call) {
+    auto bad = [&](int code, const std::string& msg) {
+        o->err = msg;
+        return code;
+    };
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return bad(SG_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    Req* d_req = nullptr;
+    Out* d_out = nullptr;
+    if (!o->stage.get(0, o->cfg.max_batch, d_req) || !o->stage.get(1, o->cfg.max_batch, d_out))
+        return bad(SG_E_NOMEM, "host-path buffers");
+    e = hipMemcpy(d_req, req, sizeof(Req) * n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return bad(SG_E_DEVICE, std::string("host-path upload: ") + hipGetErrorString(e));
+    const int rc = call(d_req, d_out);
+    if (rc) return rc;
+    e = hipMemcpy(out, d_out, sizeof(Out) * n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return bad(SG_E_DEVICE, std::string("host-path download: ") + hipGetErrorString(e));
+    return SG_OK;
+}
+
 int bits_for(uint64_t v) {  // bits needed to represent v (v >= 1)
     int b = 0;
     while (b < 64 && (v >> b) != 0) ++b;
     return b;
-}
-
-template <class T>
-void dfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
 }
 
 // calcGlobalThreshold(rule) * exceedCount (ClusterFlowChecker.java:38-48, :68)
@@ -495,16 +496,39 @@ int upload_rule_table(sg_handle* h) {
     }
     if (h->K) HIP_TRY(h, hipMemcpy(h->d_rules, h->rule_tab.data(), sizeof(Rule) * h->K, hipMemcpyHostToDevice));
     // limiter slot of each rule's namespace
-    dfree(h->d_rule_lim);
+    h->d_rule_lim.reset();
     if (h->K) {
         std::vector<uint8_t> rl(h->K, 0xFF);
         for (uint32_t k = 0; k < h->K; ++k) {
             const int ns = h->rules[k].namespace_id;
             if (ns >= 0 && (size_t)ns < h->ns_slot.size() && h->ns_slot[ns] >= 0) rl[k] = (uint8_t)h->ns_slot[ns];
         }
-        if (hipMalloc(&h->d_rule_lim, h->K) != hipSuccess) return fail(h, SG_E_NOMEM, "rule limiter table");
+        if (!h->d_rule_lim.alloc_bytes(h->K)) return fail(h, SG_E_NOMEM, "rule limiter table");
         HIP_TRY(h, hipMemcpy(h->d_rule_lim, rl.data(), h->K, hipMemcpyHostToDevice));
     }
+    return SG_OK;
+}
+
+// A flow workspace's batch buffers for cfg.max_batch requests (class_off set): everything but seg_end, which follows
+// the loaded rules (flow_seg_alloc), and bin_buf (bin_setup, on the first binned batch).
+bool flow_ws_alloc(sg_handle* h, sg_handle::FlowWs& w) {
+    const uint64_t n = h->cfg.max_batch;
+    const uint64_t short_words = h->class_off[kClasses - 1] + n / (kClassMax[kClasses - 2] + 1) + 1;
+    // + kRecW records of slack: the short walker stages record windows past a segment's end unclamped
+    return w.rec.alloc(n + kRecW) && w.rec_sorted.alloc(n + kRecW) && w.hist.alloc(radix_hist_words(n)) &&
+           w.bnd.alloc((size_t)kMaxWl * kMaxPeriods) && w.p0.alloc(kMaxWl) && w.np.alloc(kMaxWl) && w.err.alloc(1) &&
+           w.long_list.alloc(n + 1) && w.long_key.alloc(n + 1) && w.long_end.alloc(n + 1) &&
+           w.long_pend.alloc((size_t)kLongTab * kLongPeriods) && w.short_list.alloc(short_words) &&
+           w.short_key.alloc(short_words) && w.short_end.alloc(short_words) && w.counts.alloc(1 + kClasses) &&
+           w.skips.alloc(2 * n / kSkipMin + 1) && w.skip_count.alloc(1);
+}
+
+// Segment marks for K flowIds: [K + 1] ends (none marked: 0), then [K + 1] starts (none marked: 0xFFFFFFFF).
+int flow_seg_alloc(sg_handle* h, DevBuf<uint32_t>& seg, uint32_t K) {
+    const size_t cap = (size_t)K + 1;
+    if (!seg.alloc(2 * cap)) return fail(h, SG_E_NOMEM, "segment marks");
+    HIP_TRY(h, hipMemset(seg, 0, sizeof(uint32_t) * cap));
+    HIP_TRY(h, hipMemset(seg + cap, 0xFF, sizeof(uint32_t) * cap));
     return SG_OK;
 }
 
@@ -525,58 +549,37 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
     h->cfg = *cfg;
     h->device = cfg->device;
     auto bail = [&](int rc) {
-        sg_destroy(h);
+        delete h;
         return rc;
     };
     if (hipSetDevice(h->device) != hipSuccess) return bail(SG_E_DEVICE);
     const uint64_t n = cfg->max_batch;
-    // + kRecW records of slack: the short walker stages record windows past a segment's end unclamped
-    if (hipMalloc(&h->d_rec, (n + kRecW) * 8) != hipSuccess || hipMalloc(&h->d_rec_sorted, (n + kRecW) * 8) != hipSuccess)
-        return bail(SG_E_NOMEM);
-    if (hipMalloc(&h->d_bnd, sizeof(uint32_t) * kMaxWl * kMaxPeriods) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipMalloc(&h->d_hist, sizeof(uint32_t) * radix_hist_words(n)) != hipSuccess) return bail(SG_E_NOMEM);
-    {
-        const uint64_t tiles = n / 4096 + 1;
-        if (hipMalloc(&h->d_lim_ring, sizeof(LimRing) * kMaxLim) != hipSuccess ||
-            hipMalloc(&h->d_lim_slot, n) != hipSuccess ||
-            hipMalloc(&h->d_lim_tile, sizeof(uint32_t) * tiles * kMaxLim * 2) != hipSuccess ||
-            hipMalloc(&h->d_lim_period, sizeof(uint32_t) * kMaxLim * kMaxPeriods * 3) != hipSuccess)
-            return bail(SG_E_NOMEM);
-    }
-    if (hipMalloc(&h->d_p0, sizeof(int64_t) * kMaxWl) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipMalloc(&h->d_np, sizeof(uint32_t) * kMaxWl) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipMalloc(&h->d_err, sizeof(int)) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipMalloc(&h->d_last_ts, 2 * sizeof(int64_t)) != hipSuccess) return bail(SG_E_NOMEM);  // + front_ts
-    if (hipMalloc(&h->d_long_list, sizeof(uint32_t) * (n + 1)) != hipSuccess ||
-        hipMalloc(&h->d_long_key, sizeof(uint32_t) * (n + 1)) != hipSuccess ||
-        hipMalloc(&h->d_long_end, sizeof(uint32_t) * (n + 1)) != hipSuccess ||
-        hipMalloc(&h->d_long_pend, sizeof(uint32_t) * (size_t)kLongTab * kLongPeriods) != hipSuccess)
-        return bail(SG_E_NOMEM);
     {  // short-segment class slices: class c holds segments longer than kClassMax[c-1], so at most n/(that+1)
         uint64_t off = 0;
         for (int c = 0; c < kClasses; ++c) {
             h->class_off[c] = off;
             off += (c == 0 ? n : n / (kClassMax[c - 1] + 1)) + 1;
         }
-        if (hipMalloc(&h->d_short_list, sizeof(uint32_t) * off) != hipSuccess ||
-            hipMalloc(&h->d_short_key, sizeof(uint32_t) * off) != hipSuccess ||
-            hipMalloc(&h->d_short_end, sizeof(uint32_t) * off) != hipSuccess)
+    }
+    if (!flow_ws_alloc(h, h->ws[0])) return bail(SG_E_NOMEM);
+    {
+        const uint64_t tiles = n / 4096 + 1;
+        if (!h->d_lim_ring.alloc(kMaxLim) || !h->d_lim_slot.alloc(n) || !h->d_lim_tile.alloc(tiles * kMaxLim * 2) ||
+            !h->d_lim_period.alloc((size_t)kMaxLim * kMaxPeriods * 3))
             return bail(SG_E_NOMEM);
     }
-    if (hipMalloc(&h->d_dbg, 128 * 8) != hipSuccess || hipMemset(h->d_dbg, 0, 128 * 8) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipMalloc(&h->d_long_count, (1 + kClasses) * sizeof(uint32_t)) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipMalloc(&h->d_skips, sizeof(uint4) * (2 * n / kSkipMin + 1)) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipMalloc(&h->d_skip_count, sizeof(uint32_t)) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipHostMalloc(&h->h_err, sizeof(int)) != hipSuccess) return bail(SG_E_NOMEM);
-    if (hipHostMalloc(&h->h_long, 2 * sizeof(uint32_t)) != hipSuccess) return bail(SG_E_NOMEM);
+    if (!h->d_last_ts.alloc(2)) return bail(SG_E_NOMEM);  // + front_ts
+    if (!h->d_dbg.alloc(128) || hipMemset(h->d_dbg, 0, 128 * 8) != hipSuccess) return bail(SG_E_NOMEM);
+    if (!h->h_err.alloc_bytes(sizeof(int))) return bail(SG_E_NOMEM);
+    if (!h->h_long.alloc_bytes(2 * sizeof(uint32_t))) return bail(SG_E_NOMEM);
     int64_t neg = -1;
     if (hipMemcpy(h->d_last_ts, &neg, sizeof(neg), hipMemcpyHostToDevice) != hipSuccess) return bail(SG_E_DEVICE);
     h->d_front_ts = h->d_last_ts + 1;
     if (hipMemcpy(h->d_front_ts, &neg, sizeof(neg), hipMemcpyHostToDevice) != hipSuccess) return bail(SG_E_DEVICE);
-    if (hipMalloc(&h->d_plast_ts, sizeof(int64_t)) != hipSuccess) return bail(SG_E_NOMEM);
+    if (!h->d_plast_ts.alloc_bytes(sizeof(int64_t))) return bail(SG_E_NOMEM);
     if (hipMemcpy(h->d_plast_ts, &neg, sizeof(neg), hipMemcpyHostToDevice) != hipSuccess) return bail(SG_E_DEVICE);
     for (auto& e : h->ev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(SG_E_DEVICE);
+        if (hipEventCreate(e.put()) != hipSuccess) return bail(SG_E_DEVICE);
     // the auxiliary stream carries the wave walkers beside the lane walkers (pace, hot params, cluster params);
     // env SG_AUX_PRIO=1 (tuning) creates it at the highest stream priority
     int aux_prio = 0;
@@ -584,9 +587,9 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) aux_prio = greatest;
     }
-    if (hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, aux_prio) != hipSuccess ||
-        hipEventCreateWithFlags(&h->fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->join, hipEventDisableTiming) != hipSuccess)
+    if (hipStreamCreateWithPriority(h->aux.put(), hipStreamNonBlocking, aux_prio) != hipSuccess ||
+        hipEventCreateWithFlags(h->fork.put(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(h->join.put(), hipEventDisableTiming) != hipSuccess)
         return bail(SG_E_DEVICE);
     if (const char* d = std::getenv("SG_DEBUG")) h->dbg = std::atoi(d);
     if (const char* d = std::getenv("SG_CXW")) h->l_cxw = std::atoi(d) != 0 ? 1 : 0;
@@ -595,6 +598,8 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
     if (const char* d = std::getenv("SG_SEG_MARK")) h->seg_mark_pass = std::atoi(d) != 0;
     if (const char* d = std::getenv("SG_LIM_PIPE")) h->lim_pipe = std::atoi(d) != 0;
     if (const char* d = std::getenv("SG_BIN")) h->bin_mode = std::atoi(d);
+    if (const char* d = std::getenv("SG_FRONT_EIGHTHS")) h->front_eighths = std::atoi(d);
+    if (const char* d = std::getenv("SG_CU_BLOCKED")) h->cu_blocked = std::atoi(d) == 1;
     if (const char* d = std::getenv("SG_PREP_TILES")) h->prep_tiles = std::max(1, std::min(64, std::atoi(d)));
     if (const char* d = std::getenv("SG_D2H_BLOCKS")) h->d2h_blocks = std::max(1, std::atoi(d));
     if (const char* sm = std::getenv("SG_SHORT_MAX")) {
@@ -609,216 +614,7 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
     return SG_OK;
 }
 
-void sg_destroy(sg_handle* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    {
-        auto& w = h->pws;
-        if (h->s_back) (void)hipStreamSynchronize(h->s_back);
-        dfree(w.rec);
-        dfree(w.rec_sorted);
-        dfree(w.hist);
-        dfree(w.bnd);
-        dfree(w.p0);
-        dfree(w.np);
-        dfree(w.err);
-        dfree(w.long_list);
-        dfree(w.long_key);
-        dfree(w.long_end);
-        dfree(w.long_pend);
-        dfree(w.short_list);
-        dfree(w.short_key);
-        dfree(w.short_end);
-        dfree(w.counts);
-        dfree(w.skips);
-        dfree(w.skip_count);
-        dfree(w.seg_end);
-        dfree(w.bin_buf);
-        for (auto* st : {&h->s_front, &h->s_back, &h->s_aux2, &h->s_aux3, &h->s_xcopy})
-            if (*st) (void)hipStreamDestroy(*st);
-        if (h->xcopy_done) (void)hipEventDestroy(h->xcopy_done);
-        for (int x = 0; x < 2; ++x) {
-            if (h->front_done[x]) (void)hipEventDestroy(h->front_done[x]);
-            if (h->back_done[x]) (void)hipEventDestroy(h->back_done[x]);
-        }
-        if (h->tjoin) (void)hipEventDestroy(h->tjoin);
-        if (h->lm_in) (void)hipEventDestroy(h->lm_in);
-        if (h->lm_done) (void)hipEventDestroy(h->lm_done);
-        if (h->pfork) (void)hipEventDestroy(h->pfork);
-        if (h->pjoin) (void)hipEventDestroy(h->pjoin);
-        for (auto& d : h->dev) {
-            if (d.done) (void)hipEventDestroy(d.done);
-            if (d.h_err) (void)hipHostFree(d.h_err);
-        }
-    }
-    dfree(h->d_rules);
-    dfree(h->d_ring);
-    dfree(h->d_hot);
-    dfree(h->d_occ);
-    dfree(h->d_seg_end);
-    dfree(h->d_hot_key);
-    dfree(h->d_bin_buf);
-    dfree(h->d_rec);
-    dfree(h->d_rec_sorted);
-    dfree(h->d_hist);
-    dfree(h->d_lim_ring);
-    dfree(h->d_rule_lim);
-    dfree(h->d_lim_slot);
-    dfree(h->d_lim_tile);
-    dfree(h->d_xg_ws[0]);
-    dfree(h->d_xg_ws[1]);
-    dfree(h->d_limx_err);
-    if (h->h_limx_err) (void)hipHostFree(h->h_limx_err);
-    dfree(h->d_lnkeys);
-    dfree(h->d_lnvals);
-    dfree(h->d_lnode_new);
-    dfree(h->d_lev_node);
-    dfree(h->d_ldyn);
-    if (h->h_lnode_new) (void)hipHostFree(h->h_lnode_new);
-    dfree(h->d_lim_period);
-    dfree(h->d_bnd);
-    dfree(h->d_p0);
-    dfree(h->d_np);
-    dfree(h->d_err);
-    dfree(h->d_last_ts);
-    dfree(h->d_long_list);
-    dfree(h->d_long_count);
-    dfree(h->d_short_list);
-    dfree(h->d_short_key);
-    dfree(h->d_short_end);
-    dfree(h->d_long_key);
-    dfree(h->d_long_end);
-    dfree(h->d_long_pend);
-    dfree(h->d_fid);
-    dfree(h->d_dbg);
-    dfree(h->d_skips);
-    dfree(h->d_prules);
-    dfree(h->d_phot);
-    dfree(h->d_ptable);
-    dfree(h->d_plast_ts);
-    dfree(h->d_preq_h);
-    dfree(h->d_pout_h);
-    dfree(h->d_pace_rules);
-    dfree(h->d_pace_latest);
-    dfree(h->d_pace_last_ts);
-    dfree(h->d_pace_req_h);
-    dfree(h->d_pace_out_h);
-    dfree(h->d_skip_count);
-    dfree(h->d_cprules);
-    dfree(h->d_cphot);
-    dfree(h->d_cpkeys);
-    dfree(h->d_cpring);
-    dfree(h->d_cplast_ts);
-    dfree(h->d_cpreq_h);
-    dfree(h->d_cpval_h);
-    dfree(h->d_cpout_h);
-    dfree(h->d_cpfid);
-    dfree(h->vd.tab);
-    dfree(h->vd.entries);
-    dfree(h->vd.arena);
-    dfree(h->vd.desc);
-    dfree(h->vd.hash);
-    dfree(h->vd.slot_of);
-    dfree(h->vd.dedupe);
-    dfree(h->vd.scan);
-    dfree(h->vd.sums);
-    dfree(h->vd.cnt);
-    dfree(h->vd.totals);
-    dfree(h->d_lrules);
-    dfree(h->d_lfrules);
-    dfree(h->d_lctl);
-    dfree(h->d_llast_fetch);
-    dfree(h->d_ps_begin);
-    dfree(h->d_ps_rules);
-    dfree(h->d_ps_grade);
-    dfree(h->d_ps_idx);
-    dfree(h->d_ps_init);
-    dfree(h->d_ps_tc);
-    dfree(h->d_ps_last_ts);
-    dfree(h->d_ps_cmode);
-    dfree(h->d_ps_ckey);
-    dfree(h->d_ps_gkey);
-    dfree(h->d_cp_owner);
-    dfree(h->d_cp_pslot);
-    dfree(h->d_cp_long);
-    dfree(h->d_cp_short);
-    dfree(h->d_cp_slot_item);
-    dfree(h->d_p_msb);
-    dfree(h->d_p_mt);
-    dfree(h->d_p_mbk);
-    dfree(h->d_cp_bnd);
-    dfree(h->d_cp_p0);
-    dfree(h->d_cp_np);
-    dfree(h->d_cp_items);
-    dfree(h->d_cp_counts);
-    dfree(h->d_cp_mlist);
-    dfree(h->d_cp_chk);
-    dfree(h->d_cp_assume);
-    dfree(h->d_cp_rec);
-    dfree(h->d_cp_rec2);
-    dfree(h->d_cp_hist);
-    dfree(h->d_cp_save);
-    dfree(h->d_cp_ckpt);
-    dfree(h->d_cp_skips);
-    dfree(h->d_cp_skip_count);
-    dfree(h->d_cp_changed);
-    dfree(h->d_cp_rule_lim);
-    dfree(h->d_cnow);
-    dfree(h->d_cthr);
-    dfree(h->d_coff);
-    dfree(h->d_cres);
-    dfree(h->d_cfid);
-    dfree(h->d_ctok);
-    dfree(h->d_calive);
-    dfree(h->d_clast_ts);
-    dfree(h->d_creq_h);
-    dfree(h->d_cout_h);
-    dfree(h->d_lhead);
-    dfree(h->d_lsec);
-    dfree(h->d_lbor);
-    dfree(h->d_lmin);
-    dfree(h->d_llast_ts);
-    dfree(h->d_lev_h);
-    for (auto& w : h->lws) {
-        dfree(w.pslot);
-        dfree(w.cxside);
-        dfree(w.flags);
-        dfree(w.cxw_next);
-        dfree(w.cx_list);
-        dfree(w.exit_pos);
-        dfree(w.exit_cnt);
-        dfree(w.skips);
-        dfree(w.skip_count);
-    }
-    dfree(h->d_lout_h);
-    dfree(h->d_lext_h);
-    dfree(h->d_lgkey);
-    dfree(h->d_linbound);
-    dfree(h->d_lentry_acc);
-    dfree(h->d_lm_cnt);
-    dfree(h->d_lm_gate);
-    dfree(h->d_lentry_fetch);
-    dfree(h->d_req_h);
-    dfree(h->d_out_h);
-    drain_async(h);
-    for (auto& sl : h->slots) {
-        dfree(sl.d_req);
-        dfree(sl.d_out);
-        if (sl.h_err) (void)hipHostFree(sl.h_err);
-        for (hipEvent_t e : {sl.h2d, sl.comp, sl.d2h})
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (hipStream_t st : {h->s_in, h->s_comp, h->s_out})
-        if (st) (void)hipStreamDestroy(st);
-    if (h->h_err) (void)hipHostFree(h->h_err);
-    if (h->h_long) (void)hipHostFree(h->h_long);
-    for (auto& e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->fork) (void)hipEventDestroy(h->fork);
-    if (h->join) (void)hipEventDestroy(h->join);
-    if (h->aux) (void)hipStreamDestroy(h->aux);
-    delete h;
-}
+void sg_destroy(sg_handle* h) { delete h; }
 
 const char* sg_last_error(const sg_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
@@ -848,8 +644,8 @@ int sg_lim_arrivals(sg_handle* h, const sg_req* req, uint64_t n, int64_t t_base,
     // reads only the request batch and the rule → limiter table: batches in flight on the pipeline go on
     int rc = ensure_layout(h);
     if (rc) return rc;
-    if (!h->d_limx_err && (hipMalloc(&h->d_limx_err, sizeof(int)) != hipSuccess ||
-                           hipHostMalloc(&h->h_limx_err, sizeof(int)) != hipSuccess))
+    if (!h->d_limx_err && (!h->d_limx_err.alloc_bytes(sizeof(int)) ||
+                           !h->h_limx_err.alloc_bytes(sizeof(int))))
         return fail(h, SG_E_NOMEM, "exchange error word");
     HIP_TRY(h, hipMemsetAsync(counts_out, 0, sizeof(uint32_t) * (size_t)h->n_lim * n_ms, stream));
     HIP_TRY(h, hipMemsetAsync(h->d_limx_err, 0, sizeof(int), stream));
@@ -875,8 +671,8 @@ int sg_lim_arrivals_param(sg_handle* h, const sg_cparam_req* req, uint64_t n, in
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = cp_rule_limiters(h, stream);
     if (rc) return rc;
-    if (!h->d_limx_err && (hipMalloc(&h->d_limx_err, sizeof(int)) != hipSuccess ||
-                           hipHostMalloc(&h->h_limx_err, sizeof(int)) != hipSuccess))
+    if (!h->d_limx_err && (!h->d_limx_err.alloc_bytes(sizeof(int)) ||
+                           !h->h_limx_err.alloc_bytes(sizeof(int))))
         return fail(h, SG_E_NOMEM, "exchange error word");
     HIP_TRY(h, hipMemsetAsync(counts_out, 0, sizeof(uint32_t) * (size_t)h->n_lim * n_ms, stream));
     HIP_TRY(h, hipMemsetAsync(h->d_limx_err, 0, sizeof(int), stream));
@@ -997,20 +793,14 @@ struct FlowLoad {
     int stride = 1;
     int n_wl = 0;
     int32_t wl[kMaxWl]{};
-    Rule* d_rules = nullptr;
-    Bucket* d_ring = nullptr;
-    BucketHot* d_hot = nullptr;
-    Occ* d_occ = nullptr;
-    uint32_t* d_seg_end = nullptr;
+    DevBuf<Rule> d_rules;
+    DevBuf<Bucket> d_ring;
+    DevBuf<BucketHot> d_hot;
+    DevBuf<Occ> d_occ;
+    DevBuf<uint32_t> d_seg_end;       // flow_seg_alloc for the new rules: workspace 0's
 };
 
-void flow_rules_abort(FlowLoad& L) {
-    dfree(L.d_rules);
-    dfree(L.d_ring);
-    dfree(L.d_hot);
-    dfree(L.d_occ);
-    dfree(L.d_seg_end);
-}
+void flow_rules_abort(FlowLoad& L) { L = FlowLoad{}; }  // under the device that prepared it
 
 int flow_rules_prepare_impl(sg_handle* h, const sg_flow_rule* rules, uint32_t n, FlowLoad& L) {
     // old flowId → old index, to keep the metric of surviving flows (ClusterFlowRuleManager.java:361)
@@ -1050,29 +840,19 @@ int flow_rules_prepare_impl(sg_handle* h, const sg_flow_rule* rules, uint32_t n,
         tab[i] = R;
     }
 
-    Rule*& d_rules = L.d_rules;
-    Bucket*& d_ring = L.d_ring;
-    BucketHot*& d_hot = L.d_hot;
-    Occ*& d_occ = L.d_occ;
-    uint32_t*& d_seg_end = L.d_seg_end;
-    int32_t* d_src = nullptr;
     if (n && h->front_only) {  // a node's front: rule thresholds and limiter slots only
-        if (hipMalloc(&d_rules, sizeof(Rule) * n) != hipSuccess) return fail(h, SG_E_NOMEM, "rule table");
+        if (!L.d_rules.alloc(n)) return fail(h, SG_E_NOMEM, "rule table");
     } else if (n) {
-        if (hipMalloc(&d_rules, sizeof(Rule) * n) != hipSuccess || hipMalloc(&d_seg_end, sizeof(uint32_t) * 2 * n) != hipSuccess ||
-            hipMalloc(&d_ring, sizeof(Bucket) * (size_t)n * stride) != hipSuccess ||
-            hipMalloc(&d_hot, sizeof(BucketHot) * (size_t)n * stride) != hipSuccess ||
-            hipMalloc(&d_occ, sizeof(Occ) * n) != hipSuccess || hipMalloc(&d_src, sizeof(int32_t) * n) != hipSuccess) {
-            dfree(d_src);
+        DevBuf<int32_t> d_src;
+        if (!L.d_rules.alloc(n) || !L.d_ring.alloc((size_t)n * stride) || !L.d_hot.alloc((size_t)n * stride) ||
+            !L.d_occ.alloc(n) || !d_src.alloc(n))
             return fail(h, SG_E_NOMEM, "rule state allocation failed");
-        }
-        HIP_TRY(h, hipMemset(d_seg_end, 0, sizeof(uint32_t) * n));           // no segment ends marked
-        HIP_TRY(h, hipMemset(d_seg_end + n, 0xFF, sizeof(uint32_t) * n));  // no segment starts marked
+        const int rc = flow_seg_alloc(h, L.d_seg_end, n);
+        if (rc) return rc;
         HIP_TRY(h, hipMemcpy(d_src, src.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        HIP_TRY(h, launch_init_state(d_ring, d_occ, n, stride, d_src, h->d_ring, h->d_occ, h->stride, 0));
-        HIP_TRY(h, launch_hot_sync(d_ring, d_hot, (uint64_t)n * stride, 0));
+        HIP_TRY(h, launch_init_state(L.d_ring, L.d_occ, n, stride, d_src, h->d_ring, h->d_occ, h->stride, 0));
+        HIP_TRY(h, launch_hot_sync(L.d_ring, L.d_hot, (uint64_t)n * stride, 0));
         HIP_TRY(h, hipDeviceSynchronize());
-        dfree(d_src);
     }
     return SG_OK;
 }
@@ -1102,21 +882,14 @@ int flow_rules_commit(sg_handle* h, const sg_flow_rule* rules, uint32_t n, FlowL
     h->c_off.assign(n, 2000);  // ClusterFlowConfig.clientOfflineTime / resourceTimeout defaults
     h->c_res.assign(n, 2000);
     h->conc_dirty = true;
-    dfree(h->d_rules);
-    dfree(h->d_ring);
-    dfree(h->d_hot);
-    dfree(h->d_occ);
-    dfree(h->d_seg_end);
-    h->d_rules = L.d_rules;
-    h->d_ring = L.d_ring;
-    h->d_hot = L.d_hot;
-    h->d_occ = L.d_occ;
-    h->d_seg_end = L.d_seg_end;
-    L.d_rules = nullptr;
-    L.d_ring = nullptr;
-    L.d_hot = nullptr;
-    L.d_occ = nullptr;
-    L.d_seg_end = nullptr;
+    h->d_rules = std::move(L.d_rules);
+    h->d_ring = std::move(L.d_ring);
+    h->d_hot = std::move(L.d_hot);
+    h->d_occ = std::move(L.d_occ);
+    sg_handle::FlowWs& w = h->ws[0];
+    w.seg_end = std::move(L.d_seg_end);  // null without rules and on a node's front
+    w.seg_cap = w.seg_end ? n + 1 : 0;
+    w.seg_start = w.seg_end ? w.seg_end + w.seg_cap : nullptr;
     h->rules.assign(rules, rules + n);
     h->rule_tab = L.tab;
     h->K = n;
@@ -1164,14 +937,11 @@ static int upload_fid_table(sg_handle* h) {
         while (tab[p].fid != 0) p = (p + 1) & (cap - 1);
         tab[p] = FidSlot{fid, k, 0};
     }
-    FidSlot* d = nullptr;
-    if (hipMalloc(&d, sizeof(FidSlot) * cap) != hipSuccess) return fail(h, SG_E_NOMEM, "flowId table");
-    if (hipMemcpy(d, tab.data(), sizeof(FidSlot) * cap, hipMemcpyHostToDevice) != hipSuccess) {
-        dfree(d);
+    DevBuf<FidSlot> d;
+    if (!d.alloc(cap)) return fail(h, SG_E_NOMEM, "flowId table");
+    if (hipMemcpy(d, tab.data(), sizeof(FidSlot) * cap, hipMemcpyHostToDevice) != hipSuccess)
         return fail(h, SG_E_DEVICE, "flowId table upload");
-    }
-    dfree(h->d_fid);
-    h->d_fid = d;
+    h->d_fid = std::move(d);
     h->fid_mask = cap - 1;
     return SG_OK;
 }
@@ -1229,14 +999,11 @@ static int upload_cp_fid_table(sg_handle* h, const sg_cparam_rule* rules, uint32
         while (tab[p].fid != 0) p = (p + 1) & (cap - 1);
         tab[p] = FidSlot{rules[k].flow_id, k, 0};
     }
-    FidSlot* d = nullptr;
-    if (hipMalloc(&d, sizeof(FidSlot) * cap) != hipSuccess) return fail(h, SG_E_NOMEM, "param flowId table");
-    if (hipMemcpy(d, tab.data(), sizeof(FidSlot) * cap, hipMemcpyHostToDevice) != hipSuccess) {
-        dfree(d);
+    DevBuf<FidSlot> d;
+    if (!d.alloc(cap)) return fail(h, SG_E_NOMEM, "param flowId table");
+    if (hipMemcpy(d, tab.data(), sizeof(FidSlot) * cap, hipMemcpyHostToDevice) != hipSuccess)
         return fail(h, SG_E_DEVICE, "param flowId table upload");
-    }
-    dfree(h->d_cpfid);
-    h->d_cpfid = d;
+    h->d_cpfid = std::move(d);
     h->cpfid_mask = cap - 1;
     return SG_OK;
 }
@@ -1258,25 +1025,15 @@ int sg_vdict_init(sg_handle* h, const sg_vdict_config* cfg) {
     while (v.dedupe_slots < 2 * v.max_batch) v.dedupe_slots <<= 1;
     const uint64_t frames = h->cfg.max_batch ? h->cfg.max_batch : 1;
     const uint64_t mb = v.max_batch;
-    if (hipMalloc(&v.tab, 8 * slots) != hipSuccess || hipMalloc(&v.entries, sizeof(VEntry) * (v.capacity + 1)) != hipSuccess ||
-        hipMalloc(&v.arena, v.arena_bytes ? v.arena_bytes : 1) != hipSuccess ||
-        hipMalloc(&v.desc, sizeof(VDesc) * mb) != hipSuccess || hipMalloc(&v.hash, 8 * mb) != hipSuccess ||
-        hipMalloc(&v.slot_of, 4 * mb) != hipSuccess || hipMalloc(&v.dedupe, 4 * v.dedupe_slots) != hipSuccess ||
-        hipMalloc(&v.scan, 8 * mb) != hipSuccess ||
-        hipMalloc(&v.sums, 8 * (scan_blocks(std::max(mb, frames)) + 1)) != hipSuccess ||
-        hipMalloc(&v.cnt, 8 * frames) != hipSuccess || hipMalloc(&v.totals, 16) != hipSuccess ||
+    if (!v.tab.alloc_bytes(8 * slots) || !v.entries.alloc_bytes(sizeof(VEntry) * (v.capacity + 1)) ||
+        !v.arena.alloc_bytes(v.arena_bytes ? v.arena_bytes : 1) ||
+        !v.desc.alloc_bytes(sizeof(VDesc) * mb) || !v.hash.alloc_bytes(8 * mb) ||
+        !v.slot_of.alloc_bytes(4 * mb) || !v.dedupe.alloc_bytes(4 * v.dedupe_slots) ||
+        !v.scan.alloc_bytes(8 * mb) ||
+        !v.sums.alloc_bytes(8 * (scan_blocks(std::max(mb, frames)) + 1)) ||
+        !v.cnt.alloc_bytes(8 * frames) || !v.totals.alloc_bytes(16) ||
         hipMemset(v.tab, 0, 8 * slots) != hipSuccess) {
-        dfree(v.tab);
-        dfree(v.entries);
-        dfree(v.arena);
-        dfree(v.desc);
-        dfree(v.hash);
-        dfree(v.slot_of);
-        dfree(v.dedupe);
-        dfree(v.scan);
-        dfree(v.sums);
-        dfree(v.cnt);
-        dfree(v.totals);
+        v = sg_handle::VDict{};
         return fail(h, SG_E_NOMEM, "value dictionary allocation");
     }
     HIP_TRY(h, hipDeviceSynchronize());
@@ -1356,13 +1113,13 @@ int sg_vdict_intern(sg_handle* h, const uint8_t* types, const uint32_t* offsets,
     const uint64_t nbytes = offsets[n];
     if (nbytes && !bytes) return fail(h, SG_E_INVAL, "null buffer");
     HIP_TRY(h, hipSetDevice(h->device));
-    uint8_t *d_types = nullptr, *d_bytes = nullptr;
-    uint32_t* d_off = nullptr;
-    uint64_t* d_ids = nullptr;
+    DevBuf<uint8_t> d_types, d_bytes;
+    DevBuf<uint32_t> d_off;
+    DevBuf<uint64_t> d_ids;
     int rc = SG_OK;
     auto run = [&]() -> int {
-        if (hipMalloc(&d_types, n) != hipSuccess || hipMalloc(&d_off, 4 * (n + 1)) != hipSuccess ||
-            hipMalloc(&d_bytes, nbytes ? nbytes : 1) != hipSuccess || hipMalloc(&d_ids, 8 * n) != hipSuccess)
+        if (!d_types.alloc_bytes(n) || !d_off.alloc_bytes(4 * (n + 1)) ||
+            !d_bytes.alloc_bytes(nbytes ? nbytes : 1) || !d_ids.alloc_bytes(8 * n))
             return fail(h, SG_E_NOMEM, "intern buffers");
         HIP_TRY(h, hipMemcpy(d_types, types, n, hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(d_off, offsets, 4 * (n + 1), hipMemcpyHostToDevice));
@@ -1379,10 +1136,6 @@ int sg_vdict_intern(sg_handle* h, const uint8_t* types, const uint32_t* offsets,
     };
     rc = run();
     (void)hipDeviceSynchronize();
-    dfree(d_types);
-    dfree(d_off);
-    dfree(d_bytes);
-    dfree(d_ids);
     return rc;
 }
 
@@ -1397,14 +1150,14 @@ int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* type
     for (uint64_t j = 0; j < n; ++j)
         if (ids[j] == 0 || ids[j] > h->vd.count) return fail(h, SG_E_INVAL, "unknown value id");
     HIP_TRY(h, hipSetDevice(h->device));
-    uint64_t* d_ids = nullptr;
-    VEntry* d_e = nullptr;
-    uint32_t* d_off = nullptr;
-    uint8_t* d_bytes = nullptr;
+    DevBuf<uint64_t> d_ids;
+    DevBuf<VEntry> d_e;
+    DevBuf<uint32_t> d_off;
+    DevBuf<uint8_t> d_bytes;
     std::vector<VEntry> e(n);
     auto run = [&]() -> int {
-        if (hipMalloc(&d_ids, 8 * n) != hipSuccess || hipMalloc(&d_e, sizeof(VEntry) * n) != hipSuccess ||
-            hipMalloc(&d_off, 4 * (n + 1)) != hipSuccess)
+        if (!d_ids.alloc_bytes(8 * n) || !d_e.alloc_bytes(sizeof(VEntry) * n) ||
+            !d_off.alloc_bytes(4 * (n + 1)))
             return fail(h, SG_E_NOMEM, "lookup buffers");
         HIP_TRY(h, hipMemcpy(d_ids, ids, 8 * n, hipMemcpyHostToDevice));
         HIP_TRY(h, launch_vd_gather(h->vd.entries, d_ids, n, d_e, nullptr));
@@ -1419,7 +1172,7 @@ int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* type
         if (total > bytes_cap) return fail(h, SG_E_CAPACITY, "bytes_out too small");
         if (total == 0) return SG_OK;
         if (!bytes_out) return fail(h, SG_E_INVAL, "null buffer");
-        if (hipMalloc(&d_bytes, total) != hipSuccess) return fail(h, SG_E_NOMEM, "lookup buffers");
+        if (!d_bytes.alloc_bytes(total)) return fail(h, SG_E_NOMEM, "lookup buffers");
         HIP_TRY(h, hipMemcpy(d_off, offsets_out, 4 * (n + 1), hipMemcpyHostToDevice));
         HIP_TRY(h, launch_vd_bytes(d_e, d_off, n, h->vd.arena, d_bytes, nullptr));
         HIP_TRY(h, hipMemcpy(bytes_out, d_bytes, total, hipMemcpyDeviceToHost));
@@ -1427,10 +1180,6 @@ int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* type
     };
     const int rc = run();
     (void)hipDeviceSynchronize();
-    dfree(d_ids);
-    dfree(d_e);
-    dfree(d_off);
-    dfree(d_bytes);
     return rc;
 }
 
@@ -1550,61 +1299,17 @@ int ticket_status(sg_handle* h, const sg_handle::DevTicket& d) {
     return rc;
 }
 
-// Workspace 0: the handle's own batch buffers.
-void main_ws(sg_handle* h, sg_handle::FlowWs& w) {
-    w.rec = h->d_rec;
-    w.rec_sorted = h->d_rec_sorted;
-    w.hist = h->d_hist;
-    w.bnd = h->d_bnd;
-    w.p0 = h->d_p0;
-    w.np = h->d_np;
-    w.err = h->d_err;
-    w.long_list = h->d_long_list;
-    w.long_key = h->d_long_key;
-    w.long_end = h->d_long_end;
-    w.long_pend = h->d_long_pend;
-    w.short_list = h->d_short_list;
-    w.short_key = h->d_short_key;
-    w.counts = h->d_long_count;
-    w.skips = h->d_skips;
-    w.skip_count = h->d_skip_count;
-    w.seg_end = h->d_seg_end;
-    w.seg_start = h->d_seg_end ? h->d_seg_end + h->K : nullptr;
-    w.short_end = h->d_short_end;
-    w.bin_buf = h->d_bin_buf;
-}
-
 // Workspace 1 and the pipeline's streams / events, allocated on first pipelined batch (seg_end grows with K).
 int pipe_setup(sg_handle* h) {
-    auto& w = h->pws;
-    const uint64_t n = h->cfg.max_batch;
+    auto& w = h->ws[1];
     if (!w.rec) {
-        uint64_t short_words = 0;
-        for (int c = 0; c < kClasses; ++c) short_words += (c == 0 ? n : n / (kClassMax[c - 1] + 1)) + 1;
-        if (hipMalloc(&w.rec, (n + kRecW) * 8) != hipSuccess || hipMalloc(&w.rec_sorted, (n + kRecW) * 8) != hipSuccess ||
-            hipMalloc(&w.hist, sizeof(uint32_t) * radix_hist_words(n)) != hipSuccess ||
-            hipMalloc(&w.bnd, sizeof(uint32_t) * kMaxWl * kMaxPeriods) != hipSuccess ||
-            hipMalloc(&w.p0, sizeof(int64_t) * kMaxWl) != hipSuccess ||
-            hipMalloc(&w.np, sizeof(uint32_t) * kMaxWl) != hipSuccess || hipMalloc(&w.err, sizeof(int)) != hipSuccess ||
-            hipMalloc(&w.long_list, sizeof(uint32_t) * (n + 1)) != hipSuccess ||
-            hipMalloc(&w.long_key, sizeof(uint32_t) * (n + 1)) != hipSuccess ||
-            hipMalloc(&w.long_end, sizeof(uint32_t) * (n + 1)) != hipSuccess ||
-            hipMalloc(&w.long_pend, sizeof(uint32_t) * (size_t)kLongTab * kLongPeriods) != hipSuccess ||
-            hipMalloc(&w.short_list, sizeof(uint32_t) * short_words) != hipSuccess ||
-            hipMalloc(&w.short_key, sizeof(uint32_t) * short_words) != hipSuccess ||
-            hipMalloc(&w.short_end, sizeof(uint32_t) * short_words) != hipSuccess ||
-            hipMalloc(&w.counts, (1 + kClasses) * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc(&w.skips, sizeof(uint4) * (2 * n / kSkipMin + 1)) != hipSuccess ||
-            hipMalloc(&w.skip_count, sizeof(uint32_t)) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "pipeline workspace");
+        if (!flow_ws_alloc(h, w)) return fail(h, SG_E_NOMEM, "pipeline workspace");
         // CU partition between the halves (env SG_FRONT_EIGHTHS = k: the front half gets CUs i with i % 8 < k,
         // the walkers the rest; 0 = no masks, both halves on every CU)
         int cus = 0;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-        int k8 = h->front_eighths;
-        if (const char* e = std::getenv("SG_FRONT_EIGHTHS")) k8 = std::atoi(e);
-        // env SG_CU_BLOCKED=1 (tuning): the front half gets CUs i with i / (cus / 8) < k (contiguous eighths)
-        const bool blocked = std::getenv("SG_CU_BLOCKED") && std::atoi(std::getenv("SG_CU_BLOCKED")) == 1;
+        const int k8 = h->front_eighths;
+        const bool blocked = h->cu_blocked;
         if (k8 > 0 && k8 < 8 && cus >= 8) {
             std::vector<uint32_t> fm((cus + 31) / 32, 0u), bm((cus + 31) / 32, 0u);
             int nb = 0;
@@ -1615,34 +1320,33 @@ int pipe_setup(sg_handle* h) {
                     ++nb;
                 }
             }
-            HIP_TRY(h, hipExtStreamCreateWithCUMask(&h->s_front, (uint32_t)fm.size(), fm.data()));
-            HIP_TRY(h, hipExtStreamCreateWithCUMask(&h->s_back, (uint32_t)bm.size(), bm.data()));
-            HIP_TRY(h, hipExtStreamCreateWithCUMask(&h->s_aux2, (uint32_t)bm.size(), bm.data()));
-            HIP_TRY(h, hipExtStreamCreateWithCUMask(&h->s_aux3, (uint32_t)bm.size(), bm.data()));
+            HIP_TRY(h, hipExtStreamCreateWithCUMask(h->s_front.put(), (uint32_t)fm.size(), fm.data()));
+            HIP_TRY(h, hipExtStreamCreateWithCUMask(h->s_back.put(), (uint32_t)bm.size(), bm.data()));
+            HIP_TRY(h, hipExtStreamCreateWithCUMask(h->s_aux2.put(), (uint32_t)bm.size(), bm.data()));
+            HIP_TRY(h, hipExtStreamCreateWithCUMask(h->s_aux3.put(), (uint32_t)bm.size(), bm.data()));
             h->walk_cus = nb;
         } else {
-            HIP_TRY(h, hipStreamCreateWithFlags(&h->s_front, hipStreamNonBlocking));
-            HIP_TRY(h, hipStreamCreateWithFlags(&h->s_back, hipStreamNonBlocking));
-            HIP_TRY(h, hipStreamCreateWithFlags(&h->s_aux2, hipStreamNonBlocking));
-            HIP_TRY(h, hipStreamCreateWithFlags(&h->s_aux3, hipStreamNonBlocking));
+            HIP_TRY(h, hipStreamCreateWithFlags(h->s_front.put(), hipStreamNonBlocking));
+            HIP_TRY(h, hipStreamCreateWithFlags(h->s_back.put(), hipStreamNonBlocking));
+            HIP_TRY(h, hipStreamCreateWithFlags(h->s_aux2.put(), hipStreamNonBlocking));
+            HIP_TRY(h, hipStreamCreateWithFlags(h->s_aux3.put(), hipStreamNonBlocking));
         }
-        HIP_TRY(h, hipEventCreateWithFlags(&h->tjoin, hipEventDisableTiming));
+        HIP_TRY(h, hipEventCreateWithFlags(h->tjoin.put(), hipEventDisableTiming));
         for (int x = 0; x < 2; ++x) {
-            HIP_TRY(h, hipEventCreateWithFlags(&h->front_done[x], hipEventDisableTiming));
-            HIP_TRY(h, hipEventCreateWithFlags(&h->back_done[x], hipEventDisableTiming));
+            HIP_TRY(h, hipEventCreateWithFlags(h->front_done[x].put(), hipEventDisableTiming));
+            HIP_TRY(h, hipEventCreateWithFlags(h->back_done[x].put(), hipEventDisableTiming));
         }
-        HIP_TRY(h, hipEventCreateWithFlags(&h->pfork, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->pjoin, hipEventDisableTiming));
+        HIP_TRY(h, hipEventCreateWithFlags(h->pfork.put(), hipEventDisableTiming));
+        HIP_TRY(h, hipEventCreateWithFlags(h->pjoin.put(), hipEventDisableTiming));
     }
-    if (h->pws_segcap < h->K) {
-        dfree(w.seg_end);
-        if (hipMalloc(&w.seg_end, sizeof(uint32_t) * 2 * (h->K + 1)) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "pipeline workspace");
-        h->pws_segcap = h->K + 1;
-        HIP_TRY(h, hipMemset(w.seg_end, 0, sizeof(uint32_t) * h->pws_segcap));
-        HIP_TRY(h, hipMemset(w.seg_end + h->pws_segcap, 0xFF, sizeof(uint32_t) * h->pws_segcap));
+    if (w.seg_cap < h->K) {  // grows with K; a reload to no more rules keeps it (all marks are reset between batches)
+        w.seg_cap = 0;
+        w.seg_start = nullptr;
+        const int rc = flow_seg_alloc(h, w.seg_end, h->K);
+        if (rc) return rc;
+        w.seg_cap = h->K + 1;
     }
-    w.seg_start = w.seg_end + h->pws_segcap;
+    w.seg_start = w.seg_end + w.seg_cap;
     return SG_OK;
 }
 
@@ -1746,15 +1450,13 @@ bool bin_setup(sg_handle* h, sg_handle::FlowWs& w, BatchArgs& a, hipStream_t str
     const int bsh = std::max(0, kb - 9);
     if (bsh > kBinMaxBsh || (((h->K - 1) >> bsh) + 1) > kBinRegular) return false;
     if (!h->d_hot_key) {
-        if (hipMalloc(&h->d_hot_key, sizeof(uint32_t) * (kBinHot + 1) + sizeof(uint2) * kHotTab) != hipSuccess)
+        if (!h->d_hot_key.alloc_bytes(sizeof(uint32_t) * (kBinHot + 1) + sizeof(uint2) * kHotTab))
             return false;
         h->hot_gen = ~0ull;
     }
     uint2* tab = reinterpret_cast<uint2*>(h->d_hot_key + kBinHot + 1);
     if (!w.bin_buf) {
-        if (hipMalloc(&w.bin_buf, (h->cfg.max_batch + kRecW) * 8) != hipSuccess) return false;
-        if (w.rec == h->d_rec) h->d_bin_buf = w.bin_buf;
-        else h->pws.bin_buf = w.bin_buf;
+        if (!w.bin_buf.alloc(h->cfg.max_batch + kRecW)) return false;
     }
     if (h->hot_gen != h->rules_gen) {  // flowIds renumbered: no hot flowIds yet (stream-ordered before k_prep)
         if (launch_hot_reset(tab, stream) != hipSuccess) return false;
@@ -1790,7 +1492,6 @@ int flow_front(sg_handle* h, BatchArgs& a, uint32_t* hist, hipStream_t stream, b
     if (stats) HIP_TRY(h, hipEventRecord(h->ev[1], stream));
     if (a.bin_on) {  // one scatter pass by bin digit, the regular bins sorted and every segment listed in LDS
         HIP_TRY(h, launch_bin_front(a, hist, true, a.csum0 != nullptr, stream));
-        if (a.rec == h->d_rec) h->last_sorted = a.rec_sorted;
         if (stats) HIP_TRY(h, hipEventRecord(h->ev[2], stream));
         return SG_OK;
     }
@@ -1802,7 +1503,6 @@ int flow_front(sg_handle* h, BatchArgs& a, uint32_t* hist, hipStream_t stream, b
         HIP_TRY(h, radix_sort_records(a.rec, a.rec_sorted, a.n, a.kshift, hist, &sorted, stream, 64, a.hist0 != nullptr,
                                       a.seg_marked ? &mk : nullptr, a.csum0 != nullptr));
         a.rec_sorted = sorted;
-        if (a.rec == h->d_rec) h->last_sorted = sorted;
     }
     if (stats) HIP_TRY(h, hipEventRecord(h->ev[2], stream));
     HIP_TRY(h, launch_seg_flow(a, stream));
@@ -1860,12 +1560,12 @@ int enqueue_flow(sg_handle* h, const sg_req* req, uint64_t n, sg_result* out, hi
                  bool stats) {
     int rc = ensure_layout(h);
     if (rc) return rc;
-    sg_handle::FlowWs w;
-    main_ws(h, w);
+    sg_handle::FlowWs& w = h->ws[0];
     BatchArgs a = flow_args(h, w, req, n, out);
     bin_setup(h, w, a, stream);
     rc = flow_front(h, a, w.hist, stream, stats);
     if (rc) return rc;
+    h->last_sorted = a.rec_sorted;
     return flow_back(h, a, stream, h->aux, h->fork, h->join, err_dst, stats);
 }
 
@@ -1883,29 +1583,25 @@ int enqueue_flow_pipelined(sg_handle* h, const sg_req* req, uint64_t n, sg_resul
     const int x = (int)(h->pipe_seq & 1);
     const int xp = x ^ 1;
     const bool first = h->pipe_seq == 0;
-    sg_handle::FlowWs w = h->pws;
-    if (x == 0) main_ws(h, w);
+    sg_handle::FlowWs& w = h->ws[x];
     // sharded namespace limiter: the armed exchange is copied into workspace x's own buffer now (the caller's
     // buffer is free again when this returns); the batch two back, which read that buffer, has finished its
     // front half by then
     const bool xshard = h->shard_world > 1 && h->n_lim > 0;
     if (xshard) {
         const uint64_t words = (uint64_t)h->shard_world * h->n_lim * h->lim_xn;
-        if (words > h->xg_ws_cap) {
+        if (words > h->d_xg_ws[0].size() || words > h->d_xg_ws[1].size()) {
             (void)hipDeviceSynchronize();
-            dfree(h->d_xg_ws[0]);
-            dfree(h->d_xg_ws[1]);
-            if (hipMalloc(&h->d_xg_ws[0], 4 * words) != hipSuccess || hipMalloc(&h->d_xg_ws[1], 4 * words) != hipSuccess)
+            if (!h->d_xg_ws[0].reserve(words) || !h->d_xg_ws[1].reserve(words))
                 return fail(h, SG_E_NOMEM, "exchange buffers");
-            h->xg_ws_cap = words;
         } else if (h->pipe_seq >= 2) {
             HIP_TRY(h, hipEventSynchronize(h->front_done[x]));
         }
         // complete before returning (the caller may free or refill its buffer then): a device-to-device hipMemcpy
         // may return before the copy has run, and the front half on s_front could read a half-copied exchange
         if (!h->s_xcopy) {
-            HIP_TRY(h, hipStreamCreateWithFlags(&h->s_xcopy, hipStreamNonBlocking));
-            HIP_TRY(h, hipEventCreateWithFlags(&h->xcopy_done, hipEventDisableTiming));
+            HIP_TRY(h, hipStreamCreateWithFlags(h->s_xcopy.put(), hipStreamNonBlocking));
+            HIP_TRY(h, hipEventCreateWithFlags(h->xcopy_done.put(), hipEventDisableTiming));
         }
         HIP_TRY(h, hipMemcpyAsync(h->d_xg_ws[x], h->lim_xg, 4 * words, hipMemcpyDeviceToDevice, h->s_xcopy));
         HIP_TRY(h, hipEventRecord(h->xcopy_done, h->s_xcopy));
@@ -1936,6 +1632,7 @@ int enqueue_flow_pipelined(sg_handle* h, const sg_req* req, uint64_t n, sg_resul
     rc = flow_front(h, a, w.hist, h->s_front, false);
     h->lim_x_armed = false;
     if (rc) return rc;
+    if (x == 0) h->last_sorted = a.rec_sorted;
     HIP_TRY(h, hipEventRecord(h->front_done[x], h->s_front));
     HIP_TRY(h, hipStreamWaitEvent(h->s_back, h->front_done[x], 0));
     a.walk_cus = h->walk_cus;
@@ -1966,6 +1663,15 @@ int drain_async(sg_handle* h) {
     return SG_OK;
 }
 
+}  // namespace
+
+sg_handle::~sg_handle() {
+    (void)hipSetDevice(device);
+    drain_async(this);
+}
+
+namespace {
+
 // The sharded limiter's plan over the armed exchange alone (no local batch): every shard's replica of the namespace
 // windows walks the same node arrivals.
 int lim_plan_only(sg_handle* h, hipStream_t stream) {
@@ -1974,7 +1680,7 @@ int lim_plan_only(sg_handle* h, hipStream_t stream) {
     int rc = ensure_layout(h);
     if (rc) return rc;
     BatchArgs a{};
-    a.err = h->d_err;
+    a.err = h->ws[0].err;
     LimArgs L{};
     L.n_lim = h->n_lim;
     std::memcpy(L.qps, h->lim_qps, sizeof(L.qps));
@@ -2039,8 +1745,8 @@ int sg_flow_decide_batch(sg_handle* h, const sg_req* req, uint64_t n, sg_result*
 void* sg_host_alloc(sg_handle* h, uint64_t bytes) {
     if (!h || bytes == 0) return nullptr;
     if (hipSetDevice(h->device) != hipSuccess) return nullptr;
-    void* p = nullptr;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+    void* p = nullptr;  // the caller's from here on (sg_host_free)
+    if (!PinnedAlloc::alloc(&p, bytes)) {
         fail(h, SG_E_NOMEM, "pinned host allocation");
         return nullptr;
     }
@@ -2050,7 +1756,7 @@ void* sg_host_alloc(sg_handle* h, uint64_t bytes) {
 void sg_host_free(sg_handle* h, void* p) {
     if (!h || !p) return;
     (void)hipSetDevice(h->device);
-    (void)hipHostFree(p);
+    PinnedAlloc::free(p);
 }
 
 // A pipelined batch of a shard with a namespace limiter consumes the armed exchange (sg_lim_exchange before every
@@ -2077,17 +1783,17 @@ int sg_flow_submit(sg_handle* h, const sg_req* req, uint64_t n, sg_result* out, 
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if (!h->s_comp) {  // first use: streams, per-slot device buffers, events, pinned error words
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->s_comp, hipStreamNonBlocking));
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
+        HIP_TRY(h, hipStreamCreateWithFlags(h->s_in.put(), hipStreamNonBlocking));
+        HIP_TRY(h, hipStreamCreateWithFlags(h->s_comp.put(), hipStreamNonBlocking));
+        HIP_TRY(h, hipStreamCreateWithFlags(h->s_out.put(), hipStreamNonBlocking));
         for (auto& sl : h->slots) {
-            if (hipMalloc(&sl.d_req, sizeof(sg_req) * h->cfg.max_batch) != hipSuccess ||
-                hipMalloc(&sl.d_out, sizeof(sg_result) * h->cfg.max_batch) != hipSuccess ||
-                hipHostMalloc(&sl.h_err, sizeof(int)) != hipSuccess)
+            if (!sl.d_req.alloc_bytes(sizeof(sg_req) * h->cfg.max_batch) ||
+                !sl.d_out.alloc_bytes(sizeof(sg_result) * h->cfg.max_batch) ||
+                !sl.h_err.alloc_bytes(sizeof(int)))
                 return fail(h, SG_E_NOMEM, "host pipeline buffers");
-            HIP_TRY(h, hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming));
-            HIP_TRY(h, hipEventCreateWithFlags(&sl.comp, hipEventDisableTiming));
-            HIP_TRY(h, hipEventCreateWithFlags(&sl.d2h, hipEventDisableTiming));
+            HIP_TRY(h, hipEventCreateWithFlags(sl.h2d.put(), hipEventDisableTiming));
+            HIP_TRY(h, hipEventCreateWithFlags(sl.comp.put(), hipEventDisableTiming));
+            HIP_TRY(h, hipEventCreateWithFlags(sl.d2h.put(), hipEventDisableTiming));
         }
     }
     sg_handle::Slot& sl = h->slots[h->next_ticket % kAsyncSlots];
@@ -2136,8 +1842,8 @@ int sg_flow_enqueue(sg_handle* h, const sg_req* req, uint64_t n, sg_result* out,
     HIP_TRY(h, hipSetDevice(h->device));
     sg_handle::DevTicket& d = h->dev[h->next_ticket % kDevSlots];
     if (!d.done) {
-        if (hipHostMalloc(&d.h_err, sizeof(int)) != hipSuccess) return fail(h, SG_E_NOMEM, "pinned error word");
-        HIP_TRY(h, hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
+        if (!d.h_err.alloc_bytes(sizeof(int))) return fail(h, SG_E_NOMEM, "pinned error word");
+        HIP_TRY(h, hipEventCreateWithFlags(d.done.put(), hipEventDisableTiming));
     }
     if (d.ticket) {  // every slot in flight: complete the oldest (its status waits in `finished`)
         hipError_t e = hipEventSynchronize(d.done);
@@ -2193,17 +1899,8 @@ int sg_flow_decide_batch_host(sg_handle* h, const sg_req* req, uint64_t n, sg_re
     if (!h) return SG_E_INVAL;
     // empty or refused before the device: the device entry point answers (and walks an armed exchange)
     if (n == 0 || n > h->cfg.max_batch || !req || !out) return sg_flow_decide_batch(h, n ? req : nullptr, n, out, nullptr);
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_req_h) {
-        if (hipMalloc(&h->d_req_h, sizeof(sg_req) * h->cfg.max_batch) != hipSuccess ||
-            hipMalloc(&h->d_out_h, sizeof(sg_result) * h->cfg.max_batch) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "host-path buffers");
-    }
-    HIP_TRY(h, hipMemcpy(h->d_req_h, req, sizeof(sg_req) * n, hipMemcpyHostToDevice));
-    int rc = sg_flow_decide_batch(h, h->d_req_h, n, h->d_out_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpy(out, h->d_out_h, sizeof(sg_result) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    return host_batch(h, h->device, req, n, out,
+                      [&](sg_req* d_req, sg_result* d_out) { return sg_flow_decide_batch(h, d_req, n, d_out, nullptr); });
 }
 
 // Envoy RLS (SentinelEnvoyRlsServiceImpl.shouldRateLimit, service/v3/SentinelEnvoyRlsServiceImpl.java:34-85): every
@@ -2339,11 +2036,10 @@ int sg_snapshot_metrics(sg_handle* h, int64_t now_ms, double* out, uint64_t cap)
     if (h->K == 0) return SG_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     drain_async(h);
-    double* d_out = nullptr;
-    HIP_TRY(h, hipMalloc(&d_out, sizeof(double) * 2 * h->K));
+    DevBuf<double> d_out;
+    if (!d_out.alloc(2 * (size_t)h->K)) return fail(h, SG_E_DEVICE, "snapshot buffer: out of memory");
     hipError_t e1 = launch_snapshot(h->d_rules, h->d_ring, h->d_occ, h->K, h->stride, now_ms, d_out, 0);
     hipError_t e2 = e1 == hipSuccess ? hipMemcpy(out, d_out, sizeof(double) * 2 * h->K, hipMemcpyDeviceToHost) : e1;
-    (void)hipFree(d_out);
     if (e2 != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e2));
     return SG_OK;
 }
@@ -2368,8 +2064,8 @@ int sg_snapshot_metrics_enqueue(sg_handle* h, int64_t now_ms, double* out_dev, u
     if (rc) return rc;
     sg_handle::DevTicket& d = h->dev[h->next_ticket % kDevSlots];
     if (!d.done) {
-        if (hipHostMalloc(&d.h_err, sizeof(int)) != hipSuccess) return fail(h, SG_E_NOMEM, "pinned error word");
-        HIP_TRY(h, hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
+        if (!d.h_err.alloc_bytes(sizeof(int))) return fail(h, SG_E_NOMEM, "pinned error word");
+        HIP_TRY(h, hipEventCreateWithFlags(d.done.put(), hipEventDisableTiming));
     }
     if (d.ticket) {
         hipError_t e = hipEventSynchronize(d.done);
@@ -2415,15 +2111,15 @@ int sg_param_load_rules(sg_handle* h, const sg_param_rule* rules, uint32_t n, co
                   [](const sg_param_hot_item& x, const sg_param_hot_item& y) { return x.value < y.value; });
     }
     if (base >= (1ull << 32)) return fail(h, SG_E_UNSUPPORTED, "param tables larger than 2^32 slots");
-    dfree(h->d_prules);
-    dfree(h->d_phot);
-    dfree(h->d_ptable);
+    h->d_prules.reset();
+    h->d_phot.reset();
+    h->d_ptable.reset();
     h->ptotal = 0;
     if (n) {
-        if (hipMalloc(&h->d_prules, sizeof(PRule) * n) != hipSuccess ||
-            hipMalloc(&h->d_ptable, sizeof(PSlot) * base) != hipSuccess)
+        if (!h->d_prules.alloc_bytes(sizeof(PRule) * n) ||
+            !h->d_ptable.alloc_bytes(sizeof(PSlot) * base))
             return fail(h, SG_E_NOMEM, "param table allocation");
-        if (n_hot && hipMalloc(&h->d_phot, sizeof(sg_param_hot_item) * n_hot) != hipSuccess)
+        if (n_hot && !h->d_phot.alloc_bytes(sizeof(sg_param_hot_item) * n_hot))
             return fail(h, SG_E_NOMEM, "param hot items");
         HIP_TRY(h, hipMemcpy(h->d_prules, tab.data(), sizeof(PRule) * n, hipMemcpyHostToDevice));
         if (n_hot)
@@ -2449,8 +2145,8 @@ int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int
     p.req = req;
     p.out = pass;
     p.n = n;
-    p.rec = h->d_rec;
-    p.rec_sorted = h->d_rec_sorted;
+    p.rec = h->ws[0].rec;
+    p.rec_sorted = h->ws[0].rec_sorted;
     p.ibits = bits_for(h->cfg.max_batch > 1 ? h->cfg.max_batch - 1 : 1);
     p.imask = (1ull << p.ibits) - 1;
     p.rules = h->d_prules;
@@ -2458,40 +2154,40 @@ int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int
     p.hot = h->d_phot;
     p.table = h->d_ptable;
     p.total_slots = h->ptotal;
-    p.err = h->d_err;
+    p.err = h->ws[0].err;
     p.last_ts = h->d_plast_ts;
-    p.long_list = h->d_long_list;
-    p.long_count = h->d_long_count;
+    p.long_list = h->ws[0].long_list;
+    p.long_count = h->ws[0].counts;
     uint32_t psplit = 64u;  // lane / wave walker split of the hot-parameter walkers (SG_PARAM_SHORT_MAX: tuning; r04: 64 < 32 by 2%)
     if (const char* e = std::getenv("SG_PARAM_SHORT_MAX")) psplit = (uint32_t)std::strtoul(e, nullptr, 10);
     p.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : psplit;
     const int gbits = bits_for(h->ptotal + 1);
     p.gshift = p.ibits + 8;  // {slot | acquire code : 8 | request index}
     if (p.gshift + gbits > 64) return fail(h, SG_E_UNSUPPORTED, "param tables x max_batch too large for 64-bit records");
-    if (!h->d_p_msb && (hipMalloc(&h->d_p_msb, sizeof(uint32_t) * kMaxPeriods) != hipSuccess ||
-                        hipMalloc(&h->d_p_mt, 2 * sizeof(int64_t)) != hipSuccess))  // {t0, {np, zero word}}
+    if (!h->d_p_msb && (!h->d_p_msb.alloc_bytes(sizeof(uint32_t) * kMaxPeriods) ||
+                        !h->d_p_mt.alloc_bytes(2 * sizeof(int64_t))))  // {t0, {np, zero word}}
         return fail(h, SG_E_NOMEM, "param millisecond table");
     p.msb = h->d_p_msb;
     p.mt0 = h->d_p_mt;
     p.mnp = reinterpret_cast<uint32_t*>(h->d_p_mt + 1);
-    if (!h->d_p_mbk && hipMalloc(&h->d_p_mbk, sizeof(uint16_t) * kPcBuckets) != hipSuccess)
+    if (!h->d_p_mbk && !h->d_p_mbk.alloc_bytes(sizeof(uint16_t) * kPcBuckets))
         return fail(h, SG_E_NOMEM, "param millisecond buckets");
     p.mbk = h->d_p_mbk;
     p.bshift = 0;
     while ((((uint64_t)n - 1) >> p.bshift) >= kPcBuckets) ++p.bshift;
     BatchArgs sg{};  // k_seg's lists in the main workspace; its error word: a zero word (the param flags are no errors)
-    sg.err = reinterpret_cast<int*>(h->d_p_mt) + 3;
-    sg.short_list = h->d_short_list;
-    sg.short_count = h->d_long_count + 1;
+    sg.err = reinterpret_cast<int*>(h->d_p_mt.get()) + 3;
+    sg.short_list = h->ws[0].short_list;
+    sg.short_count = h->ws[0].counts + 1;
     for (int c = 0; c < kClasses; ++c) sg.class_off[c] = h->class_off[c];
-    HIP_TRY(h, hipMemsetAsync(h->d_err, 0, sizeof(int), stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_long_count, 0, (1 + kClasses) * sizeof(uint32_t), stream));
+    HIP_TRY(h, hipMemsetAsync(h->ws[0].err, 0, sizeof(int), stream));
+    HIP_TRY(h, hipMemsetAsync(h->ws[0].counts, 0, (1 + kClasses) * sizeof(uint32_t), stream));
     HIP_TRY(h, hipMemsetAsync(sg.err, 0, sizeof(int), stream));
     uint64_t* sorted = nullptr;
-    HIP_TRY(h, launch_param_batch(p, sg, h->d_rec, h->d_rec_sorted, h->d_hist, p.gshift, p.gshift + gbits, &sorted, stream,
+    HIP_TRY(h, launch_param_batch(p, sg, h->ws[0].rec, h->ws[0].rec_sorted, h->ws[0].hist, p.gshift, p.gshift + gbits, &sorted, stream,
                                   h->aux, h->fork, h->join));
     h->last_sorted = sorted;
-    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     const int err = *h->h_err & ~kErrNonPositive;
     if (err & kErrTime)
@@ -2504,17 +2200,8 @@ int sg_param_decide_batch_host(sg_handle* h, const sg_param_req* req, uint64_t n
     if (!h) return SG_E_INVAL;
     if (n == 0) return SG_OK;
     if (n > h->cfg.max_batch) return fail(h, SG_E_CAPACITY, "batch larger than max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_preq_h) {
-        if (hipMalloc(&h->d_preq_h, sizeof(sg_param_req) * h->cfg.max_batch) != hipSuccess ||
-            hipMalloc(&h->d_pout_h, sizeof(int32_t) * h->cfg.max_batch) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "host-path buffers");
-    }
-    HIP_TRY(h, hipMemcpy(h->d_preq_h, req, sizeof(sg_param_req) * n, hipMemcpyHostToDevice));
-    int rc = sg_param_decide_batch(h, h->d_preq_h, n, h->d_pout_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpy(pass, h->d_pout_h, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    return host_batch(h, h->device, req, n, pass,
+                      [&](sg_param_req* d_req, int32_t* d_out) { return sg_param_decide_batch(h, d_req, n, d_out, nullptr); });
 }
 
 int sg_param_read_state(sg_handle* h, uint32_t rule, uint64_t value, int64_t* last_time, int64_t* tokens) {
@@ -2571,17 +2258,17 @@ int sg_pace_load_rules(sg_handle* h, const sg_pace_rule* rules, uint32_t n) {
         tab[i].max_queueing_ms = rules[i].max_queueing_ms;
         tab[i].pad = 0;
     }
-    dfree(h->d_pace_rules);
-    dfree(h->d_pace_latest);
+    h->d_pace_rules.reset();
+    h->d_pace_latest.reset();
     h->pace_tab.clear();
     if (!h->d_pace_last_ts) {
         const int64_t neg = INT64_MIN;
-        if (hipMalloc(&h->d_pace_last_ts, sizeof(int64_t)) != hipSuccess) return fail(h, SG_E_NOMEM, "pace state");
+        if (!h->d_pace_last_ts.alloc_bytes(sizeof(int64_t))) return fail(h, SG_E_NOMEM, "pace state");
         HIP_TRY(h, hipMemcpy(h->d_pace_last_ts, &neg, sizeof(neg), hipMemcpyHostToDevice));
     }
     if (n) {
-        if (hipMalloc(&h->d_pace_rules, sizeof(PaceRule) * n) != hipSuccess ||
-            hipMalloc(&h->d_pace_latest, sizeof(int64_t) * n) != hipSuccess)
+        if (!h->d_pace_rules.alloc_bytes(sizeof(PaceRule) * n) ||
+            !h->d_pace_latest.alloc_bytes(sizeof(int64_t) * n))
             return fail(h, SG_E_NOMEM, "pace rule allocation");
         std::vector<int64_t> init(n, -1);
         HIP_TRY(h, hipMemcpy(h->d_pace_rules, tab.data(), sizeof(PaceRule) * n, hipMemcpyHostToDevice));
@@ -2603,18 +2290,18 @@ int sg_pace_decide_batch(sg_handle* h, const sg_pace_req* req, uint64_t n, int32
     p.req = req;
     p.out = wait;
     p.n = n;
-    p.rec = h->d_rec;
-    p.rec_sorted = h->d_rec_sorted;
+    p.rec = h->ws[0].rec;
+    p.rec_sorted = h->ws[0].rec_sorted;
     p.ibits = bits_for(h->cfg.max_batch > 1 ? h->cfg.max_batch - 1 : 1);
     p.imask = (1ull << p.ibits) - 1;
     p.rules = h->d_pace_rules;
     p.n_rules = (uint32_t)h->pace_tab.size();
     p.latest = h->d_pace_latest;
-    p.err = h->d_err;
+    p.err = h->ws[0].err;
     p.last_ts = h->d_pace_last_ts;
-    p.long_list = h->d_long_list;
-    p.long_count = h->d_long_count;
-    p.short_list = h->d_short_list;
+    p.long_list = h->ws[0].long_list;
+    p.long_count = h->ws[0].counts;
+    p.short_list = h->ws[0].short_list;
     uint32_t psplit = 128u;  // lane / wave walker split of the pace walkers (SG_PACE_SHORT_MAX: tuning; 1M rules,
                              // 16M canPass: 32 → 1.31, 64 → 1.24, 96..256 → 1.21-1.22, 512 → 1.34 ms/step)
     if (const char* e = std::getenv("SG_PACE_SHORT_MAX")) psplit = (uint32_t)std::strtoul(e, nullptr, 10);
@@ -2623,25 +2310,25 @@ int sg_pace_decide_batch(sg_handle* h, const sg_pace_req* req, uint64_t n, int32
     p.gshift = p.ibits + 8;  // {rule | acquire code : 8 | request index}
     if (p.gshift + gbits > 64) return fail(h, SG_E_UNSUPPORTED, "pace rules x max_batch too large for 64-bit records");
     // the millisecond table (shared with the hot-parameter path: both are synchronous calls of this handle)
-    if (!h->d_p_msb && (hipMalloc(&h->d_p_msb, sizeof(uint32_t) * kMaxPeriods) != hipSuccess ||
-                        hipMalloc(&h->d_p_mt, 2 * sizeof(int64_t)) != hipSuccess))
+    if (!h->d_p_msb && (!h->d_p_msb.alloc_bytes(sizeof(uint32_t) * kMaxPeriods) ||
+                        !h->d_p_mt.alloc_bytes(2 * sizeof(int64_t))))
         return fail(h, SG_E_NOMEM, "pace millisecond table");
     p.msb = h->d_p_msb;
     p.mt0 = h->d_p_mt;
     p.mnp = reinterpret_cast<uint32_t*>(h->d_p_mt + 1);
-    if (!h->d_p_mbk && hipMalloc(&h->d_p_mbk, sizeof(uint16_t) * kPcBuckets) != hipSuccess)
+    if (!h->d_p_mbk && !h->d_p_mbk.alloc_bytes(sizeof(uint16_t) * kPcBuckets))
         return fail(h, SG_E_NOMEM, "pace millisecond buckets");
     p.mbk = h->d_p_mbk;
     p.bshift = 0;
     while ((((uint64_t)n - 1) >> p.bshift) >= kPcBuckets) ++p.bshift;
-    HIP_TRY(h, hipMemsetAsync(h->d_err, 0, sizeof(int), stream));
+    HIP_TRY(h, hipMemsetAsync(h->ws[0].err, 0, sizeof(int), stream));
     for (int c = 0; c < kClasses; ++c) p.class_off[c] = h->class_off[c];
-    HIP_TRY(h, hipMemsetAsync(h->d_long_count, 0, (1 + kClasses) * sizeof(uint32_t), stream));
+    HIP_TRY(h, hipMemsetAsync(h->ws[0].counts, 0, (1 + kClasses) * sizeof(uint32_t), stream));
     uint64_t* sorted = nullptr;
-    HIP_TRY(h, launch_pace_batch(p, h->d_rec, h->d_rec_sorted, h->d_hist, p.gshift, p.gshift + gbits, &sorted, stream,
+    HIP_TRY(h, launch_pace_batch(p, h->ws[0].rec, h->ws[0].rec_sorted, h->ws[0].hist, p.gshift, p.gshift + gbits, &sorted, stream,
                                  h->aux, h->fork, h->join));
     h->last_sorted = sorted;
-    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     if (*h->h_err & kErrTime)
         return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
@@ -2653,17 +2340,8 @@ int sg_pace_decide_batch_host(sg_handle* h, const sg_pace_req* req, uint64_t n, 
     if (n == 0) return SG_OK;
     if (!req || !wait) return fail(h, SG_E_INVAL, "null buffer");
     if (n > h->cfg.max_batch) return fail(h, SG_E_CAPACITY, "batch larger than max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_pace_req_h) {
-        if (hipMalloc(&h->d_pace_req_h, sizeof(sg_pace_req) * h->cfg.max_batch) != hipSuccess ||
-            hipMalloc(&h->d_pace_out_h, sizeof(int32_t) * h->cfg.max_batch) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "host-path buffers");
-    }
-    HIP_TRY(h, hipMemcpy(h->d_pace_req_h, req, sizeof(sg_pace_req) * n, hipMemcpyHostToDevice));
-    int rc = sg_pace_decide_batch(h, h->d_pace_req_h, n, h->d_pace_out_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpy(wait, h->d_pace_out_h, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    return host_batch(h, h->device, req, n, wait,
+                      [&](sg_pace_req* d_req, int32_t* d_out) { return sg_pace_decide_batch(h, d_req, n, d_out, nullptr); });
 }
 
 int sg_pace_read_state(sg_handle* h, uint32_t rule, int64_t* latest_passed_time) {
@@ -2734,20 +2412,13 @@ int sg_cparam_load_rules(sg_handle* h, const sg_cparam_rule* rules, uint32_t n, 
                   [](const sg_param_hot_item& x, const sg_param_hot_item& y) { return x.value < y.value; });
     }
     if (base >= (1ull << 32)) return fail(h, SG_E_UNSUPPORTED, "param tables larger than 2^32 slots");
-    CPRule* d_rules = nullptr;
-    sg_param_hot_item* d_hot = nullptr;
-    uint64_t* d_keys = nullptr;
-    CPBucket* d_ring = nullptr;
+    DevBuf<CPRule> d_rules;
+    DevBuf<sg_param_hot_item> d_hot;
+    DevBuf<uint64_t> d_keys;
+    DevBuf<CPBucket> d_ring;
     if (n) {
-        if (hipMalloc(&d_rules, sizeof(CPRule) * n) != hipSuccess || hipMalloc(&d_keys, 8 * base) != hipSuccess ||
-            hipMalloc(&d_ring, sizeof(CPBucket) * base * stride) != hipSuccess ||
-            (n_hot && hipMalloc(&d_hot, sizeof(sg_param_hot_item) * n_hot) != hipSuccess)) {
-            dfree(d_rules);
-            dfree(d_keys);
-            dfree(d_ring);
-            dfree(d_hot);
+        if (!d_rules.alloc(n) || !d_keys.alloc(base) || !d_ring.alloc(base * stride) || (n_hot && !d_hot.alloc(n_hot)))
             return fail(h, SG_E_NOMEM, "param table allocation");
-        }
         HIP_TRY(h, hipMemcpy(d_rules, tab.data(), sizeof(CPRule) * n, hipMemcpyHostToDevice));
         if (n_hot) HIP_TRY(h, hipMemcpy(d_hot, hs.data(), sizeof(sg_param_hot_item) * n_hot, hipMemcpyHostToDevice));
         HIP_TRY(h, launch_cp_clear(d_keys, d_ring, base, stride, 0));
@@ -2762,14 +2433,10 @@ int sg_cparam_load_rules(sg_handle* h, const sg_cparam_rule* rules, uint32_t n, 
         }
         HIP_TRY(h, hipDeviceSynchronize());
     }
-    dfree(h->d_cprules);
-    dfree(h->d_cphot);
-    dfree(h->d_cpkeys);
-    dfree(h->d_cpring);
-    h->d_cprules = d_rules;
-    h->d_cphot = d_hot;
-    h->d_cpkeys = d_keys;
-    h->d_cpring = d_ring;
+    h->d_cprules = std::move(d_rules);
+    h->d_cphot = std::move(d_hot);
+    h->d_cpkeys = std::move(d_keys);
+    h->d_cpring = std::move(d_ring);
     h->cprules.assign(rules, rules + n);
     h->cptab = tab;
     h->l_groups_stale = true;  // cluster-mode param rules group by these rules' flowIds and namespaces
@@ -2778,7 +2445,7 @@ int sg_cparam_load_rules(sg_handle* h, const sg_cparam_rule* rules, uint32_t n, 
     h->cptotal = base;
     h->cpstride = stride;
     if (!h->d_cplast_ts) {
-        if (hipMalloc(&h->d_cplast_ts, sizeof(int64_t)) != hipSuccess) return fail(h, SG_E_NOMEM, "ts");
+        if (!h->d_cplast_ts.alloc_bytes(sizeof(int64_t))) return fail(h, SG_E_NOMEM, "ts");
         const int64_t neg = -1;
         HIP_TRY(h, hipMemcpy(h->d_cplast_ts, &neg, sizeof(neg), hipMemcpyHostToDevice));
     }
@@ -2803,7 +2470,7 @@ static CPArgs cp_args(sg_handle* h, const sg_cparam_req* req, uint64_t n, const 
     c.stride = h->cpstride;
     c.total_slots = h->cptotal;
     c.per = h->cptab.empty() ? 1 : h->cptab[0].table_mask + 2;
-    c.err = h->d_err;
+    c.err = h->ws[0].err;
     c.last_ts = h->d_cplast_ts;
     return c;
 }
@@ -2825,8 +2492,8 @@ int cp_rule_limiters(sg_handle* h, hipStream_t stream) {
     }
     h->cp_any_lim = any_lim;
     if (any_lim && (rl != h->cp_rule_lim_host || !h->d_cp_rule_lim)) {
-        dfree(h->d_cp_rule_lim);
-        if (hipMalloc(&h->d_cp_rule_lim, rl.size()) != hipSuccess) return fail(h, SG_E_NOMEM, "cparam limiter table");
+        h->d_cp_rule_lim.reset();
+        if (!h->d_cp_rule_lim.alloc_bytes(rl.size())) return fail(h, SG_E_NOMEM, "cparam limiter table");
         HIP_TRY(h, hipMemcpyAsync(h->d_cp_rule_lim, rl.data(), rl.size(), hipMemcpyHostToDevice, stream));
         HIP_TRY(h, hipStreamSynchronize(stream));
         h->cp_rule_lim_host = rl;
@@ -2889,48 +2556,33 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         return fail(h, SG_E_UNSUPPORTED, "param tables x values too large for 64-bit records");
     // scratch sized for the batch's value positions
     if (nv > h->cp_val_cap) {
-        dfree(h->d_cp_owner);
-        dfree(h->d_cp_pslot);
-        dfree(h->d_cp_long);
-        dfree(h->d_cp_short);
-        dfree(h->d_cp_chk);
-        dfree(h->d_cp_rec);
-        dfree(h->d_cp_rec2);
-        dfree(h->d_cp_hist);
-        dfree(h->d_cp_items);
-        if (hipMalloc(&h->d_cp_items, sizeof(uint32_t) * 9 * nv) != hipSuccess ||
-            hipMalloc(&h->d_cp_owner, sizeof(uint32_t) * nv) != hipSuccess ||
-            hipMalloc(&h->d_cp_pslot, sizeof(uint32_t) * nv) != hipSuccess || hipMalloc(&h->d_cp_chk, nv) != hipSuccess ||
-            hipMalloc(&h->d_cp_rec, 8 * nv) != hipSuccess || hipMalloc(&h->d_cp_rec2, 8 * nv) != hipSuccess ||
-            hipMalloc(&h->d_cp_hist, sizeof(uint32_t) * radix_hist_words(nv)) != hipSuccess)
+        h->cp_val_cap = 0;  // the whole group is laid out for one size: none of it counts until all of it is there
+        h->d_cp_long.reset();
+        h->d_cp_short.reset();
+        if (!h->d_cp_items.alloc(9 * nv) || !h->d_cp_owner.alloc(nv) || !h->d_cp_pslot.alloc(nv) || !h->d_cp_chk.alloc(nv) ||
+            !h->d_cp_rec.alloc(nv) || !h->d_cp_rec2.alloc(nv) || !h->d_cp_hist.alloc(radix_hist_words(nv)))
             return fail(h, SG_E_NOMEM, "cparam batch scratch");
         uint64_t off = 0;  // k_seg's class slices for nv records (as sg_create sizes them for max_batch)
         for (int c = 0; c < kClasses; ++c) {
             h->cp_class_off[c] = off;
             off += (c == 0 ? nv : nv / (kClassMax[c - 1] + 1)) + 1;
         }
-        if (hipMalloc(&h->d_cp_long, sizeof(uint32_t) * (nv + 1)) != hipSuccess ||
-            hipMalloc(&h->d_cp_short, sizeof(uint32_t) * off) != hipSuccess)
+        if (!h->d_cp_long.alloc(nv + 1) || !h->d_cp_short.alloc(off))
             return fail(h, SG_E_NOMEM, "cparam segment lists");
         h->cp_val_cap = nv;
     }
-    if (h->cptotal > h->cp_slot_item_cap) {
-        dfree(h->d_cp_slot_item);
-        if (hipMalloc(&h->d_cp_slot_item, sizeof(uint32_t) * h->cptotal) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "cparam slot items");
-        h->cp_slot_item_cap = h->cptotal;
-    }
-    if (!h->d_cp_counts && (hipMalloc(&h->d_cp_counts, 8 * sizeof(uint32_t)) != hipSuccess ||
-                            hipMalloc(&h->d_cp_mlist, sizeof(uint32_t) * h->cfg.max_batch) != hipSuccess))
+    if (!h->d_cp_slot_item.reserve(h->cptotal)) return fail(h, SG_E_NOMEM, "cparam slot items");
+    if (!h->d_cp_counts && (!h->d_cp_counts.alloc_bytes(8 * sizeof(uint32_t)) ||
+                            !h->d_cp_mlist.alloc_bytes(sizeof(uint32_t) * h->cfg.max_batch)))
         return fail(h, SG_E_NOMEM, "cparam batch scratch");
-    if (!h->d_cp_assume && (hipMalloc(&h->d_cp_assume, h->cfg.max_batch) != hipSuccess ||
-                            hipMalloc(&h->d_cp_changed, sizeof(int) * (2 + (size_t)h->cp_max_rounds)) != hipSuccess))
+    if (!h->d_cp_assume && (!h->d_cp_assume.alloc_bytes(h->cfg.max_batch) ||
+                            !h->d_cp_changed.alloc_bytes(sizeof(int) * (2 + (size_t)h->cp_max_rounds))))
         return fail(h, SG_E_NOMEM, "cparam batch scratch");
     int rc = cp_rule_limiters(h, stream);
     if (rc) return rc;
     const bool any_lim = h->cp_any_lim;
     const uint32_t R = (uint32_t)h->cprules.size();
-    HIP_TRY(h, hipMemsetAsync(h->d_err, 0, sizeof(int), stream));
+    HIP_TRY(h, hipMemsetAsync(h->ws[0].err, 0, sizeof(int), stream));
     CPBatch b{};
     b.owner = h->d_cp_owner;
     b.chk = h->d_cp_chk;
@@ -2942,9 +2594,9 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     b.idmask = (1ull << idbits) - 1;
     b.n_wl = (int)h->cp_wls.size();
     for (int w = 0; w < b.n_wl; ++w) b.wl[w] = h->cp_wls[w];
-    if (!h->d_cp_bnd && (hipMalloc(&h->d_cp_bnd, sizeof(uint32_t) * kMaxWl * kMaxPeriods) != hipSuccess ||
-                         hipMalloc(&h->d_cp_p0, sizeof(int64_t) * kMaxWl) != hipSuccess ||
-                         hipMalloc(&h->d_cp_np, sizeof(uint32_t) * kMaxWl) != hipSuccess))
+    if (!h->d_cp_bnd && (!h->d_cp_bnd.alloc_bytes(sizeof(uint32_t) * kMaxWl * kMaxPeriods) ||
+                         !h->d_cp_p0.alloc_bytes(sizeof(int64_t) * kMaxWl) ||
+                         !h->d_cp_np.alloc_bytes(sizeof(uint32_t) * kMaxWl)))
         return fail(h, SG_E_NOMEM, "cparam period tables");
     b.bnd = h->d_cp_bnd;
     b.p0 = h->d_cp_p0;
@@ -2967,7 +2619,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     if (n_values == 0) {  // every request is BAD_REQUEST, NO_RULE_EXISTS or out of bounds (none reaches the limiter)
         HIP_TRY(h, launch_cp_finish_batch(c, stream));
         int err = 0;
-        HIP_TRY(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, hipMemcpyAsync(&err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
         HIP_TRY(h, hipStreamSynchronize(stream));
         h->cp_rounds = 0;
         if (err & kErrTime) return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
@@ -2983,14 +2635,14 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         int kb = bits_for((uint64_t)R);
         if (kb < 1) kb = 1;
         a.n = n;
-        a.rec = h->d_rec;
+        a.rec = h->ws[0].rec;
         a.kshift = 64 - kb;
         a.K = R;
-        a.bnd = h->d_bnd;
-        a.np = h->d_np;
-        a.p0 = h->d_p0;
+        a.bnd = h->ws[0].bnd;
+        a.np = h->ws[0].np;
+        a.p0 = h->ws[0].p0;
         a.out = out;
-        a.err = h->d_err;
+        a.err = h->ws[0].err;
         HIP_TRY(h, launch_cp_limprep(c, a, stream));
         LimArgs L{};
         L.n_lim = h->n_lim;
@@ -3023,23 +2675,23 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     sgm.rec_sorted = sorted;
     sgm.kshift = pbits;
     sgm.K = (uint32_t)h->cptotal;
-    sgm.err = h->d_err;
+    sgm.err = h->ws[0].err;
     sgm.long_list = h->d_cp_long;
-    sgm.long_count = h->d_long_count;
+    sgm.long_count = h->ws[0].counts;
     sgm.short_list = h->d_cp_short;
-    sgm.short_count = h->d_long_count + 1;
+    sgm.short_count = h->ws[0].counts + 1;
     for (int cl = 0; cl < kClasses; ++cl) sgm.class_off[cl] = h->cp_class_off[cl];
     uint32_t csplit = 64u;  // lane / wave walker split of the cluster param walkers (SG_CPARAM_SHORT_MAX: tuning; r04: 64 < 32 by 5%)
     if (const char* e = std::getenv("SG_CPARAM_SHORT_MAX")) csplit = (uint32_t)std::strtoul(e, nullptr, 10);
     sgm.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : csplit;
-    HIP_TRY(h, hipMemsetAsync(h->d_long_count, 0, (1 + kClasses) * sizeof(uint32_t), stream));
+    HIP_TRY(h, hipMemsetAsync(h->ws[0].counts, 0, (1 + kClasses) * sizeof(uint32_t), stream));
     HIP_TRY(h, launch_seg(sgm, stream));
     // are there multi-value requests? (then the first walk saves the touched rings for the re-walks)
     uint32_t counts[1 + kClasses], np[kMaxWl] = {};
     int err = 0, has_multi = 0;
-    HIP_TRY(h, hipMemcpyAsync(counts, h->d_long_count, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemcpyAsync(counts, h->ws[0].counts, sizeof(counts), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipMemcpyAsync(np, b.np, sizeof(uint32_t) * b.n_wl, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemcpyAsync(&err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipMemcpyAsync(&has_multi, h->d_cp_changed, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     uint64_t touched = 0;
@@ -3050,12 +2702,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         // re-walk flags clear, the multi-value requests' list
         HIP_TRY(h, hipMemsetAsync(b.dflag, 0, sizeof(uint32_t) * touched, stream));
         HIP_TRY(h, launch_cp_mlist(c, b, stream));
-        if (touched * h->cpstride > h->cp_save_cap) {
-            dfree(h->d_cp_save);
-            if (hipMalloc(&h->d_cp_save, sizeof(CPBucket) * touched * h->cpstride) != hipSuccess)
-                return fail(h, SG_E_NOMEM, "cparam ring save area");
-            h->cp_save_cap = touched * h->cpstride;
-        }
+        if (!h->d_cp_save.reserve((size_t)touched * h->cpstride)) return fail(h, SG_E_NOMEM, "cparam ring save area");
         b.save = h->d_cp_save;  // the first walk saves the touched rings, re-walks restore the dirty ones
         // hot slots' ring at the opening of every window period, so a re-walk resumes at the first period a changed
         // outcome touches (batches of <= kCkMaxPeriods periods, within a memory cap)
@@ -3066,12 +2713,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         const uint64_t ck = (uint64_t)counts[0] * ck_np * h->cpstride;
         if (counts[0] > 0 && ck_np <= kCkMaxPeriods && ck * sizeof(CPBucket) <= kCkMaxBytes &&
             !std::getenv("SG_CP_NO_CKPT")) {
-            if (ck > h->cp_ckpt_cap) {
-                dfree(h->d_cp_ckpt);
-                if (hipMalloc(&h->d_cp_ckpt, sizeof(CPBucket) * ck) != hipSuccess)
-                    return fail(h, SG_E_NOMEM, "cparam ring checkpoints");
-                h->cp_ckpt_cap = ck;
-            }
+            if (!h->d_cp_ckpt.reserve(ck)) return fail(h, SG_E_NOMEM, "cparam ring checkpoints");
             b.ckpt = h->d_cp_ckpt;
             b.ck_np = ck_np;
             HIP_TRY(h, hipMemsetAsync(b.dq, 0xFF, sizeof(uint32_t) * touched, stream));
@@ -3080,13 +2722,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     // saturated ranges of hot slots (pieces of <= 4096 records, each >= 256: at most 2 nv / 256 + 1)
     {
         const uint64_t cap = 2 * nv / 256 + 1;
-        if (cap > h->cp_skip_cap) {
-            dfree(h->d_cp_skips);
-            if (hipMalloc(&h->d_cp_skips, sizeof(uint2) * cap) != hipSuccess ||
-                (!h->d_cp_skip_count && hipMalloc(&h->d_cp_skip_count, sizeof(uint32_t)) != hipSuccess))
-                return fail(h, SG_E_NOMEM, "cparam skip list");
-            h->cp_skip_cap = cap;
-        }
+        if (!h->d_cp_skips.reserve(cap) || !h->d_cp_skip_count.reserve(1)) return fail(h, SG_E_NOMEM, "cparam skip list");
         b.skips = h->d_cp_skips;
         b.skip_count = h->d_cp_skip_count;
         b.skip_cap = (uint32_t)cap;
@@ -3125,7 +2761,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         }
         int changed[kChain] = {0, 0, 0};
         HIP_TRY(h, hipMemcpyAsync(changed, h->d_cp_changed + 1 + r0, sizeof(int) * (r1 - r0), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, hipMemcpyAsync(&err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
         HIP_TRY(h, hipStreamSynchronize(stream));
         round = r1;
         for (uint32_t r = r0; r < r1; ++r) {
@@ -3169,7 +2805,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     }
     h->cp_rounds = converged ? (round ? round : 1) : kMaxRounds + 1;
     HIP_TRY(h, launch_cp_finish_batch(c, stream));
-    HIP_TRY(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemcpyAsync(&err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     if (err & kErrTime) return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
     if (err & kErrBounds)
@@ -3194,33 +2830,22 @@ int sg_cparam_decide_batch_host(sg_handle* h, const sg_cparam_req* req, uint64_t
     if (n == 0 || n > h->cfg.max_batch || !req || !out || (!values && n_values))
         return sg_cparam_decide_batch(h, n ? req : nullptr, n, values, n_values, out, nullptr);
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_cpreq_h) {
-        if (hipMalloc(&h->d_cpreq_h, sizeof(sg_cparam_req) * h->cfg.max_batch) != hipSuccess ||
-            hipMalloc(&h->d_cpout_h, sizeof(sg_result) * h->cfg.max_batch) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "host-path buffers");
-    }
-    if (n_values > h->cpval_cap) {
-        dfree(h->d_cpval_h);
-        if (hipMalloc(&h->d_cpval_h, 8 * n_values) != hipSuccess) return fail(h, SG_E_NOMEM, "host-path values");
-        h->cpval_cap = n_values;
-    }
-    HIP_TRY(h, hipMemcpy(h->d_cpreq_h, req, sizeof(sg_cparam_req) * n, hipMemcpyHostToDevice));
-    if (n_values) HIP_TRY(h, hipMemcpy(h->d_cpval_h, values, 8 * n_values, hipMemcpyHostToDevice));
-    int rc = sg_cparam_decide_batch(h, h->d_cpreq_h, n, h->d_cpval_h, n_values, h->d_cpout_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpy(out, h->d_cpout_h, sizeof(sg_result) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    uint64_t* d_vals = nullptr;
+    if (!h->stage.get(2, n_values, d_vals)) return fail(h, SG_E_NOMEM, "host-path values");
+    if (n_values) HIP_TRY(h, hipMemcpy(d_vals, values, 8 * n_values, hipMemcpyHostToDevice));
+    return host_batch(h, h->device, req, n, out, [&](sg_cparam_req* d_req, sg_result* d_out) {
+        return sg_cparam_decide_batch(h, d_req, n, d_vals, n_values, d_out, nullptr);
+    });
 }
 
 int sg_cparam_read_sum(sg_handle* h, uint32_t rule, uint64_t value, int64_t now_ms, int64_t* sum) {
     if (!h || !sum || rule >= h->cptab.size()) return SG_E_INVAL;
     HIP_TRY(h, hipSetDevice(h->device));
-    int64_t* d = nullptr;
-    HIP_TRY(h, hipMalloc(&d, sizeof(int64_t)));
+    DevBuf<int64_t> d;
+    if (!d.alloc(1)) return fail(h, SG_E_DEVICE, "read buffer: out of memory");
     CPArgs c = cp_args(h, nullptr, 0, nullptr, 0, nullptr);
     hipError_t e = launch_cp_read(c, rule, value, now_ms, d, 0);
     if (e == hipSuccess) e = hipMemcpy(sum, d, sizeof(int64_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
     return SG_OK;
 }
@@ -3233,20 +2858,15 @@ int sg_cparam_top_values(sg_handle* h, int64_t now_ms, uint32_t number, uint64_t
     drain_async(h);
     CPArgs c = cp_args(h, nullptr, 0, nullptr, 0, nullptr);
     const uint64_t per = h->cptotal / R;
-    CPTop* d_top = nullptr;
-    unsigned long long* d_cnt = nullptr;
-    if (hipMalloc(&d_top, sizeof(CPTop) * h->cptotal) != hipSuccess || hipMalloc(&d_cnt, sizeof(unsigned long long)) != hipSuccess) {
-        dfree(d_top);
-        return fail(h, SG_E_NOMEM, "top values buffer");
-    }
+    DevBuf<CPTop> d_top;
+    DevBuf<unsigned long long> d_cnt;
+    if (!d_top.alloc(h->cptotal) || !d_cnt.alloc(1)) return fail(h, SG_E_NOMEM, "top values buffer");
     unsigned long long cnt = 0;
     hipError_t e = hipMemset(d_cnt, 0, sizeof(cnt));
     if (e == hipSuccess) e = launch_cp_top(c, now_ms, per, d_top, d_cnt, 0);
     if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost);
     std::vector<CPTop> top(cnt);
     if (e == hipSuccess && cnt) e = hipMemcpy(top.data(), d_top, sizeof(CPTop) * cnt, hipMemcpyDeviceToHost);
-    (void)hipFree(d_top);
-    (void)hipFree(d_cnt);
     if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
     // per rule: count descending (the reference compares (int) casts of the counts), ties by value
     std::sort(top.begin(), top.end(), [](const CPTop& a, const CPTop& b) {
@@ -3313,13 +2933,13 @@ int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local
     h->l_wmin = (wl2 == kMinuteWl) ? 0 : h->l_n_wl;
     if (wl2 != kMinuteWl) h->l_wl[h->l_n_wl++] = kMinuteWl;
 
-    dfree(h->d_lrules);
-    dfree(h->d_lfrules);
-    dfree(h->d_lctl);
-    dfree(h->d_lhead);
-    dfree(h->d_lsec);
-    dfree(h->d_lbor);
-    dfree(h->d_lmin);
+    h->d_lrules.reset();
+    h->d_lfrules.reset();
+    h->d_lctl.reset();
+    h->d_lhead.reset();
+    h->d_lsec.reset();
+    h->d_lbor.reset();
+    h->d_lmin.reset();
     h->l_nodes = n;
     h->l_n_origins = 0;
     h->l_n_contexts = 0;
@@ -3330,33 +2950,32 @@ int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local
     h->l_cluster_refs.clear();
     h->l_groups_stale = false;
     h->l_rule_slot.clear();
-    dfree(h->d_lnkeys);
-    dfree(h->d_lnvals);
-    dfree(h->d_ldyn);
-    h->l_nmap_cap = 0;
+    h->d_lnkeys.reset();
+    h->d_lnvals.reset();
+    h->d_ldyn.reset();
     h->l_pool_cap = h->l_pool_used = 0;
     h->l_epoch = 0;
     h->l_batches = 0;
-    dfree(h->d_lgkey);
-    dfree(h->d_linbound);  // every resource's entries EntryType.OUT until sg_local_set_entry_types
+    h->d_lgkey.reset();
+    h->d_linbound.reset();  // every resource's entries EntryType.OUT until sg_local_set_entry_types
     h->l_ps_applied = 0;
-    if (!h->d_lentry_fetch && (hipMalloc(&h->d_lentry_fetch, sizeof(int64_t)) != hipSuccess ||
-                               hipMalloc(&h->d_lentry_acc, sizeof(LBucket) * kMinuteS) != hipSuccess))
+    if (!h->d_lentry_fetch && (!h->d_lentry_fetch.alloc_bytes(sizeof(int64_t)) ||
+                               !h->d_lentry_acc.alloc_bytes(sizeof(LBucket) * kMinuteS)))
         return fail(h, SG_E_NOMEM, "ENTRY_NODE state");
     {
         const int64_t neg1 = -1;  // StatisticNode.lastFetchTime of Constants.ENTRY_NODE
         HIP_TRY(h, hipMemcpy(h->d_lentry_fetch, &neg1, sizeof(neg1), hipMemcpyHostToDevice));
     }
-    if (!h->d_llast_ts && hipMalloc(&h->d_llast_ts, sizeof(int64_t)) != hipSuccess) return fail(h, SG_E_NOMEM, "ts");
+    if (!h->d_llast_ts && !h->d_llast_ts.alloc_bytes(sizeof(int64_t))) return fail(h, SG_E_NOMEM, "ts");
     const int64_t neg = -1;
     HIP_TRY(h, hipMemcpy(h->d_llast_ts, &neg, sizeof(neg), hipMemcpyHostToDevice));
     h->lcfg = *cfg;
     h->ltab = tab;
     if (n) {
-        if (hipMalloc(&h->d_lrules, sizeof(LRule) * n) != hipSuccess || hipMalloc(&h->d_lhead, sizeof(LHead) * n) != hipSuccess ||
-            hipMalloc(&h->d_lsec, sizeof(LBucket) * (size_t)n * cfg->sample_count) != hipSuccess ||
-            hipMalloc(&h->d_lbor, sizeof(LFuture) * (size_t)n * cfg->sample_count) != hipSuccess ||
-            hipMalloc(&h->d_lmin, sizeof(LBucket) * (size_t)n * kMinuteS) != hipSuccess)
+        if (!h->d_lrules.alloc_bytes(sizeof(LRule) * n) || !h->d_lhead.alloc_bytes(sizeof(LHead) * n) ||
+            !h->d_lsec.alloc_bytes(sizeof(LBucket) * (size_t)n * cfg->sample_count) ||
+            !h->d_lbor.alloc_bytes(sizeof(LFuture) * (size_t)n * cfg->sample_count) ||
+            !h->d_lmin.alloc_bytes(sizeof(LBucket) * (size_t)n * kMinuteS))
             return fail(h, SG_E_NOMEM, "local state allocation");
         HIP_TRY(h, hipMemcpy(h->d_lrules, tab.data(), sizeof(LRule) * n, hipMemcpyHostToDevice));
         LArgs L{};
@@ -3368,8 +2987,8 @@ int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local
         L.bor = h->d_lbor;
         L.minute = h->d_lmin;
         HIP_TRY(h, launch_local_init(L, 0));
-        dfree(h->d_llast_fetch);
-        if (hipMalloc(&h->d_llast_fetch, sizeof(int64_t) * n) != hipSuccess) return fail(h, SG_E_NOMEM, "lastFetchTime");
+        h->d_llast_fetch.reset();
+        if (!h->d_llast_fetch.alloc_bytes(sizeof(int64_t) * n)) return fail(h, SG_E_NOMEM, "lastFetchTime");
         std::vector<int64_t> neg1(n, -1);  // StatisticNode.lastFetchTime = -1
         HIP_TRY(h, hipMemcpy(h->d_llast_fetch, neg1.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
         HIP_TRY(h, hipDeviceSynchronize());
@@ -3385,8 +3004,8 @@ int sg_local_set_entry_types(sg_handle* h, const uint8_t* inbound, uint32_t n) {
     drain_async(h);
     std::vector<uint8_t> v(n);
     for (uint32_t k = 0; k < n; ++k) v[k] = inbound[k] ? 1 : 0;
-    dfree(h->d_linbound);
-    if (n && hipMalloc(&h->d_linbound, n) != hipSuccess) return fail(h, SG_E_NOMEM, "entry types");
+    h->d_linbound.reset();
+    if (n && !h->d_linbound.alloc_bytes(n)) return fail(h, SG_E_NOMEM, "entry types");
     if (n) HIP_TRY(h, hipMemcpy(h->d_linbound, v.data(), n, hipMemcpyHostToDevice));
     return SG_OK;
 }
@@ -3422,11 +3041,11 @@ int sg_local_metrics_raw_enqueue(sg_handle* h, int64_t now_ms, sg_metric_node* d
     int rc = pipe_setup(h);
     if (rc) return rc;
     if (!h->lm_done) {
-        HIP_TRY(h, hipEventCreateWithFlags(&h->lm_in, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->lm_done, hipEventDisableTiming));
+        HIP_TRY(h, hipEventCreateWithFlags(h->lm_in.put(), hipEventDisableTiming));
+        HIP_TRY(h, hipEventCreateWithFlags(h->lm_done.put(), hipEventDisableTiming));
     }
-    if ((!h->d_lm_cnt && hipMalloc(&h->d_lm_cnt, sizeof(unsigned long long)) != hipSuccess) ||
-        (!h->d_lm_gate && hipMalloc(&h->d_lm_gate, sizeof(int)) != hipSuccess))
+    if ((!h->d_lm_cnt && !h->d_lm_cnt.alloc_bytes(sizeof(unsigned long long))) ||
+        (!h->d_lm_gate && !h->d_lm_gate.alloc_bytes(sizeof(int))))
         return fail(h, SG_E_NOMEM, "metric row counter");
     LArgs L{};
     L.K = (uint32_t)h->ltab.size();
@@ -3502,7 +3121,7 @@ int local_metrics(sg_handle* h, int64_t now_ms, sg_metric_node* out, uint64_t ca
         if (e == hipSuccess && h->d_linbound) e = launch_local_entry_rows(L, now_ms, dst, d_cnt, emit, raw, 0);
         return e;
     };
-    if (!h->d_lm_cnt && hipMalloc(&h->d_lm_cnt, sizeof(unsigned long long)) != hipSuccess)
+    if (!h->d_lm_cnt && !h->d_lm_cnt.alloc_bytes(sizeof(unsigned long long)))
         return fail(h, SG_E_NOMEM, "metric row counter");
     unsigned long long* d_cnt = h->d_lm_cnt;
     unsigned long long cnt = 0;
@@ -3517,12 +3136,11 @@ int local_metrics(sg_handle* h, int64_t now_ms, sg_metric_node* out, uint64_t ca
         if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
         return SG_OK;
     }
-    sg_metric_node* d_out = nullptr;
-    if (cnt && hipMalloc(&d_out, sizeof(sg_metric_node) * cnt) != hipSuccess) return fail(h, SG_E_NOMEM, "metric rows");
+    DevBuf<sg_metric_node> d_out;
+    if (cnt && !d_out.alloc(cnt)) return fail(h, SG_E_NOMEM, "metric rows");
     e = pass(d_out, d_cnt, 1);
     if (e == hipSuccess && cnt) e = hipMemcpy(out, d_out, sizeof(sg_metric_node) * cnt, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
     std::sort(out, out + cnt, [](const sg_metric_node& a, const sg_metric_node& b) {  // the listener's TreeMap by time
         return a.timestamp != b.timestamp ? a.timestamp < b.timestamp : a.resource < b.resource;
@@ -3558,26 +3176,26 @@ int local_apply_params(sg_handle* h) {
 int lnode_prepare(sg_handle* h, uint64_t n) {
     const uint32_t K = (uint32_t)h->ltab.size();
     if (!h->d_lev_node) {
-        if (hipMalloc(&h->d_lev_node, sizeof(uint2) * h->cfg.max_batch) != hipSuccess ||
-            hipMalloc(&h->d_lnode_new, sizeof(uint32_t)) != hipSuccess ||
-            hipHostMalloc(&h->h_lnode_new, sizeof(uint32_t)) != hipSuccess)
+        if (!h->d_lev_node.alloc_bytes(sizeof(uint2) * h->cfg.max_batch) ||
+            !h->d_lnode_new.alloc_bytes(sizeof(uint32_t)) ||
+            !h->h_lnode_new.alloc_bytes(sizeof(uint32_t)))
             return fail(h, SG_E_NOMEM, "node pool workspace");
     }
     if (!h->d_ldyn) {
-        if (hipMalloc(&h->d_ldyn, sizeof(uint32_t) * (K ? K : 1)) != hipSuccess) return fail(h, SG_E_NOMEM, "node pool");
+        if (!h->d_ldyn.alloc_bytes(sizeof(uint32_t) * (K ? K : 1))) return fail(h, SG_E_NOMEM, "node pool");
         HIP_TRY(h, hipMemset(h->d_ldyn, 0, sizeof(uint32_t) * (K ? K : 1)));
         h->l_epoch = 0;
     }
     const uint64_t keys_per_event = (h->l_n_origins > 0 ? 1 : 0) + (h->l_n_contexts > 0 ? 1 : 0);
     const uint64_t need = 2 * ((uint64_t)h->l_pool_used + n * keys_per_event);
-    if (h->d_lnkeys && need <= h->l_nmap_cap) return SG_OK;
-    uint64_t cap = h->l_nmap_cap ? h->l_nmap_cap : (1ull << 12);
+    if (h->d_lnkeys && need <= h->d_lnkeys.size()) return SG_OK;
+    uint64_t cap = h->d_lnkeys ? h->d_lnkeys.size() : (1ull << 12);
     while (cap < need) cap <<= 1;
     std::vector<uint64_t> ok, nk(cap, 0);
     std::vector<uint32_t> ov, nv(cap, kNoNode);
     if (h->d_lnkeys) {  // rehash the existing keys
-        ok.resize(h->l_nmap_cap);
-        ov.resize(h->l_nmap_cap);
+        ok.resize(h->d_lnkeys.size());
+        ov.resize(h->d_lnkeys.size());
         HIP_TRY(h, hipDeviceSynchronize());
         HIP_TRY(h, hipMemcpy(ok.data(), h->d_lnkeys, sizeof(uint64_t) * ok.size(), hipMemcpyDeviceToHost));
         HIP_TRY(h, hipMemcpy(ov.data(), h->d_lnvals, sizeof(uint32_t) * ov.size(), hipMemcpyDeviceToHost));
@@ -3589,25 +3207,14 @@ int lnode_prepare(sg_handle* h, uint64_t n) {
             nv[j] = ov[i];
         }
     }
-    uint64_t* dk = nullptr;
-    uint32_t* dv = nullptr;
-    if (hipMalloc(&dk, sizeof(uint64_t) * cap) != hipSuccess || hipMalloc(&dv, sizeof(uint32_t) * cap) != hipSuccess) {
-        dfree(dk);
-        dfree(dv);
-        return fail(h, SG_E_NOMEM, "node pool map");
-    }
+    DevBuf<uint64_t> dk;
+    DevBuf<uint32_t> dv;
+    if (!dk.alloc(cap) || !dv.alloc(cap)) return fail(h, SG_E_NOMEM, "node pool map");
     hipError_t e = hipMemcpy(dk, nk.data(), sizeof(uint64_t) * cap, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dv, nv.data(), sizeof(uint32_t) * cap, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        dfree(dk);
-        dfree(dv);
-        return fail(h, SG_E_DEVICE, hipGetErrorString(e));
-    }
-    dfree(h->d_lnkeys);
-    dfree(h->d_lnvals);
-    h->d_lnkeys = dk;
-    h->d_lnvals = dv;
-    h->l_nmap_cap = cap;
+    if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
+    h->d_lnkeys = std::move(dk);
+    h->d_lnvals = std::move(dv);
     return SG_OK;
 }
 
@@ -3616,7 +3223,8 @@ int lnode_prepare(sg_handle* h, uint64_t n) {
 // (~260 MB at 1M resources) and grows fourfold with room for twice the nodes in use.
 int lnode_grow(sg_handle* h, uint64_t used) {
     if (used <= h->l_pool_cap) return SG_OK;
-    if (const char* f = std::getenv("SG_TEST_POOL_FAIL"))  // test aid: a failed growth (tests/test_local_rules_gpu.py)
+    // test aid: a failed growth. Read here, not in sg_create: tests/test_local_rules_gpu.py sets it on a live handle.
+    if (const char* f = std::getenv("SG_TEST_POOL_FAIL"))
         if (std::atoi(f)) return fail(h, SG_E_NOMEM, "node pool (SG_TEST_POOL_FAIL)");
     const uint64_t K = h->ltab.size();
     uint64_t cap = std::max<uint64_t>({2ull * used, 4ull * h->l_pool_cap, 1024ull, K / 16});
@@ -3624,17 +3232,11 @@ int lnode_grow(sg_handle* h, uint64_t used) {
     if (K + used >= SG_KEY_BAD || cap < used) return fail(h, SG_E_CAPACITY, "too many origin / context nodes");
     const uint64_t N = K + cap, old = h->l_nodes;
     const int S = h->lcfg.sample_count;
-    LHead* hd = nullptr;
-    LBucket *sec = nullptr, *mnt = nullptr;
-    LFuture* bor = nullptr;
-    if (hipMalloc(&hd, sizeof(LHead) * N) != hipSuccess || hipMalloc(&sec, sizeof(LBucket) * N * S) != hipSuccess ||
-        hipMalloc(&bor, sizeof(LFuture) * N * S) != hipSuccess || hipMalloc(&mnt, sizeof(LBucket) * N * kMinuteS) != hipSuccess) {
-        dfree(hd);
-        dfree(sec);
-        dfree(bor);
-        dfree(mnt);
+    DevBuf<LHead> hd;
+    DevBuf<LBucket> sec, mnt;
+    DevBuf<LFuture> bor;
+    if (!hd.alloc(N) || !sec.alloc(N * S) || !bor.alloc(N * S) || !mnt.alloc(N * kMinuteS))
         return fail(h, SG_E_NOMEM, "node pool");
-    }
     hipError_t e = hipMemcpy(hd, h->d_lhead, sizeof(LHead) * old, hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = hipMemcpy(sec, h->d_lsec, sizeof(LBucket) * old * S, hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = hipMemcpy(bor, h->d_lbor, sizeof(LFuture) * old * S, hipMemcpyDeviceToDevice);
@@ -3649,21 +3251,11 @@ int lnode_grow(sg_handle* h, uint64_t used) {
         e = launch_local_init_range(L, old, N, 0);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        dfree(hd);
-        dfree(sec);
-        dfree(bor);
-        dfree(mnt);
-        return fail(h, SG_E_DEVICE, std::string("node pool growth: ") + hipGetErrorString(e));
-    }
-    dfree(h->d_lhead);
-    dfree(h->d_lsec);
-    dfree(h->d_lbor);
-    dfree(h->d_lmin);
-    h->d_lhead = hd;
-    h->d_lsec = sec;
-    h->d_lbor = bor;
-    h->d_lmin = mnt;
+    if (e != hipSuccess) return fail(h, SG_E_DEVICE, std::string("node pool growth: ") + hipGetErrorString(e));
+    h->d_lhead = std::move(hd);
+    h->d_lsec = std::move(sec);
+    h->d_lbor = std::move(bor);
+    h->d_lmin = std::move(mnt);
     h->l_nodes = (uint32_t)N;
     h->l_pool_cap = (uint32_t)cap;
     return SG_OK;
@@ -3687,22 +3279,21 @@ struct LocalBufs {
 
 int local_bufs(sg_handle* h, int x, LocalBufs& b) {
     if (x == 0) {
-        b = LocalBufs{h->d_rec, h->d_rec_sorted, h->d_hist, h->d_bnd, h->d_p0, h->d_np, h->d_err, h->d_long_list,
-                      h->d_long_count, h->d_short_list, &h->lws[0]};
+        b = LocalBufs{h->ws[0].rec, h->ws[0].rec_sorted, h->ws[0].hist, h->ws[0].bnd, h->ws[0].p0, h->ws[0].np, h->ws[0].err, h->ws[0].long_list,
+                      h->ws[0].counts, h->ws[0].short_list, &h->lws[0]};
     } else {
-        const auto& w = h->pws;
+        const auto& w = h->ws[1];
         b = LocalBufs{w.rec, w.rec_sorted, w.hist, w.bnd, w.p0, w.np, w.err, w.long_list, w.counts, w.short_list, &h->lws[1]};
     }
     sg_handle::LocalWs& lw = h->lws[x];
     if (!lw.flags) {  // the local path's own buffers of the workspace (sized for max_batch)
         const uint64_t mb = h->cfg.max_batch;
-        h->lskip_cap = (uint32_t)(2 * mb / kSkipMin + 1);
-        if (hipMalloc(&lw.flags, sizeof(int)) != hipSuccess ||
-            hipMalloc(&lw.exit_pos, sizeof(uint32_t) * (mb + 1)) != hipSuccess ||
-            hipMalloc(&lw.exit_cnt, sizeof(uint32_t) * (mb / kLTile + 2)) != hipSuccess ||
-            hipMalloc(&lw.skips, sizeof(LSkip) * h->lskip_cap) != hipSuccess ||
-            hipMalloc(&lw.skip_count, sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc(&lw.cxw_next, sizeof(uint32_t)) != hipSuccess)
+        if (!lw.flags.alloc_bytes(sizeof(int)) ||
+            !lw.exit_pos.alloc_bytes(sizeof(uint32_t) * (mb + 1)) ||
+            !lw.exit_cnt.alloc_bytes(sizeof(uint32_t) * (mb / kLTile + 2)) ||
+            !lw.skips.alloc(2 * mb / kSkipMin + 1) ||
+            !lw.skip_count.alloc_bytes(sizeof(uint32_t)) ||
+            !lw.cxw_next.alloc_bytes(sizeof(uint32_t)))
             return fail(h, SG_E_NOMEM, "local batch workspace");
     }
     return SG_OK;
@@ -3772,7 +3363,7 @@ int local_args(sg_handle* h, const LocalBufs& b, const sg_local_event* ev, const
         const int prc = pslot_embed(h, L.ps, 0);  // cluster-mode param rules on the embedded token server
         if (prc) return prc;
         if (h->l_cxw) {
-            if (!b.lw->pslot && hipMalloc(&b.lw->pslot, sizeof(uint64_t) * h->cfg.max_batch) != hipSuccess)
+            if (!b.lw->pslot && !b.lw->pslot.alloc_bytes(sizeof(uint64_t) * h->cfg.max_batch))
                 return fail(h, SG_E_NOMEM, "param lookups of the local batch");
             L.pslot = b.lw->pslot;
         }
@@ -3794,12 +3385,12 @@ int local_args(sg_handle* h, const LocalBufs& b, const sg_local_event* ev, const
     L.flags = b.lw->flags;
     L.cxw_next = b.lw->cxw_next;
     if (h->l_cxw && (h->l_has_cx || h->l_has_cx_ps)) {  // the cx wave walker's sorted-order side words
-        if (!b.lw->cxside && hipMalloc(&b.lw->cxside, sizeof(CxSide) * h->cfg.max_batch) != hipSuccess)
+        if (!b.lw->cxside && !b.lw->cxside.alloc_bytes(sizeof(CxSide) * h->cfg.max_batch))
             return fail(h, SG_E_NOMEM, "side words of the local batch");
         L.cxside = b.lw->cxside;
     }
     if (h->l_has_cx || h->l_has_cx_ps || h->l_n_contexts > 0) {
-        if (!b.lw->cx_list && hipMalloc(&b.lw->cx_list, sizeof(uint32_t) * (h->cfg.max_batch + 1)) != hipSuccess)
+        if (!b.lw->cx_list && !b.lw->cx_list.alloc_bytes(sizeof(uint32_t) * (h->cfg.max_batch + 1)))
             return fail(h, SG_E_NOMEM, "cx segment list of the local batch");
         L.cx_list = b.lw->cx_list;
         L.cx_count = b.lw->cx_list + h->cfg.max_batch;
@@ -3808,7 +3399,7 @@ int local_args(sg_handle* h, const LocalBufs& b, const sg_local_event* ev, const
     L.exit_cnt = b.lw->exit_cnt;
     L.skips = b.lw->skips;
     L.skip_count = b.lw->skip_count;
-    L.skip_cap = h->lskip_cap;
+    L.skip_cap = (uint32_t)b.lw->skips.size();
     L.hist0 = b.hist;
     L.hist0_bits = radix_digit_bits(64 - L.kshift);
 
@@ -3902,7 +3493,7 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
         if (rc) return rc;
         L.nkeys = h->d_lnkeys;
         L.nvals = h->d_lnvals;
-        L.nmask = h->l_nmap_cap - 1;
+        L.nmask = h->d_lnkeys.size() - 1;
         L.node_base = K + h->l_pool_used;
         L.node_new = h->d_lnode_new;
         L.ev_node = h->d_lev_node;
@@ -3944,9 +3535,9 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
     if (h->stats_on) HIP_TRY(h, hipEventRecord(h->ev[2], stream));
     HIP_TRY(h, launch_local_walk(L, sgm, h->l_has_cx || h->l_has_cx_ps || track, h->aux, stream, h->fork, h->join));
     if (h->stats_on) HIP_TRY(h, hipEventRecord(h->ev[3], stream));
-    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     if (h->stats_on) {
-        HIP_TRY(h, hipMemcpyAsync(h->h_long, h->d_long_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, hipMemcpyAsync(h->h_long, h->ws[0].counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_TRY(h, hipMemcpyAsync(h->h_long + 1, L.skip_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_TRY(h, hipEventRecord(h->ev[4], stream));
     }
@@ -4040,8 +3631,8 @@ int sg_local_enqueue(sg_handle* h, const sg_local_event* ev, uint64_t n, sg_loca
     }
     sg_handle::DevTicket& d = h->dev[h->next_ticket % kDevSlots];
     if (!d.done) {
-        if (hipHostMalloc(&d.h_err, sizeof(int)) != hipSuccess) return fail(h, SG_E_NOMEM, "pinned error word");
-        HIP_TRY(h, hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
+        if (!d.h_err.alloc_bytes(sizeof(int))) return fail(h, SG_E_NOMEM, "pinned error word");
+        HIP_TRY(h, hipEventCreateWithFlags(d.done.put(), hipEventDisableTiming));
     }
     if (d.ticket) {  // every slot in flight: complete the oldest (its status waits in `finished`)
         hipError_t e = hipEventSynchronize(d.done);
@@ -4068,52 +3659,31 @@ int sg_slot_decide_batch_host(sg_handle* h, const sg_local_event* ev, const sg_s
     if (!ev || !out) return fail(h, SG_E_INVAL, "null buffer");
     if (n > h->cfg.max_batch) return fail(h, SG_E_CAPACITY, "batch larger than max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_lev_h) {
-        if (hipMalloc(&h->d_lev_h, sizeof(sg_local_event) * h->cfg.max_batch) != hipSuccess ||
-            hipMalloc(&h->d_lout_h, sizeof(sg_local_result) * h->cfg.max_batch) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "host-path buffers");
-    }
-    if (ext && !h->d_lext_h && hipMalloc(&h->d_lext_h, sizeof(sg_slot_ext) * h->cfg.max_batch) != hipSuccess)
-        return fail(h, SG_E_NOMEM, "host-path buffers");
+    // the events and the results through host_batch (slots 0, 1); ext and the arguments in slots 2, 3; the values,
+    // of any length, in a buffer of this call
+    sg_slot_ext* d_ext = nullptr;
     sg_pslot_arg* d_args = nullptr;
-    uint64_t* d_vals = nullptr;
-    hipError_t e = hipMemcpy(h->d_lev_h, ev, sizeof(sg_local_event) * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && ext) e = hipMemcpy(h->d_lext_h, ext, sizeof(sg_slot_ext) * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && args && n_args) {
-        e = hipMalloc(&d_args, sizeof(sg_pslot_arg) * n_args);
-        if (e == hipSuccess) e = hipMemcpy(d_args, args, sizeof(sg_pslot_arg) * n_args, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && values && n_values) {
-        e = hipMalloc(&d_vals, sizeof(uint64_t) * n_values);
-        if (e == hipSuccess) e = hipMemcpy(d_vals, values, sizeof(uint64_t) * n_values, hipMemcpyHostToDevice);
-    }
-    int rc = SG_E_DEVICE;
-    if (e == hipSuccess) {
-        rc = local_decide(h, h->d_lev_h, ext ? h->d_lext_h : nullptr, n, d_args, d_args ? n_args : 0, d_vals,
-                          d_vals ? n_values : 0, h->d_lout_h, nullptr);
-        if (rc == SG_OK) e = hipMemcpy(out, h->d_lout_h, sizeof(sg_local_result) * n, hipMemcpyDeviceToHost);
-    }
-    if (d_args) (void)hipFree(d_args);
-    if (d_vals) (void)hipFree(d_vals);
-    if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
-    return rc;
+    DevBuf<uint64_t> d_vals;
+    if (!args) n_args = 0;
+    if (!values) n_values = 0;
+    if ((ext && !h->stage.get(2, h->cfg.max_batch, d_ext)) || (n_args && !h->stage.get(3, n_args, d_args)) ||
+        (n_values && !d_vals.alloc(n_values)))
+        return fail(h, SG_E_NOMEM, "host-path buffers");
+    if (ext) HIP_TRY(h, hipMemcpy(d_ext, ext, sizeof(sg_slot_ext) * n, hipMemcpyHostToDevice));
+    if (n_args) HIP_TRY(h, hipMemcpy(d_args, args, sizeof(sg_pslot_arg) * n_args, hipMemcpyHostToDevice));
+    if (n_values) HIP_TRY(h, hipMemcpy(d_vals, values, sizeof(uint64_t) * n_values, hipMemcpyHostToDevice));
+    return host_batch(h, h->device, ev, n, out, [&](sg_local_event* d_ev, sg_local_result* d_out) {
+        return local_decide(h, d_ev, d_ext, n, d_args, n_args, d_vals, n_values, d_out, nullptr);
+    });
 }
 
 int sg_local_decide_batch_host(sg_handle* h, const sg_local_event* ev, uint64_t n, sg_local_result* out) {
     if (!h) return SG_E_INVAL;
     if (n == 0) return SG_OK;
     if (n > h->cfg.max_batch) return fail(h, SG_E_CAPACITY, "batch larger than max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_lev_h) {
-        if (hipMalloc(&h->d_lev_h, sizeof(sg_local_event) * h->cfg.max_batch) != hipSuccess ||
-            hipMalloc(&h->d_lout_h, sizeof(sg_local_result) * h->cfg.max_batch) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "host-path buffers");
-    }
-    HIP_TRY(h, hipMemcpy(h->d_lev_h, ev, sizeof(sg_local_event) * n, hipMemcpyHostToDevice));
-    int rc = sg_local_decide_batch(h, h->d_lev_h, n, h->d_lout_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpy(out, h->d_lout_h, sizeof(sg_local_result) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    return host_batch(h, h->device, ev, n, out, [&](sg_local_event* d_ev, sg_local_result* d_out) {
+        return sg_local_decide_batch(h, d_ev, n, d_out, nullptr);
+    });
 }
 
 namespace {
@@ -4165,7 +3735,7 @@ int local_read_pool_node(sg_handle* h, uint64_t key, int64_t* second, int64_t* b
     uint32_t node = kNoNode;
     if (h->d_lnkeys) {
         HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, launch_lnode_find(h->d_lnkeys, h->d_lnvals, h->l_nmap_cap - 1, key, h->d_lnode_new, 0));
+        HIP_TRY(h, launch_lnode_find(h->d_lnkeys, h->d_lnvals, h->d_lnkeys.size() - 1, key, h->d_lnode_new, 0));
         HIP_TRY(h, hipMemcpy(&node, h->d_lnode_new, sizeof(node), hipMemcpyDeviceToHost));
     }
     // A node a refused batch created past the pool's capacity (lnode_grow failed, l_pool_used moved past it) has
@@ -4380,9 +3950,9 @@ int local_apply_groups(sg_handle* h) {
     }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
-    dfree(h->d_lgkey);
+    h->d_lgkey.reset();
     if (groups) {
-        if (hipMalloc(&h->d_lgkey, sizeof(uint32_t) * K) != hipSuccess) return fail(h, SG_E_NOMEM, "key groups");
+        if (!h->d_lgkey.alloc_bytes(sizeof(uint32_t) * K)) return fail(h, SG_E_NOMEM, "key groups");
         HIP_TRY(h, hipMemcpy(h->d_lgkey, gkey.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice));
     }
     if (K) HIP_TRY(h, hipMemcpy(h->d_lrules, h->ltab.data(), sizeof(LRule) * K, hipMemcpyHostToDevice));
@@ -4477,17 +4047,10 @@ int sg_local_load_flow_rules(sg_handle* h, const sg_local_flow_rule* rules, uint
     // the nodes (ClusterNodes and the pool) are untouched: statistics outlive the reload
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
-    LFlowRule* d_fr = nullptr;
-    LCtl* d_ctl = nullptr;
-    auto release = [&]() {
-        dfree(d_fr);
-        dfree(d_ctl);
-    };
-    if (!fr.empty() && (hipMalloc(&d_fr, sizeof(LFlowRule) * fr.size()) != hipSuccess ||
-                        hipMalloc(&d_ctl, sizeof(LCtl) * fr.size()) != hipSuccess)) {
-        release();
+    DevBuf<LFlowRule> d_fr;
+    DevBuf<LCtl> d_ctl;
+    if (!fr.empty() && (!d_fr.alloc(fr.size()) || !d_ctl.alloc(fr.size())))
         return fail(h, SG_E_NOMEM, "local flow rule allocation");
-    }
     hipError_t e = hipSuccess;
     if (!fr.empty()) {
         e = hipMemcpy(d_fr, fr.data(), sizeof(LFlowRule) * fr.size(), hipMemcpyHostToDevice);
@@ -4495,14 +4058,9 @@ int sg_local_load_flow_rules(sg_handle* h, const sg_local_flow_rule* rules, uint
         if (e == hipSuccess) e = hipMemcpy(d_ctl, c.data(), sizeof(LCtl) * c.size(), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        release();
-        return fail(h, SG_E_DEVICE, std::string("local flow rule upload: ") + hipGetErrorString(e));
-    }
-    dfree(h->d_lfrules);
-    dfree(h->d_lctl);
-    h->d_lfrules = d_fr;
-    h->d_lctl = d_ctl;
+    if (e != hipSuccess) return fail(h, SG_E_DEVICE, std::string("local flow rule upload: ") + hipGetErrorString(e));
+    h->d_lfrules = std::move(d_fr);
+    h->d_lctl = std::move(d_ctl);
     h->ltab = tab;
     h->l_base_cx = base_cx;
     h->l_relate = relate;
@@ -4528,8 +4086,8 @@ int conc_prepare(sg_handle* h) {
     HIP_TRY(h, hipSetDevice(h->device));
     if (!h->d_ctok) {
         h->ctok_slots = 1ull << 20;
-        if (hipMalloc(&h->d_ctok, sizeof(CTok) * h->ctok_slots) != hipSuccess ||
-            hipMalloc(&h->d_calive, h->cfg.max_batch) != hipSuccess || hipMalloc(&h->d_clast_ts, sizeof(int64_t)) != hipSuccess)
+        if (!h->d_ctok.alloc_bytes(sizeof(CTok) * h->ctok_slots) ||
+            !h->d_calive.alloc_bytes(h->cfg.max_batch) || !h->d_clast_ts.alloc_bytes(sizeof(int64_t)))
             return fail(h, SG_E_NOMEM, "concurrent token table");
         HIP_TRY(h, hipMemset(h->d_ctok, 0, sizeof(CTok) * h->ctok_slots));
         const int64_t neg = -1;
@@ -4555,15 +4113,15 @@ int conc_prepare(sg_handle* h) {
     if (!h->cnow_pending && h->d_cnow && now.size() == K) {  // unchanged rules: keep the device counters
         HIP_TRY(h, hipMemcpy(now.data(), h->d_cnow, sizeof(int32_t) * K, hipMemcpyDeviceToHost));
     }
-    dfree(h->d_cnow);
-    dfree(h->d_cthr);
-    dfree(h->d_coff);
-    dfree(h->d_cres);
-    dfree(h->d_cfid);
+    h->d_cnow.reset();
+    h->d_cthr.reset();
+    h->d_coff.reset();
+    h->d_cres.reset();
+    h->d_cfid.reset();
     const size_t k1 = K ? K : 1;
-    if (hipMalloc(&h->d_cnow, sizeof(int32_t) * k1) != hipSuccess || hipMalloc(&h->d_cthr, sizeof(double) * k1) != hipSuccess ||
-        hipMalloc(&h->d_coff, sizeof(int64_t) * k1) != hipSuccess || hipMalloc(&h->d_cres, sizeof(int64_t) * k1) != hipSuccess ||
-        hipMalloc(&h->d_cfid, sizeof(int64_t) * k1) != hipSuccess)
+    if (!h->d_cnow.alloc_bytes(sizeof(int32_t) * k1) || !h->d_cthr.alloc_bytes(sizeof(double) * k1) ||
+        !h->d_coff.alloc_bytes(sizeof(int64_t) * k1) || !h->d_cres.alloc_bytes(sizeof(int64_t) * k1) ||
+        !h->d_cfid.alloc_bytes(sizeof(int64_t) * k1))
         return fail(h, SG_E_NOMEM, "concurrency rule state");
     if (K) {
         HIP_TRY(h, hipMemcpy(h->d_cnow, now.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice));
@@ -4595,7 +4153,7 @@ ConcArgs conc_args(sg_handle* h) {
     c.fid = h->d_fid;
     c.fid_mask = h->fid_mask;
     c.alive = h->d_calive;
-    c.err = h->d_err;
+    c.err = h->ws[0].err;
     c.last_ts = h->d_clast_ts;
     return c;
 }
@@ -4604,23 +4162,21 @@ ConcArgs conc_args(sg_handle* h) {
 int conc_reserve(sg_handle* h, uint64_t n) {
     if (h->ctok_used + n <= h->ctok_slots / 2) return SG_OK;
     ConcArgs c = conc_args(h);
-    unsigned long long* d_live = nullptr;
-    HIP_TRY(h, hipMalloc(&d_live, sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d_live;
+    if (!d_live.alloc(1)) return fail(h, SG_E_DEVICE, "live counter: out of memory");
     HIP_TRY(h, hipMemset(d_live, 0, sizeof(unsigned long long)));
     HIP_TRY(h, launch_conc_count(c, d_live, 0));
     unsigned long long live = 0;
     HIP_TRY(h, hipMemcpy(&live, d_live, sizeof(live), hipMemcpyDeviceToHost));
-    (void)hipFree(d_live);
     uint64_t slots = 1ull << 20;
     while (slots < 4 * (live + n)) slots <<= 1;
-    CTok* t = nullptr;
-    if (hipMalloc(&t, sizeof(CTok) * slots) != hipSuccess) return fail(h, SG_E_NOMEM, "concurrent token table");
+    DevBuf<CTok> t;
+    if (!t.alloc(slots)) return fail(h, SG_E_NOMEM, "concurrent token table");
     HIP_TRY(h, hipMemset(t, 0, sizeof(CTok) * slots));
-    HIP_TRY(h, hipMemset(h->d_err, 0, sizeof(int)));
-    HIP_TRY(h, launch_conc_rehash(h->d_ctok, h->ctok_slots, t, slots - 1, h->d_err, 0));
+    HIP_TRY(h, hipMemset(h->ws[0].err, 0, sizeof(int)));
+    HIP_TRY(h, launch_conc_rehash(h->d_ctok, h->ctok_slots, t, slots - 1, h->ws[0].err, 0));
     HIP_TRY(h, hipDeviceSynchronize());
-    dfree(h->d_ctok);
-    h->d_ctok = t;
+    h->d_ctok = std::move(t);
     h->ctok_slots = slots;
     h->ctok_used = live;
     return SG_OK;
@@ -4658,12 +4214,12 @@ int sg_conc_decide_batch(sg_handle* h, const sg_conc_req* req, uint64_t n, sg_co
     c.req = req;
     c.out = out;
     c.n = n;
-    c.rec = h->d_rec;
+    c.rec = h->ws[0].rec;
     c.kshift = 64 - kbits;
     c.imask = (1ull << c.kshift) - 1;
-    HIP_TRY(h, hipMemsetAsync(h->d_err, 0, sizeof(int), stream));
-    HIP_TRY(h, launch_conc_batch(c, h->d_rec_sorted, h->d_hist, stream));
-    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemsetAsync(h->ws[0].err, 0, sizeof(int), stream));
+    HIP_TRY(h, launch_conc_batch(c, h->ws[0].rec_sorted, h->ws[0].hist, stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     if (*h->h_err & kErrTime)
         return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
@@ -4677,17 +4233,9 @@ int sg_conc_decide_batch_host(sg_handle* h, const sg_conc_req* req, uint64_t n, 
     if (!h) return SG_E_INVAL;
     if (n == 0) return SG_OK;
     if (n > h->cfg.max_batch) return fail(h, SG_E_CAPACITY, "batch larger than max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_creq_h) {
-        if (hipMalloc(&h->d_creq_h, sizeof(sg_conc_req) * h->cfg.max_batch) != hipSuccess ||
-            hipMalloc(&h->d_cout_h, sizeof(sg_conc_result) * h->cfg.max_batch) != hipSuccess)
-            return fail(h, SG_E_NOMEM, "host-path buffers");
-    }
-    HIP_TRY(h, hipMemcpy(h->d_creq_h, req, sizeof(sg_conc_req) * n, hipMemcpyHostToDevice));
-    int rc = sg_conc_decide_batch(h, h->d_creq_h, n, h->d_cout_h, nullptr);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpy(out, h->d_cout_h, sizeof(sg_conc_result) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    return host_batch(h, h->device, req, n, out, [&](sg_conc_req* d_req, sg_conc_result* d_out) {
+        return sg_conc_decide_batch(h, d_req, n, d_out, nullptr);
+    });
 }
 
 int sg_conc_expire(sg_handle* h, int64_t now_ms, const uint8_t* client_online, uint32_t n_clients, uint64_t* removed) {
@@ -4696,17 +4244,14 @@ int sg_conc_expire(sg_handle* h, int64_t now_ms, const uint8_t* client_online, u
     drain_async(h);
     int rc = conc_prepare(h);
     if (rc) return rc;
-    uint8_t* d_on = nullptr;
-    unsigned long long* d_rm = nullptr;
-    HIP_TRY(h, hipMalloc(&d_on, n_clients ? n_clients : 1));
-    HIP_TRY(h, hipMalloc(&d_rm, sizeof(unsigned long long)));
+    DevBuf<uint8_t> d_on;
+    DevBuf<unsigned long long> d_rm;
+    if (!d_on.alloc(n_clients ? n_clients : 1) || !d_rm.alloc(1)) return fail(h, SG_E_DEVICE, "expire buffers: out of memory");
     hipError_t e = n_clients ? hipMemcpy(d_on, client_online, n_clients, hipMemcpyHostToDevice) : hipSuccess;
     if (e == hipSuccess) e = hipMemset(d_rm, 0, sizeof(unsigned long long));
     if (e == hipSuccess) e = launch_conc_expire(conc_args(h), now_ms, d_on, n_clients, d_rm, 0);
     unsigned long long rm = 0;
     if (e == hipSuccess) e = hipMemcpy(&rm, d_rm, sizeof(rm), hipMemcpyDeviceToHost);
-    (void)hipFree(d_on);
-    (void)hipFree(d_rm);
     if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
     if (removed) *removed = rm;
     return SG_OK;
@@ -4720,13 +4265,12 @@ int sg_conc_read_state(sg_handle* h, uint32_t key, int32_t* now_calls, uint64_t*
     if (rc) return rc;
     if (now_calls) HIP_TRY(h, hipMemcpy(now_calls, h->d_cnow + key, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (live_tokens) {
-        unsigned long long* d = nullptr;
-        HIP_TRY(h, hipMalloc(&d, sizeof(unsigned long long)));
+        DevBuf<unsigned long long> d;
+        if (!d.alloc(1)) return fail(h, SG_E_DEVICE, "live counter: out of memory");
         hipError_t e = hipMemset(d, 0, sizeof(unsigned long long));
         if (e == hipSuccess) e = launch_conc_count(conc_args(h), d, 0);
         unsigned long long v = 0;
         if (e == hipSuccess) e = hipMemcpy(&v, d, sizeof(v), hipMemcpyDeviceToHost);
-        (void)hipFree(d);
         if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
         *live_tokens = v;
     }
@@ -4746,7 +4290,7 @@ PSArgs pslot_args(sg_handle* h) {
     s.p.hot = h->d_phot;
     s.p.table = h->d_ptable;
     s.p.total_slots = h->ptotal;
-    s.p.err = h->d_err;
+    s.p.err = h->ws[0].err;
     s.n_res = h->ps_nres;
     s.res_begin = h->d_ps_begin;
     s.res_rules = h->d_ps_rules;
@@ -4755,7 +4299,7 @@ PSArgs pslot_args(sg_handle* h) {
     s.inited = h->d_ps_init;
     s.tc = h->d_ps_tc;
     s.tc_mask = h->ps_tc_slots - 1;
-    s.err = h->d_err;
+    s.err = h->ws[0].err;
     s.last_ts = h->d_ps_last_ts;
     return s;
 }
@@ -4802,9 +4346,9 @@ int pslot_apply_groups(sg_handle* h) {
     for (uint32_t k = 0; k < R; ++k) groups = (gkey[k] = find(k)) != k || groups;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
-    dfree(h->d_ps_gkey);
+    h->d_ps_gkey.reset();
     if (groups) {
-        if (hipMalloc(&h->d_ps_gkey, sizeof(uint32_t) * R) != hipSuccess) return fail(h, SG_E_NOMEM, "key groups");
+        if (!h->d_ps_gkey.alloc_bytes(sizeof(uint32_t) * R)) return fail(h, SG_E_NOMEM, "key groups");
         HIP_TRY(h, hipMemcpy(h->d_ps_gkey, gkey.data(), sizeof(uint32_t) * R, hipMemcpyHostToDevice));
     }
     h->ps_groups_stale = false;
@@ -4852,19 +4396,19 @@ int sg_pslot_load_rules(sg_handle* h, const sg_pslot_rule* rules, uint32_t n, co
     }
     begin[n_resources] = (uint32_t)list.size();
     HIP_TRY(h, hipSetDevice(h->device));
-    dfree(h->d_ps_begin);
-    dfree(h->d_ps_rules);
-    dfree(h->d_ps_grade);
-    dfree(h->d_ps_idx);
-    dfree(h->d_ps_init);
-    dfree(h->d_ps_cmode);
-    dfree(h->d_ps_ckey);
+    h->d_ps_begin.reset();
+    h->d_ps_rules.reset();
+    h->d_ps_grade.reset();
+    h->d_ps_idx.reset();
+    h->d_ps_init.reset();
+    h->d_ps_cmode.reset();
+    h->d_ps_ckey.reset();
     const size_t n1 = n ? n : 1;
-    if (hipMalloc(&h->d_ps_begin, sizeof(uint32_t) * (n_resources + 1)) != hipSuccess ||
-        hipMalloc(&h->d_ps_rules, sizeof(uint32_t) * n1) != hipSuccess ||
-        hipMalloc(&h->d_ps_grade, sizeof(int32_t) * n1) != hipSuccess ||
-        hipMalloc(&h->d_ps_idx, sizeof(int32_t) * n1) != hipSuccess || hipMalloc(&h->d_ps_init, sizeof(int32_t) * n1) != hipSuccess ||
-        hipMalloc(&h->d_ps_cmode, sizeof(int32_t) * n1) != hipSuccess || hipMalloc(&h->d_ps_ckey, sizeof(uint32_t) * n1) != hipSuccess)
+    if (!h->d_ps_begin.alloc_bytes(sizeof(uint32_t) * (n_resources + 1)) ||
+        !h->d_ps_rules.alloc_bytes(sizeof(uint32_t) * n1) ||
+        !h->d_ps_grade.alloc_bytes(sizeof(int32_t) * n1) ||
+        !h->d_ps_idx.alloc_bytes(sizeof(int32_t) * n1) || !h->d_ps_init.alloc_bytes(sizeof(int32_t) * n1) ||
+        !h->d_ps_cmode.alloc_bytes(sizeof(int32_t) * n1) || !h->d_ps_ckey.alloc_bytes(sizeof(uint32_t) * n1))
         return fail(h, SG_E_NOMEM, "param slot rules");
     HIP_TRY(h, hipMemcpy(h->d_ps_begin, begin.data(), sizeof(uint32_t) * (n_resources + 1), hipMemcpyHostToDevice));
     if (!list.empty()) HIP_TRY(h, hipMemcpy(h->d_ps_rules, list.data(), sizeof(uint32_t) * list.size(), hipMemcpyHostToDevice));
@@ -4877,8 +4421,8 @@ int sg_pslot_load_rules(sg_handle* h, const sg_pslot_rule* rules, uint32_t n, co
     }
     if (!h->d_ps_tc) {
         h->ps_tc_slots = 1ull << 20;
-        if (hipMalloc(&h->d_ps_tc, sizeof(PSThread) * h->ps_tc_slots) != hipSuccess ||
-            hipMalloc(&h->d_ps_last_ts, sizeof(int64_t)) != hipSuccess)
+        if (!h->d_ps_tc.alloc_bytes(sizeof(PSThread) * h->ps_tc_slots) ||
+            !h->d_ps_last_ts.alloc_bytes(sizeof(int64_t)))
             return fail(h, SG_E_NOMEM, "thread count table");
     }
     HIP_TRY(h, launch_pslot_clear(h->d_ps_tc, h->ps_tc_slots, 0));
@@ -4923,12 +4467,12 @@ int sg_pslot_decide_batch(sg_handle* h, const sg_pslot_event* ev, uint64_t n, co
     s.n_values = n_values;
     s.out = out;
     s.n = n;
-    s.rec = h->d_rec;
+    s.rec = h->ws[0].rec;
     s.kshift = 64 - kbits;
     s.imask = (1ull << s.kshift) - 1;
-    HIP_TRY(h, hipMemsetAsync(h->d_err, 0, sizeof(int), stream));
-    HIP_TRY(h, launch_pslot_batch(s, h->d_rec_sorted, h->d_hist, stream));
-    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipMemsetAsync(h->ws[0].err, 0, sizeof(int), stream));
+    HIP_TRY(h, launch_pslot_batch(s, h->ws[0].rec_sorted, h->ws[0].hist, stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     if (*h->h_err & kErrTime)
         return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
@@ -4942,14 +4486,14 @@ int sg_pslot_decide_batch_host(sg_handle* h, const sg_pslot_event* ev, uint64_t 
     if (!h) return SG_E_INVAL;
     if (n == 0) return SG_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    sg_pslot_event* d_ev = nullptr;
-    sg_pslot_arg* d_args = nullptr;
-    uint64_t* d_vals = nullptr;
-    sg_pslot_result* d_out = nullptr;
-    hipError_t e = hipMalloc(&d_ev, sizeof(sg_pslot_event) * n);
-    if (e == hipSuccess) e = hipMalloc(&d_args, sizeof(sg_pslot_arg) * (n_args ? n_args : 1));
-    if (e == hipSuccess) e = hipMalloc(&d_vals, sizeof(uint64_t) * (n_values ? n_values : 1));
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(sg_pslot_result) * n);
+    // this entry point has no max_batch bound of its own: its buffers are this call's
+    DevBuf<sg_pslot_event> d_ev;
+    DevBuf<sg_pslot_arg> d_args;
+    DevBuf<uint64_t> d_vals;
+    DevBuf<sg_pslot_result> d_out;
+    hipError_t e = d_ev.alloc(n) && d_args.alloc(n_args ? n_args : 1) && d_vals.alloc(n_values ? n_values : 1) && d_out.alloc(n)
+                       ? hipSuccess
+                       : hipErrorOutOfMemory;
     if (e == hipSuccess) e = hipMemcpy(d_ev, ev, sizeof(sg_pslot_event) * n, hipMemcpyHostToDevice);
     if (e == hipSuccess && n_args) e = hipMemcpy(d_args, args, sizeof(sg_pslot_arg) * n_args, hipMemcpyHostToDevice);
     if (e == hipSuccess && n_values) e = hipMemcpy(d_vals, values, sizeof(uint64_t) * n_values, hipMemcpyHostToDevice);
@@ -4958,10 +4502,6 @@ int sg_pslot_decide_batch_host(sg_handle* h, const sg_pslot_event* ev, uint64_t 
         rc = sg_pslot_decide_batch(h, d_ev, n, d_args, n_args, d_vals, n_values, d_out, nullptr);
         if (rc == SG_OK) e = hipMemcpy(out, d_out, sizeof(sg_pslot_result) * n, hipMemcpyDeviceToHost);
     }
-    (void)hipFree(d_ev);
-    (void)hipFree(d_args);
-    (void)hipFree(d_vals);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
     return rc;
 }
@@ -4970,11 +4510,10 @@ int sg_pslot_thread_count(sg_handle* h, uint32_t resource, int32_t param_idx, ui
     if (!h || !count || !h->ps_loaded || resource >= h->ps_nres || param_idx < 0) return SG_E_INVAL;
     HIP_TRY(h, hipSetDevice(h->device));
     drain_async(h);
-    int64_t* d = nullptr;
-    HIP_TRY(h, hipMalloc(&d, sizeof(int64_t)));
+    DevBuf<int64_t> d;
+    if (!d.alloc(1)) return fail(h, SG_E_DEVICE, "read buffer: out of memory");
     hipError_t e = launch_pslot_thread_read(pslot_args(h), resource, param_idx, value, d, 0);
     if (e == hipSuccess) e = hipMemcpy(count, d, sizeof(int64_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(e));
     return SG_OK;
 }
@@ -4992,11 +4531,11 @@ int sg_debug_copy(sg_handle* h, int what, void* dst, uint64_t bytes) {
     const void* src = nullptr;
     uint64_t cap = 0;
     switch (what) {
-    case 0: src = (h->last_sorted == h->d_rec) ? h->d_rec_sorted : h->d_rec; cap = h->cfg.max_batch * 8; break;
-    case 1: src = h->last_sorted ? h->last_sorted : h->d_rec_sorted; cap = h->cfg.max_batch * 8; break;
-    case 2: src = h->d_bnd; cap = sizeof(uint32_t) * kMaxWl * kMaxPeriods; break;
-    case 3: src = h->d_p0; cap = sizeof(int64_t) * kMaxWl; break;
-    case 4: src = h->d_np; cap = sizeof(uint32_t) * kMaxWl; break;
+    case 0: src = (h->last_sorted == h->ws[0].rec) ? h->ws[0].rec_sorted : h->ws[0].rec; cap = h->cfg.max_batch * 8; break;
+    case 1: src = h->last_sorted ? h->last_sorted : h->ws[0].rec_sorted; cap = h->cfg.max_batch * 8; break;
+    case 2: src = h->ws[0].bnd; cap = sizeof(uint32_t) * kMaxWl * kMaxPeriods; break;
+    case 3: src = h->ws[0].p0; cap = sizeof(int64_t) * kMaxWl; break;
+    case 4: src = h->ws[0].np; cap = sizeof(uint32_t) * kMaxWl; break;
     case 5: src = h->d_dbg; cap = 128 * 8; break;
     default: return SG_E_INVAL;
     }
@@ -5018,50 +4557,63 @@ int sg_debug_copy(sg_handle* h, int what, void* dst, uint64_t bytes) {
 // (peer copies for shards on other devices), and gathered back into caller order.
 
 struct sg_node {
+    ~sg_node();  // drains the node, destroys the shards and the front; then devices[0]'s members free under devices[0]
     std::string err;
     sg_config cfg{};
     std::vector<int32_t> devices;       // device of each shard
     sg_handle* front = nullptr;         // devices[0]: validation + namespace limiter over the node batch
     std::vector<sg_handle*> shards;
-    std::vector<hipStream_t> streams;   // one per shard, on its device
-    std::vector<hipEvent_t> done;       // per shard: its slice decided (and copied back)
-    std::vector<int*> h_err;            // pinned, per shard
-    hipStream_t s0 = nullptr;           // devices[0]
-    hipEvent_t routed = nullptr;
+    // What the node keeps for one shard on that shard's device; its destructor makes the device current, so the members
+    // are freed there.
+    struct Shard {
+        explicit Shard(int32_t dev) : device(dev) {}
+        Shard(Shard&&) = default;
+        ~Shard() { (void)hipSetDevice(device); }
+        int32_t device;
+        Stream stream;
+        Event done;                     // its slice decided (and copied back)
+        PinnedBuf<int> h_err;
+        DevBuf<sg_req> r_req;           // a shard on another device than devices[0]: its slice there
+        DevBuf<sg_result> r_out;
+        DevBuf<uint8_t> r_nreq, r_nout; // the same for the param / concurrent slices (see d_sub_nreq)
+        DevBuf<uint64_t> r_vals;
+        DevBuf<double> r_snap;          // its part of the node snapshot
+        DevBuf<sg_metric_node> r_mrows; // its metric rows
+        DevBuf<uint64_t> r_mcnt;        // its row count (on its device wherever that is)
+    };
+    std::vector<Shard> sh;              // one per shard
+    Stream s0;           // devices[0]
+    Event routed;
     std::vector<sg_flow_rule> rules;
     std::vector<uint8_t> shard_of;
     std::vector<uint32_t> local_of;
-    uint8_t* d_shard_of = nullptr;
-    uint32_t* d_local_of = nullptr;
-    uint32_t* d_tile_cnt = nullptr;
-    uint32_t* d_base = nullptr;         // [kMaxShards + 1] bases, then [kMaxShards] totals
-    uint32_t* h_base = nullptr;         // pinned copy
-    int* h_front_err = nullptr;         // pinned
-    sg_req* d_sub_req = nullptr;
-    uint32_t* d_sub_pos = nullptr;
-    sg_result* d_sub_out = nullptr;
-    std::vector<sg_req*> r_req;         // per shard on another device: its slice there
-    std::vector<sg_result*> r_out;
-    sg_req* d_req_h = nullptr;          // host path
-    sg_result* d_out_h = nullptr;
+    DevBuf<uint8_t> d_shard_of;
+    DevBuf<uint32_t> d_local_of;
+    DevBuf<uint32_t> d_tile_cnt;
+    DevBuf<uint32_t> d_base;            // [kMaxShards + 1] bases, then [kMaxShards] totals
+    PinnedBuf<uint32_t> h_base;         // pinned copy
+    PinnedBuf<int> h_front_err;         // pinned
+    DevBuf<sg_req> d_sub_req;
+    DevBuf<uint32_t> d_sub_pos;
+    DevBuf<sg_result> d_sub_out;
     // every shard on the front's device with the front's request-index / acquire layout: the records path (the
     // shards start at the sort, on the front's period tables, and write the caller's results in place)
     bool rec_path = false;
-    uint64_t* d_sub_rec = nullptr;      // [max_batch] the shards' record slices
+    DevBuf<uint64_t> d_sub_rec;         // [max_batch] the shards' record slices
     std::vector<sg_namespace> ns;       // the node's namespaces (rollback of a failed sg_node_set_namespaces)
     // pipelined node batches (sg_node_flow_enqueue, records path): two workspaces alternating, as the single
     // handle's pipeline — the front's k_prep / limiter / routing of batch i+1 and the shards' sorts beside the
     // shards' walkers of batch i
     struct PipeSlot {
         uint64_t ticket = 0;
-        hipEvent_t done = nullptr;   // every shard's back half of the slot's batch (recorded on s0)
-        int* h_err = nullptr;        // pinned [kMaxShards]: each shard's error word
-        uint32_t* h_base = nullptr;  // pinned [2 * kMaxShards + 1]: slice bases and counts
+        Event done;   // every shard's back half of the slot's batch (recorded on s0)
+        PinnedBuf<int> h_err;        // pinned [kMaxShards]: each shard's error word
+        PinnedBuf<uint32_t> h_base;  // pinned [2 * kMaxShards + 1]: slice bases and counts
         uint32_t G_used = 0;         // shards the batch went to
     };
     PipeSlot pipe[2];
-    hipEvent_t fdone[2] = {nullptr, nullptr};  // the front's part of the slot's batch
-    uint64_t* d_sub_rec2 = nullptr;            // workspace 1's record slices
+    Event fdone[2];  // the front's part of the slot's batch
+    DevBuf<uint64_t> d_sub_rec2;               // workspace 1's record slices
     uint64_t pseq = 0, next_ticket = 1;
     std::unordered_map<uint64_t, int> finished;  // tickets completed while making room, not yet collected
     // cluster param and concurrent tokens over the node (sg_node_cparam_*, sg_node_conc_*): a param rule lives on the
@@ -5069,34 +4621,24 @@ struct sg_node {
     std::vector<sg_cparam_rule> cp_rules;
     std::vector<uint8_t> cp_shard_of;
     std::vector<uint32_t> cp_local_of;
-    uint8_t* d_cp_shard_of = nullptr;
-    uint32_t* d_cp_local_of = nullptr;
-    uint64_t* d_nrec = nullptr;        // [max_batch] owner records, then the sort's other buffer
-    uint64_t* d_nrec2 = nullptr;
-    uint32_t* d_nhist = nullptr;
-    uint32_t* d_nvals = nullptr;       // [max_batch]
-    uint32_t* d_ncnt = nullptr;        // [3 * kMaxShards]: requests, values, value bases per shard
-    uint32_t* d_ntsum = nullptr;       // [tiles]
-    int* d_nerr = nullptr;
-    void* d_sub_nreq = nullptr;        // [max_batch] slices (sg_cparam_req / sg_conc_req: 24 B / 32 B each)
-    void* d_sub_nout = nullptr;        // [max_batch] slice results (sg_result / sg_conc_result)
-    uint64_t* d_sub_vals = nullptr;    // the param slices' values
-    uint64_t sub_vals_cap = 0;
-    std::vector<void*> r_nreq, r_nout; // shards on other devices: their slices there
-    std::vector<uint64_t*> r_vals;
-    std::vector<uint64_t> r_vals_cap;
+    DevBuf<uint8_t> d_cp_shard_of;
+    DevBuf<uint32_t> d_cp_local_of;
+    DevBuf<uint64_t> d_nrec;           // [max_batch] owner records, then the sort's other buffer
+    DevBuf<uint64_t> d_nrec2;
+    DevBuf<uint32_t> d_nhist;
+    DevBuf<uint32_t> d_nvals;          // [max_batch]
+    DevBuf<uint32_t> d_ncnt;           // [3 * kMaxShards]: requests, values, value bases per shard
+    DevBuf<uint32_t> d_ntsum;          // [tiles]
+    DevBuf<int> d_nerr;
+    DevBuf<uint8_t> d_sub_nreq;        // [max_batch] slices (sg_cparam_req / sg_conc_req: 24 B / 32 B each)
+    DevBuf<uint8_t> d_sub_nout;        // [max_batch] slice results (sg_result / sg_conc_result)
+    DevBuf<uint64_t> d_sub_vals;       // the param slices' values
     int64_t cp_last_ts = -1, cc_last_ts = -1;  // the node's previous param / concurrent batch (time order)
-    // host-path staging
-    void* d_nreq_h = nullptr;
-    void* d_nout_h = nullptr;
-    uint64_t* d_nvals_h = nullptr;
-    uint64_t nvals_h_cap = 0;
+    Staging stage;                     // the _host entry points' device copies (host_batch), on devices[0]
     // node snapshot on the device: each shard's part gathered into the front's buffer in node rule order
-    std::vector<uint32_t*> d_node_key;  // per shard (on the front's device): node rule of each local rule
-    double* d_snap = nullptr;
-    uint64_t snap_cap = 0;
+    std::vector<DevBuf<uint32_t>> d_node_key;  // per shard (on the front's device): node rule of each local rule
+    DevBuf<double> d_snap;
     bool node_key_stale = true;         // the flow rules changed since d_node_key was built
-    std::vector<double*> r_snap;        // per shard on another device: its part there
     // the local slot chain over the node (sg_node_local_*): every shard holds the node's rules under the node's
     // resource indices and decides the events of the resources it owns; the front is the staging copy of the rules
     // (it carries no local traffic) and names the owners
@@ -5107,26 +4649,19 @@ struct sg_node {
     bool l_has_frules = false;
     int32_t l_n_origins = 0, l_n_contexts = 0;
     std::vector<uint32_t> l_owner;      // [K] owner shard of each resource
-    uint8_t* d_l_owner = nullptr;       // the same on devices[0]
+    DevBuf<uint8_t> d_l_owner;          // the same on devices[0]
     int64_t l_last_ts = -1;             // the node's previous local batch (time order)
     uint64_t l_batches = 0;             // local batches decided since sg_node_local_load_rules
-    sg_local_event* d_lsub_ev = nullptr;   // [max_batch] the shards' slices
-    sg_local_result* d_lsub_out = nullptr; // [max_batch] their results
-    sg_local_event* d_lev_h = nullptr;     // host path
-    sg_local_result* d_lout_h = nullptr;
-    int* d_lerr = nullptr;
+    DevBuf<sg_local_event> d_lsub_ev;      // [max_batch] the shards' slices
+    DevBuf<sg_local_result> d_lsub_out;    // [max_batch] their results
+    DevBuf<int> d_lerr;
     // the node's metric rows: every shard's raw rows one after the other, merged by k_merge_*
-    unsigned long long* d_mbits = nullptr;  // [60][W]
-    uint32_t* d_mpre = nullptr;             // [60][W]
+    DevBuf<unsigned long long> d_mbits;     // [60][W]
+    DevBuf<uint32_t> d_mpre;                // [60][W]
     uint32_t m_words = 0;                   // W of the allocation
-    MergeSlots* d_mslots = nullptr;
-    sg_metric_node* d_mrows = nullptr;      // the shards' raw rows (grown on demand)
-    uint64_t mrows_cap = 0;
-    sg_metric_node* d_mout = nullptr;       // the host form's merged table
-    uint64_t mout_cap = 0;
-    std::vector<sg_metric_node*> r_mrows;   // per shard on another device: its rows there
-    std::vector<uint64_t> r_mrows_cap;
-    std::vector<uint64_t*> r_mcnt;          // per shard, on its device: its row count
+    DevBuf<MergeSlots> d_mslots;
+    DevBuf<sg_metric_node> d_mrows;         // the shards' raw rows (grown on demand)
+    DevBuf<sg_metric_node> d_mout;          // the host form's merged table
 };
 
 namespace {
@@ -5187,7 +4722,7 @@ int node_sync_layout(sg_node* nd) {
     nd->rec_path = same && std::getenv("SG_NODE_LEGACY") == nullptr;
     if (nd->rec_path && !nd->d_sub_rec) {
         NHIP(nd, hipSetDevice(nd->devices[0]));
-        if (hipMalloc(&nd->d_sub_rec, sizeof(uint64_t) * (nd->cfg.max_batch + kRecW)) != hipSuccess)
+        if (!nd->d_sub_rec.alloc_bytes(sizeof(uint64_t) * (nd->cfg.max_batch + kRecW)))
             return nfail(nd, SG_E_NOMEM, "shard record slices");
     }
     return SG_OK;
@@ -5210,9 +4745,9 @@ int node_walk_cus(const sg_node* nd, uint32_t g, int cus) {
 
 // Waits for the shard streams [0, g) (an early return must not leave slices in flight).
 void node_sync_shards(sg_node* nd, uint32_t g) {
-    for (uint32_t x = 0; x < g && x < nd->streams.size(); ++x) {
+    for (uint32_t x = 0; x < g && x < nd->sh.size(); ++x) {
         (void)hipSetDevice(nd->devices[x]);
-        (void)hipStreamSynchronize(nd->streams[x]);
+        (void)hipStreamSynchronize(nd->sh[x].stream);
     }
     (void)hipSetDevice(nd->devices[0]);
 }
@@ -5273,88 +4808,17 @@ int node_drain(sg_node* nd) {
 
 }  // namespace
 
+sg_node::~sg_node() {
+    node_drain(this);
+    for (size_t g = 0; g < shards.size(); ++g) sg_destroy(shards[g]);
+    sh.clear();  // each under its own device
+    sg_destroy(front);
+    (void)hipSetDevice(devices.empty() ? 0 : devices[0]);
+}
+
 extern "C" {
 
-void sg_node_destroy(sg_node* nd) {
-    if (!nd) return;
-    node_drain(nd);
-    for (size_t g = 0; g < nd->shards.size(); ++g) {
-        (void)hipSetDevice(nd->devices[g]);
-        if (g < nd->streams.size() && nd->streams[g]) (void)hipStreamDestroy(nd->streams[g]);
-        if (g < nd->done.size() && nd->done[g]) (void)hipEventDestroy(nd->done[g]);
-        if (g < nd->h_err.size() && nd->h_err[g]) (void)hipHostFree(nd->h_err[g]);
-        if (g < nd->r_req.size()) dfree(nd->r_req[g]);
-        if (g < nd->r_out.size()) dfree(nd->r_out[g]);
-        sg_destroy(nd->shards[g]);
-    }
-    if (!nd->devices.empty()) (void)hipSetDevice(nd->devices[0]);
-    if (nd->s0) (void)hipStreamDestroy(nd->s0);
-    if (nd->routed) (void)hipEventDestroy(nd->routed);
-    dfree(nd->d_shard_of);
-    dfree(nd->d_local_of);
-    dfree(nd->d_tile_cnt);
-    dfree(nd->d_base);
-    dfree(nd->d_sub_req);
-    dfree(nd->d_sub_pos);
-    dfree(nd->d_sub_out);
-    dfree(nd->d_req_h);
-    dfree(nd->d_out_h);
-    dfree(nd->d_sub_rec);
-    dfree(nd->d_sub_rec2);
-    dfree(nd->d_cp_shard_of);
-    dfree(nd->d_cp_local_of);
-    dfree(nd->d_nrec);
-    dfree(nd->d_nrec2);
-    dfree(nd->d_nhist);
-    dfree(nd->d_nvals);
-    dfree(nd->d_ncnt);
-    dfree(nd->d_ntsum);
-    dfree(nd->d_nerr);
-    dfree(nd->d_sub_nreq);
-    dfree(nd->d_sub_nout);
-    dfree(nd->d_sub_vals);
-    dfree(nd->d_nreq_h);
-    dfree(nd->d_nout_h);
-    dfree(nd->d_nvals_h);
-    dfree(nd->d_snap);
-    dfree(nd->d_l_owner);
-    dfree(nd->d_lsub_ev);
-    dfree(nd->d_lsub_out);
-    dfree(nd->d_lev_h);
-    dfree(nd->d_lout_h);
-    dfree(nd->d_lerr);
-    dfree(nd->d_mbits);
-    dfree(nd->d_mpre);
-    dfree(nd->d_mslots);
-    dfree(nd->d_mrows);
-    dfree(nd->d_mout);
-    for (size_t g = 0; g < nd->r_mcnt.size(); ++g) {
-        (void)hipSetDevice(nd->devices[g]);
-        dfree(nd->r_mrows[g]);
-        dfree(nd->r_mcnt[g]);
-    }
-    (void)hipSetDevice(nd->devices.empty() ? 0 : nd->devices[0]);
-    for (uint32_t* p : nd->d_node_key) dfree(p);
-    for (size_t g = 0; g < nd->r_nreq.size(); ++g) {
-        (void)hipSetDevice(nd->devices[g]);
-        dfree(nd->r_nreq[g]);
-        dfree(nd->r_nout[g]);
-        dfree(nd->r_vals[g]);
-        if (g < nd->r_snap.size()) dfree(nd->r_snap[g]);
-    }
-    (void)hipSetDevice(nd->devices.empty() ? 0 : nd->devices[0]);
-    for (auto& sl : nd->pipe) {
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.h_err) (void)hipHostFree(sl.h_err);
-        if (sl.h_base) (void)hipHostFree(sl.h_base);
-    }
-    for (hipEvent_t e : nd->fdone)
-        if (e) (void)hipEventDestroy(e);
-    if (nd->h_base) (void)hipHostFree(nd->h_base);
-    if (nd->h_front_err) (void)hipHostFree(nd->h_front_err);
-    sg_destroy(nd->front);
-    delete nd;
-}
+void sg_node_destroy(sg_node* nd) { delete nd; }
 
 const char* sg_node_last_error(const sg_node* nd) { return nd ? nd->err.c_str() : "null node"; }
 
@@ -5364,8 +4828,9 @@ int sg_node_create(const sg_config* cfg, const int32_t* devices, uint32_t n_shar
     sg_node* nd = new sg_node();
     nd->cfg = *cfg;
     nd->devices.assign(devices, devices + n_shards);
+    nd->sh.reserve(n_shards);
     auto bail = [&](int rc) {
-        sg_node_destroy(nd);
+        delete nd;
         return rc;
     };
     sg_config c = *cfg;
@@ -5380,24 +4845,13 @@ int sg_node_create(const sg_config* cfg, const int32_t* devices, uint32_t n_shar
         if (rc) return bail(rc);
         nd->shards.push_back(h);
         if (hipSetDevice(devices[g]) != hipSuccess) return bail(SG_E_DEVICE);
-        hipStream_t st = nullptr;
-        hipEvent_t ev = nullptr;
-        int* he = nullptr;
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess ||
-            hipHostMalloc(&he, sizeof(int)) != hipSuccess)
+        nd->sh.emplace_back(devices[g]);
+        sg_node::Shard& s = nd->sh.back();
+        if (hipStreamCreateWithFlags(s.stream.put(), hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(s.done.put(), hipEventDisableTiming) != hipSuccess || !s.h_err.alloc(1))
             return bail(SG_E_DEVICE);
-        nd->streams.push_back(st);
-        nd->done.push_back(ev);
-        nd->h_err.push_back(he);
-        sg_req* rq = nullptr;
-        sg_result* ro = nullptr;
-        if (devices[g] != devices[0] &&
-            (hipMalloc(&rq, sizeof(sg_req) * cfg->max_batch) != hipSuccess ||
-             hipMalloc(&ro, sizeof(sg_result) * cfg->max_batch) != hipSuccess))
+        if (devices[g] != devices[0] && (!s.r_req.alloc(cfg->max_batch) || !s.r_out.alloc(cfg->max_batch)))
             return bail(SG_E_NOMEM);
-        nd->r_req.push_back(rq);
-        nd->r_out.push_back(ro);
     }
     // shards on other devices: peer access both ways (their slices and results cross xGMI as peer copies)
     for (uint32_t g = 1; g < n_shards; ++g) {
@@ -5419,24 +4873,16 @@ int sg_node_create(const sg_config* cfg, const int32_t* devices, uint32_t n_shar
         (void)hipGetLastError();  // an already-enabled peer leaves its error behind
     }
     if (hipSetDevice(devices[0]) != hipSuccess) return bail(SG_E_DEVICE);
-    nd->r_nreq.assign(n_shards, nullptr);
-    nd->r_nout.assign(n_shards, nullptr);
-    nd->r_vals.assign(n_shards, nullptr);
-    nd->r_vals_cap.assign(n_shards, 0);
-    nd->r_snap.assign(n_shards, nullptr);
-    nd->r_mrows.assign(n_shards, nullptr);
-    nd->r_mrows_cap.assign(n_shards, 0);
-    nd->r_mcnt.assign(n_shards, nullptr);
     const uint64_t n = cfg->max_batch;
-    if (hipStreamCreateWithFlags(&nd->s0, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&nd->routed, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc(&nd->d_tile_cnt, sizeof(uint32_t) * kMaxShards * (route_tiles(n) + 1)) != hipSuccess ||
-        hipMalloc(&nd->d_base, sizeof(uint32_t) * (2 * kMaxShards + 1)) != hipSuccess ||
-        hipMalloc(&nd->d_sub_req, sizeof(sg_req) * n) != hipSuccess ||
-        hipMalloc(&nd->d_sub_pos, sizeof(uint32_t) * n) != hipSuccess ||
-        hipMalloc(&nd->d_sub_out, sizeof(sg_result) * n) != hipSuccess ||
-        hipHostMalloc(&nd->h_base, sizeof(uint32_t) * (2 * kMaxShards + 1)) != hipSuccess ||
-        hipHostMalloc(&nd->h_front_err, sizeof(int)) != hipSuccess)
+    if (hipStreamCreateWithFlags(nd->s0.put(), hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(nd->routed.put(), hipEventDisableTiming) != hipSuccess ||
+        !nd->d_tile_cnt.alloc_bytes(sizeof(uint32_t) * kMaxShards * (route_tiles(n) + 1)) ||
+        !nd->d_base.alloc_bytes(sizeof(uint32_t) * (2 * kMaxShards + 1)) ||
+        !nd->d_sub_req.alloc_bytes(sizeof(sg_req) * n) ||
+        !nd->d_sub_pos.alloc_bytes(sizeof(uint32_t) * n) ||
+        !nd->d_sub_out.alloc_bytes(sizeof(sg_result) * n) ||
+        !nd->h_base.alloc_bytes(sizeof(uint32_t) * (2 * kMaxShards + 1)) ||
+        !nd->h_front_err.alloc_bytes(sizeof(int)))
         return bail(SG_E_NOMEM);
     *out = nd;
     return SG_OK;
@@ -5494,8 +4940,8 @@ int sg_node_load_flow_rules(sg_node* nd, const sg_flow_rule* rules, uint32_t n) 
         part[g].push_back(rules[k]);
     }
     std::vector<FlowLoad> prep(G + 1);
-    uint8_t* d_so = nullptr;
-    uint32_t* d_lo = nullptr;
+    DevBuf<uint8_t> d_so;
+    DevBuf<uint32_t> d_lo;
     auto abort_all = [&](uint32_t upto) {  // the prepared shards [0, upto), the front's (index G) and the tables
         for (uint32_t x = 0; x < upto; ++x) {
             (void)hipSetDevice(nd->devices[x]);
@@ -5503,8 +4949,8 @@ int sg_node_load_flow_rules(sg_node* nd, const sg_flow_rule* rules, uint32_t n) 
         }
         (void)hipSetDevice(nd->devices[0]);
         flow_rules_abort(prep[G]);
-        dfree(d_so);
-        dfree(d_lo);
+        d_so.reset();
+        d_lo.reset();
     };
     // env SG_TEST_NODE_FAIL_SHARD = g (tests): preparing shard g fails as an allocation would
     const char* inj = std::getenv("SG_TEST_NODE_FAIL_SHARD");
@@ -5524,7 +4970,7 @@ int sg_node_load_flow_rules(sg_node* nd, const sg_flow_rule* rules, uint32_t n) 
     }
     NHIP(nd, hipSetDevice(nd->devices[0]));
     rc = flow_rules_prepare(f, rules, n, prep[G]);
-    if (!rc && n && (hipMalloc(&d_so, n) != hipSuccess || hipMalloc(&d_lo, sizeof(uint32_t) * n) != hipSuccess ||
+    if (!rc && n && (!d_so.alloc_bytes(n) || !d_lo.alloc_bytes(sizeof(uint32_t) * n) ||
                      hipMemcpy(d_so, so.data(), n, hipMemcpyHostToDevice) != hipSuccess ||
                      hipMemcpy(d_lo, lo.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess))
         rc = fail(f, SG_E_NOMEM, "routing tables");
@@ -5542,10 +4988,8 @@ int sg_node_load_flow_rules(sg_node* nd, const sg_flow_rule* rules, uint32_t n) 
     NHIP(nd, hipSetDevice(nd->devices[0]));
     rc = flow_rules_commit(f, rules, n, prep[G]);
     if (rc) return node_child(nd, f, rc);
-    dfree(nd->d_shard_of);
-    dfree(nd->d_local_of);
-    nd->d_shard_of = d_so;
-    nd->d_local_of = d_lo;
+    nd->d_shard_of = std::move(d_so);
+    nd->d_local_of = std::move(d_lo);
     nd->rules.assign(rules, rules + n);
     nd->shard_of = so;
     nd->local_of = lo;
@@ -5577,8 +5021,7 @@ int sg_node_flow_decide_batch(sg_node* nd, const sg_req* req, uint64_t n, sg_res
     // 1. the front: validation + namespace limiter in caller order, the batch's time check, its last timestamp, the
     // default results in the caller's buffer, the batch's period tables
     NHIP(nd, hipStreamSynchronize(user));  // the caller's batch is in place
-    sg_handle::FlowWs w;
-    main_ws(f, w);
+    sg_handle::FlowWs& w = f->ws[0];
     BatchArgs a = flow_args(f, w, req, n, out);
     // one shard holding every rule in the front's order (G = 1): the front's records are its records as they are
     const bool direct = nd->rec_path && G == 1 && nd->shards[0]->K == f->K && nd->shards[0]->kbits == f->kbits;
@@ -5631,20 +5074,19 @@ int sg_node_flow_decide_batch(sg_node* nd, const sg_req* req, uint64_t n, sg_res
     // 3. every shard decides its slice on its own stream
     for (uint32_t g = 0; g < G; ++g) {
         const uint32_t base = nd->h_base[g], cnt = nd->h_base[kMaxShards + 1 + g];
-        *nd->h_err[g] = 0;
+        *nd->sh[g].h_err = 0;
         if (cnt == 0) continue;
         sg_handle* h = nd->shards[g];
         const int dev = nd->devices[g];
         NHIP(nd, hipSetDevice(dev));
-        NHIP(nd, hipStreamWaitEvent(nd->streams[g], nd->routed, 0));
+        NHIP(nd, hipStreamWaitEvent(nd->sh[g].stream, nd->routed, 0));
         if (nd->rec_path) {
             // the slice's records (node request indices) through the shard's sort and walkers; the period tables,
             // window lengths, requests and results are the node batch's
-            sg_handle::FlowWs sw;
-            main_ws(h, sw);
+            sg_handle::FlowWs& sw = h->ws[0];
             BatchArgs b = flow_args(h, sw, req, cnt, out);
             b.rec = direct ? a.rec : nd->d_sub_rec + base;
-            b.rec_sorted = direct ? h->d_rec_sorted : sw.rec;  // the sort's other buffer
+            b.rec_sorted = direct ? h->ws[0].rec_sorted : sw.rec;  // the sort's other buffer
             b.hist0 = direct ? a.hist0 : nullptr;
             b.hist0_bits = a.hist0_bits;
             b.csum0 = direct ? a.csum0 : nullptr;
@@ -5654,9 +5096,9 @@ int sg_node_flow_decide_batch(sg_node* nd, const sg_req* req, uint64_t n, sg_res
             b.p0 = a.p0;
             b.np = a.np;
             b.walk_cus = node_walk_cus(nd, g, 0);
-            hipStream_t st = nd->streams[g];
+            hipStream_t st = nd->sh[g].stream;
             rc = node_shard_rec(h, b, cnt, direct ? w.hist : sw.hist, st, st, h->aux, h->fork, h->join, nullptr,
-                                nd->h_err[g]);
+                                nd->sh[g].h_err);
             if (rc) {
                 node_sync_shards(nd, g + 1);
                 return node_child(nd, h, rc);
@@ -5665,31 +5107,31 @@ int sg_node_flow_decide_batch(sg_node* nd, const sg_req* req, uint64_t n, sg_res
             const sg_req* sreq = nd->d_sub_req + base;
             sg_result* sout = nd->d_sub_out + base;
             if (dev != nd->devices[0]) {
-                NHIP(nd, hipMemcpyPeerAsync(nd->r_req[g], dev, sreq, nd->devices[0], sizeof(sg_req) * cnt, nd->streams[g]));
-                sreq = nd->r_req[g];
-                sout = nd->r_out[g];
+                NHIP(nd, hipMemcpyPeerAsync(nd->sh[g].r_req, dev, sreq, nd->devices[0], sizeof(sg_req) * cnt, nd->sh[g].stream));
+                sreq = nd->sh[g].r_req;
+                sout = nd->sh[g].r_out;
             }
-            rc = enqueue_flow(h, sreq, cnt, sout, nd->streams[g], nd->h_err[g], false);
+            rc = enqueue_flow(h, sreq, cnt, sout, nd->sh[g].stream, nd->sh[g].h_err, false);
             if (rc) {
                 node_sync_shards(nd, g + 1);
                 return node_child(nd, h, rc);
             }
             if (dev != nd->devices[0])
                 NHIP(nd, hipMemcpyPeerAsync(nd->d_sub_out + base, nd->devices[0], sout, dev, sizeof(sg_result) * cnt,
-                                            nd->streams[g]));
+                                            nd->sh[g].stream));
         }
-        NHIP(nd, hipEventRecord(nd->done[g], nd->streams[g]));
+        NHIP(nd, hipEventRecord(nd->sh[g].done, nd->sh[g].stream));
     }
     // 4. back into caller order (the sub_req path; the records path wrote the results in place)
     NHIP(nd, hipSetDevice(nd->devices[0]));
     for (uint32_t g = 0; g < G; ++g)
-        if (nd->h_base[kMaxShards + 1 + g]) NHIP(nd, hipStreamWaitEvent(nd->s0, nd->done[g], 0));
+        if (nd->h_base[kMaxShards + 1 + g]) NHIP(nd, hipStreamWaitEvent(nd->s0, nd->sh[g].done, 0));
     if (!nd->rec_path) NHIP(nd, launch_route_gather(nd->d_sub_out, nd->d_sub_pos, nd->h_base[G], out, nd->s0));
     NHIP(nd, hipEventRecord(nd->routed, nd->s0));
     NHIP(nd, hipStreamWaitEvent(user, nd->routed, 0));
     NHIP(nd, hipStreamSynchronize(nd->s0));
     for (uint32_t g = 0; g < G; ++g) {
-        const int e = *nd->h_err[g];
+        const int e = *nd->sh[g].h_err;
         if (e) return node_child(nd, nd->shards[g], flow_status(nd->shards[g], e));
     }
     return SG_OK;
@@ -5700,15 +5142,9 @@ int sg_node_flow_decide_batch_host(sg_node* nd, const sg_req* req, uint64_t n, s
     if (n == 0) return SG_OK;
     if (!req || !out) return nfail(nd, SG_E_INVAL, "null buffer");
     if (n > nd->cfg.max_batch) return nfail(nd, SG_E_CAPACITY, "batch larger than max_batch");
-    NHIP(nd, hipSetDevice(nd->devices[0]));
-    if (!nd->d_req_h && (hipMalloc(&nd->d_req_h, sizeof(sg_req) * nd->cfg.max_batch) != hipSuccess ||
-                         hipMalloc(&nd->d_out_h, sizeof(sg_result) * nd->cfg.max_batch) != hipSuccess))
-        return nfail(nd, SG_E_NOMEM, "host-path buffers");
-    NHIP(nd, hipMemcpy(nd->d_req_h, req, sizeof(sg_req) * n, hipMemcpyHostToDevice));
-    const int rc = sg_node_flow_decide_batch(nd, nd->d_req_h, n, nd->d_out_h, nullptr);
-    if (rc) return rc;
-    NHIP(nd, hipMemcpy(out, nd->d_out_h, sizeof(sg_result) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    return host_batch(nd, nd->devices[0], req, n, out, [&](sg_req* d_req, sg_result* d_out) {
+        return sg_node_flow_decide_batch(nd, d_req, n, d_out, nullptr);
+    });
 }
 
 int sg_node_flow_enqueue(sg_node* nd, const sg_req* req, uint64_t n, sg_result* out, uint64_t* ticket) {
@@ -5738,13 +5174,13 @@ int sg_node_flow_enqueue(sg_node* nd, const sg_req* req, uint64_t n, sg_result* 
     const int x = (int)(nd->pseq & 1);
     sg_node::PipeSlot& sl = nd->pipe[x];
     if (!sl.done) {
-        if (hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&nd->fdone[x], hipEventDisableTiming) != hipSuccess ||
-            hipHostMalloc(&sl.h_err, sizeof(int) * kMaxShards) != hipSuccess ||
-            hipHostMalloc(&sl.h_base, sizeof(uint32_t) * (2 * kMaxShards + 1)) != hipSuccess)
+        if (hipEventCreateWithFlags(sl.done.put(), hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(nd->fdone[x].put(), hipEventDisableTiming) != hipSuccess ||
+            !sl.h_err.alloc_bytes(sizeof(int) * kMaxShards) ||
+            !sl.h_base.alloc_bytes(sizeof(uint32_t) * (2 * kMaxShards + 1)))
             return nfail(nd, SG_E_NOMEM, "node pipeline slot");
     }
-    if (x == 1 && !nd->d_sub_rec2 && hipMalloc(&nd->d_sub_rec2, sizeof(uint64_t) * (nd->cfg.max_batch + kRecW)) != hipSuccess)
+    if (x == 1 && !nd->d_sub_rec2 && !nd->d_sub_rec2.alloc_bytes(sizeof(uint64_t) * (nd->cfg.max_batch + kRecW)))
         return nfail(nd, SG_E_NOMEM, "shard record slices");
     if (sl.ticket) {  // the batch two back used this workspace: complete it (its status waits in `finished`)
         const hipError_t e = hipEventSynchronize(sl.done);
@@ -5753,8 +5189,7 @@ int sg_node_flow_enqueue(sg_node* nd, const sg_req* req, uint64_t n, sg_result* 
     }
     // 1. the front on its pipeline stream: validation, the namespace limiter in caller order, the time check against
     // the previous node batch (the front's own last timestamp, in stream order), the period tables, the routing
-    sg_handle::FlowWs w = f->pws;
-    if (x == 0) main_ws(f, w);
+    sg_handle::FlowWs& w = f->ws[x];
     BatchArgs a = flow_args(f, w, req, n, out);
     const bool direct = G == 1 && nd->shards[0]->K == f->K && nd->shards[0]->kbits == f->kbits;
     if (!direct) a.hist0 = nullptr;
@@ -5825,8 +5260,7 @@ int sg_node_flow_enqueue(sg_node* nd, const sg_req* req, uint64_t n, sg_result* 
             src[g] = SG_E_DEVICE;
             return;
         }
-        sg_handle::FlowWs sw = h->pws;
-        if (x == 0) main_ws(h, sw);
+        sg_handle::FlowWs& sw = h->ws[x];
         BatchArgs b = flow_args(h, sw, req, cnt, out);
         b.rec = direct ? a.rec : sub_rec + base;
         b.rec_sorted = direct ? sw.rec_sorted : sw.rec;
@@ -5919,8 +5353,8 @@ int sg_node_snapshot_metrics(sg_node* nd, int64_t now_ms, double* out, uint64_t 
     const uint32_t G = (uint32_t)nd->shards.size();
     NHIP(nd, hipSetDevice(nd->devices[0]));
     if (nd->node_key_stale || nd->d_node_key.size() != G) {
-        for (uint32_t* p : nd->d_node_key) dfree(p);
-        nd->d_node_key.assign(G, nullptr);
+        nd->d_node_key.clear();
+        nd->d_node_key.resize(G);
         std::vector<std::vector<uint32_t>> keys(G);
         for (uint64_t k = 0; k < K; ++k) {
             auto& v = keys[nd->shard_of[k]];
@@ -5929,7 +5363,7 @@ int sg_node_snapshot_metrics(sg_node* nd, int64_t now_ms, double* out, uint64_t 
         }
         for (uint32_t g = 0; g < G; ++g) {
             if (keys[g].empty()) continue;
-            if (hipMalloc(&nd->d_node_key[g], sizeof(uint32_t) * keys[g].size()) != hipSuccess)
+            if (!nd->d_node_key[g].alloc_bytes(sizeof(uint32_t) * keys[g].size()))
                 return nfail(nd, SG_E_NOMEM, "node snapshot keys");
             NHIP(nd, hipMemcpy(nd->d_node_key[g], keys[g].data(), sizeof(uint32_t) * keys[g].size(), hipMemcpyHostToDevice));
         }
@@ -5938,11 +5372,7 @@ int sg_node_snapshot_metrics(sg_node* nd, int64_t now_ms, double* out, uint64_t 
     uint64_t part_max = 0;
     for (sg_handle* h : nd->shards) part_max = std::max<uint64_t>(part_max, h->K);
     const uint64_t need = 2 * K + 2 * part_max;  // the node's rows, then one shard part staged on the front
-    if (need > nd->snap_cap) {
-        dfree(nd->d_snap);
-        if (hipMalloc(&nd->d_snap, sizeof(double) * need) != hipSuccess) return nfail(nd, SG_E_NOMEM, "node snapshot");
-        nd->snap_cap = need;
-    }
+    if (!nd->d_snap.reserve(need)) return nfail(nd, SG_E_NOMEM, "node snapshot");
     double* stage = nd->d_snap + 2 * K;
     for (uint32_t g = 0; g < G; ++g) {
         sg_handle* h = nd->shards[g];
@@ -5951,12 +5381,12 @@ int sg_node_snapshot_metrics(sg_node* nd, int64_t now_ms, double* out, uint64_t 
         double* part = stage;
         if (dev != nd->devices[0]) {  // computed on its device, then copied over xGMI
             NHIP(nd, hipSetDevice(dev));
-            if (!nd->r_snap[g] && hipMalloc(&nd->r_snap[g], sizeof(double) * 2 * part_max) != hipSuccess)
-                return nfail(nd, SG_E_NOMEM, "node snapshot part");
-            part = nd->r_snap[g];
+            // regrown with the rules: a reload may give this shard more of them than the first snapshot saw
+            if (!nd->sh[g].r_snap.reserve(2 * part_max)) return nfail(nd, SG_E_NOMEM, "node snapshot part");
+            part = nd->sh[g].r_snap;
         }
-        NHIP(nd, launch_snapshot(h->d_rules, h->d_ring, h->d_occ, h->K, h->stride, now_ms, part, nd->streams[g]));
-        NHIP(nd, hipStreamSynchronize(nd->streams[g]));
+        NHIP(nd, launch_snapshot(h->d_rules, h->d_ring, h->d_occ, h->K, h->stride, now_ms, part, nd->sh[g].stream));
+        NHIP(nd, hipStreamSynchronize(nd->sh[g].stream));
         NHIP(nd, hipSetDevice(nd->devices[0]));
         if (dev != nd->devices[0])
             NHIP(nd, hipMemcpyPeerAsync(stage, nd->devices[0], part, dev, sizeof(double) * 2 * h->K, nd->s0));
@@ -6000,9 +5430,9 @@ int sg_node_cparam_load_rules(sg_node* nd, const sg_cparam_rule* rules, uint32_t
         if (rc) return node_child(nd, h, rc);
     }
     NHIP(nd, hipSetDevice(nd->devices[0]));
-    dfree(nd->d_cp_shard_of);
-    dfree(nd->d_cp_local_of);
-    if (n && (hipMalloc(&nd->d_cp_shard_of, n) != hipSuccess || hipMalloc(&nd->d_cp_local_of, sizeof(uint32_t) * n) != hipSuccess))
+    nd->d_cp_shard_of.reset();
+    nd->d_cp_local_of.reset();
+    if (n && (!nd->d_cp_shard_of.alloc_bytes(n) || !nd->d_cp_local_of.alloc_bytes(sizeof(uint32_t) * n)))
         return nfail(nd, SG_E_NOMEM, "param routing tables");
     if (n) {
         NHIP(nd, hipMemcpy(nd->d_cp_shard_of, so.data(), n, hipMemcpyHostToDevice));
@@ -6023,21 +5453,17 @@ int node_nreq_scratch(sg_node* nd, uint64_t n_values) {
     const uint64_t n = nd->cfg.max_batch;
     NHIP(nd, hipSetDevice(nd->devices[0]));
     if (!nd->d_nrec) {
-        if (hipMalloc(&nd->d_nrec, 8 * n) != hipSuccess || hipMalloc(&nd->d_nrec2, 8 * n) != hipSuccess ||
-            hipMalloc(&nd->d_nhist, sizeof(uint32_t) * radix_hist_words(n)) != hipSuccess ||
-            hipMalloc(&nd->d_nvals, sizeof(uint32_t) * n) != hipSuccess ||
-            hipMalloc(&nd->d_ncnt, sizeof(uint32_t) * 3 * kMaxShards) != hipSuccess ||
-            hipMalloc(&nd->d_ntsum, sizeof(uint32_t) * (nreq_tiles(n) + 1)) != hipSuccess ||
-            hipMalloc(&nd->d_nerr, sizeof(int)) != hipSuccess ||
-            hipMalloc(&nd->d_sub_nreq, std::max(sizeof(sg_cparam_req), sizeof(sg_conc_req)) * n) != hipSuccess ||
-            hipMalloc(&nd->d_sub_nout, std::max(sizeof(sg_result), sizeof(sg_conc_result)) * n) != hipSuccess)
+        if (!nd->d_nrec.alloc_bytes(8 * n) || !nd->d_nrec2.alloc_bytes(8 * n) ||
+            !nd->d_nhist.alloc_bytes(sizeof(uint32_t) * radix_hist_words(n)) ||
+            !nd->d_nvals.alloc_bytes(sizeof(uint32_t) * n) ||
+            !nd->d_ncnt.alloc_bytes(sizeof(uint32_t) * 3 * kMaxShards) ||
+            !nd->d_ntsum.alloc_bytes(sizeof(uint32_t) * (nreq_tiles(n) + 1)) ||
+            !nd->d_nerr.alloc_bytes(sizeof(int)) ||
+            !nd->d_sub_nreq.alloc_bytes(std::max(sizeof(sg_cparam_req), sizeof(sg_conc_req)) * n) ||
+            !nd->d_sub_nout.alloc_bytes(std::max(sizeof(sg_result), sizeof(sg_conc_result)) * n))
             return nfail(nd, SG_E_NOMEM, "node token routing scratch");
     }
-    if (n_values > nd->sub_vals_cap) {
-        dfree(nd->d_sub_vals);
-        if (hipMalloc(&nd->d_sub_vals, 8 * n_values) != hipSuccess) return nfail(nd, SG_E_NOMEM, "node param values");
-        nd->sub_vals_cap = n_values;
-    }
+    if (!nd->d_sub_vals.reserve(n_values)) return nfail(nd, SG_E_NOMEM, "node param values");
     return SG_OK;
 }
 
@@ -6097,14 +5523,10 @@ int node_slice_alloc(sg_node* nd, uint32_t g, uint64_t nv) {
     if (dev == nd->devices[0]) return SG_OK;
     NHIP(nd, hipSetDevice(dev));
     const uint64_t n = nd->cfg.max_batch;
-    if (!nd->r_nreq[g] && (hipMalloc(&nd->r_nreq[g], std::max(sizeof(sg_cparam_req), sizeof(sg_conc_req)) * n) != hipSuccess ||
-                           hipMalloc(&nd->r_nout[g], std::max(sizeof(sg_result), sizeof(sg_conc_result)) * n) != hipSuccess))
+    if (!nd->sh[g].r_nreq && (!nd->sh[g].r_nreq.alloc_bytes(std::max(sizeof(sg_cparam_req), sizeof(sg_conc_req)) * n) ||
+                           !nd->sh[g].r_nout.alloc_bytes(std::max(sizeof(sg_result), sizeof(sg_conc_result)) * n)))
         return nfail(nd, SG_E_NOMEM, "shard slice buffers");
-    if (nv > nd->r_vals_cap[g]) {
-        dfree(nd->r_vals[g]);
-        if (hipMalloc(&nd->r_vals[g], 8 * nv) != hipSuccess) return nfail(nd, SG_E_NOMEM, "shard values");
-        nd->r_vals_cap[g] = nv;
-    }
+    if (!nd->sh[g].r_vals.reserve(nv)) return nfail(nd, SG_E_NOMEM, "shard values");
     return SG_OK;
 }
 
@@ -6138,24 +5560,24 @@ int node_run_shards(sg_node* nd, const std::vector<uint64_t>& base, const std::v
         const uint64_t* vals = svals;
         void* out = sout;
         if (remote) {
-            if (e == hipSuccess) e = hipMemcpyPeer(nd->r_nreq[g], dev, sreq, nd->devices[0], req_b * cnt[g]);
-            if (e == hipSuccess && vcnt[g]) e = hipMemcpyPeer(nd->r_vals[g], dev, svals, nd->devices[0], 8 * vcnt[g]);
-            req = nd->r_nreq[g];
-            vals = nd->r_vals[g];
-            out = nd->r_nout[g];
+            if (e == hipSuccess) e = hipMemcpyPeer(nd->sh[g].r_nreq, dev, sreq, nd->devices[0], req_b * cnt[g]);
+            if (e == hipSuccess && vcnt[g]) e = hipMemcpyPeer(nd->sh[g].r_vals, dev, svals, nd->devices[0], 8 * vcnt[g]);
+            req = nd->sh[g].r_nreq;
+            vals = nd->sh[g].r_vals;
+            out = nd->sh[g].r_nout;
         }
         if (e != hipSuccess) {
             rc[g] = SG_E_DEVICE;
             msg[g] = hipGetErrorString(e);
             return;
         }
-        const int r = decide(h, req, vcnt[g] ? vals : nullptr, vcnt[g], cnt[g], out, nd->streams[g]);
+        const int r = decide(h, req, vcnt[g] ? vals : nullptr, vcnt[g], cnt[g], out, nd->sh[g].stream);
         if (r) {
             rc[g] = r;
             child[g] = 1;
             return;
         }
-        e = hipStreamSynchronize(nd->streams[g]);
+        e = hipStreamSynchronize(nd->sh[g].stream);
         if (e == hipSuccess && remote) e = hipMemcpyPeer(sout, nd->devices[0], out, dev, out_b * cnt[g]);
         if (e != hipSuccess) {
             rc[g] = SG_E_DEVICE;
@@ -6210,13 +5632,13 @@ int sg_node_cparam_decide_batch(sg_node* nd, const sg_cparam_req* req, uint64_t 
     q.K = (uint32_t)nd->cp_rules.size();
     q.shard_of = nd->d_cp_shard_of;
     q.local_of = nd->d_cp_local_of;
-    q.sub_cp = static_cast<sg_cparam_req*>(nd->d_sub_nreq);
+    q.sub_cp = reinterpret_cast<sg_cparam_req*>(nd->d_sub_nreq.get());
     q.last_ts = nd->cp_last_ts;
     NHIP(nd, hipStreamSynchronize((hipStream_t)stream));  // the caller's batch is in place (synchronous call)
     std::vector<uint64_t> base, cnt, vbase, vcnt;
     rc = node_nreq_route(nd, q, base, cnt, vbase, vcnt);
     if (rc) return rc;
-    sg_result* sub_out = static_cast<sg_result*>(nd->d_sub_nout);
+    sg_result* sub_out = reinterpret_cast<sg_result*>(nd->d_sub_nout.get());
     rc = node_run_shards(nd, base, cnt, vbase, vcnt, sizeof(sg_cparam_req), sizeof(sg_result), q.sub_cp, sub_out,
                          [](sg_handle* h, const void* r, const uint64_t* v, uint64_t nv, uint64_t c, void* o, hipStream_t st) {
                              return sg_cparam_decide_batch(h, static_cast<const sg_cparam_req*>(r), c, v, nv,
@@ -6240,22 +5662,12 @@ int sg_node_cparam_decide_batch_host(sg_node* nd, const sg_cparam_req* req, uint
     if (n > nd->cfg.max_batch) return nfail(nd, SG_E_CAPACITY, "batch larger than max_batch");
     NHIP(nd, hipSetDevice(nd->devices[0]));
     node_drain(nd);
-    if (!nd->d_nreq_h && (hipMalloc(&nd->d_nreq_h, sizeof(sg_conc_req) * nd->cfg.max_batch) != hipSuccess ||
-                          hipMalloc(&nd->d_nout_h, sizeof(sg_conc_result) * nd->cfg.max_batch) != hipSuccess))
-        return nfail(nd, SG_E_NOMEM, "node host-path buffers");
-    if (n_values > nd->nvals_h_cap) {
-        dfree(nd->d_nvals_h);
-        if (hipMalloc(&nd->d_nvals_h, 8 * n_values) != hipSuccess) return nfail(nd, SG_E_NOMEM, "node host-path values");
-        nd->nvals_h_cap = n_values;
-    }
-    NHIP(nd, hipMemcpy(nd->d_nreq_h, req, sizeof(sg_cparam_req) * n, hipMemcpyHostToDevice));
-    if (n_values) NHIP(nd, hipMemcpy(nd->d_nvals_h, values, 8 * n_values, hipMemcpyHostToDevice));
-    const int rc = sg_node_cparam_decide_batch(nd, static_cast<const sg_cparam_req*>(nd->d_nreq_h), n,
-                                               n_values ? nd->d_nvals_h : nullptr, n_values,
-                                               static_cast<sg_result*>(nd->d_nout_h), nullptr);
-    if (rc) return rc;
-    NHIP(nd, hipMemcpy(out, nd->d_nout_h, sizeof(sg_result) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    uint64_t* d_vals = nullptr;
+    if (!nd->stage.get(2, n_values, d_vals)) return nfail(nd, SG_E_NOMEM, "node host-path values");
+    if (n_values) NHIP(nd, hipMemcpy(d_vals, values, 8 * n_values, hipMemcpyHostToDevice));
+    return host_batch(nd, nd->devices[0], req, n, out, [&](sg_cparam_req* d_req, sg_result* d_out) {
+        return sg_node_cparam_decide_batch(nd, d_req, n, n_values ? d_vals : nullptr, n_values, d_out, nullptr);
+    });
 }
 
 int sg_node_cparam_read_sum(sg_node* nd, uint32_t rule, uint64_t value, int64_t now_ms, int64_t* sum) {
@@ -6310,13 +5722,13 @@ int sg_node_conc_decide_batch(sg_node* nd, const sg_conc_req* req, uint64_t n, s
     q.K = (uint32_t)nd->shard_of.size();
     q.shard_of = nd->d_shard_of;
     q.local_of = nd->d_local_of;
-    q.sub_cc = static_cast<sg_conc_req*>(nd->d_sub_nreq);
+    q.sub_cc = reinterpret_cast<sg_conc_req*>(nd->d_sub_nreq.get());
     q.last_ts = nd->cc_last_ts;
     NHIP(nd, hipStreamSynchronize((hipStream_t)stream));  // the caller's batch is in place (synchronous call)
     std::vector<uint64_t> base, cnt, vbase, vcnt;
     rc = node_nreq_route(nd, q, base, cnt, vbase, vcnt);
     if (rc) return rc;
-    sg_conc_result* sub_out = static_cast<sg_conc_result*>(nd->d_sub_nout);
+    sg_conc_result* sub_out = reinterpret_cast<sg_conc_result*>(nd->d_sub_nout.get());
     rc = node_run_shards(nd, base, cnt, vbase, vcnt, sizeof(sg_conc_req), sizeof(sg_conc_result), q.sub_cc, sub_out,
                          [](sg_handle* h, const void* r, const uint64_t*, uint64_t, uint64_t c, void* o, hipStream_t st) {
                              return sg_conc_decide_batch(h, static_cast<const sg_conc_req*>(r), c,
@@ -6340,15 +5752,9 @@ int sg_node_conc_decide_batch_host(sg_node* nd, const sg_conc_req* req, uint64_t
     if (n > nd->cfg.max_batch) return nfail(nd, SG_E_CAPACITY, "batch larger than max_batch");
     NHIP(nd, hipSetDevice(nd->devices[0]));
     node_drain(nd);
-    if (!nd->d_nreq_h && (hipMalloc(&nd->d_nreq_h, sizeof(sg_conc_req) * nd->cfg.max_batch) != hipSuccess ||
-                          hipMalloc(&nd->d_nout_h, sizeof(sg_conc_result) * nd->cfg.max_batch) != hipSuccess))
-        return nfail(nd, SG_E_NOMEM, "node host-path buffers");
-    NHIP(nd, hipMemcpy(nd->d_nreq_h, req, sizeof(sg_conc_req) * n, hipMemcpyHostToDevice));
-    const int rc = sg_node_conc_decide_batch(nd, static_cast<const sg_conc_req*>(nd->d_nreq_h), n,
-                                             static_cast<sg_conc_result*>(nd->d_nout_h), nullptr);
-    if (rc) return rc;
-    NHIP(nd, hipMemcpy(out, nd->d_nout_h, sizeof(sg_conc_result) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    return host_batch(nd, nd->devices[0], req, n, out, [&](sg_conc_req* d_req, sg_conc_result* d_out) {
+        return sg_node_conc_decide_batch(nd, d_req, n, d_out, nullptr);
+    });
 }
 
 int sg_node_conc_set_rule_timeouts(sg_node* nd, const int64_t* client_offline_ms, const int64_t* resource_timeout_ms,
@@ -6432,9 +5838,9 @@ int node_local_owners(sg_node* nd, std::vector<uint32_t>& own) {
 
 int node_local_set_owners(sg_node* nd, const std::vector<uint32_t>& own) {
     NHIP(nd, hipSetDevice(nd->devices[0]));
-    dfree(nd->d_l_owner);
+    nd->d_l_owner.reset();
     const std::vector<uint8_t> o8(own.begin(), own.end());
-    if (hipMalloc(&nd->d_l_owner, o8.size() ? o8.size() : 1) != hipSuccess) return nfail(nd, SG_E_NOMEM, "owner table");
+    if (!nd->d_l_owner.alloc_bytes(o8.size() ? o8.size() : 1)) return nfail(nd, SG_E_NOMEM, "owner table");
     if (!o8.empty()) NHIP(nd, hipMemcpy(nd->d_l_owner, o8.data(), o8.size(), hipMemcpyHostToDevice));
     nd->l_owner = own;
     return SG_OK;
@@ -6466,8 +5872,8 @@ int node_merge_rows(sg_node* nd, const sg_metric_node* d_rows, uint64_t n, sg_me
     NHIP(nd, launch_merge_rows(m, stream));
     unsigned long long total = 0;
     int err = 0;
-    NHIP(nd, hipMemcpyAsync(&total, &nd->d_mslots->n_out, sizeof(total), hipMemcpyDeviceToHost, stream));
-    NHIP(nd, hipMemcpyAsync(&err, &nd->d_mslots->err, sizeof(err), hipMemcpyDeviceToHost, stream));
+    NHIP(nd, hipMemcpyAsync(&total, &nd->d_mslots.get()->n_out, sizeof(total), hipMemcpyDeviceToHost, stream));
+    NHIP(nd, hipMemcpyAsync(&err, &nd->d_mslots.get()->err, sizeof(err), hipMemcpyDeviceToHost, stream));
     NHIP(nd, hipStreamSynchronize(stream));
     if (err & kMergeBad)
         return nfail(nd, SG_E_INVAL, "metric rows outside the merge's contract: timestamps multiples of 1000 within one "
@@ -6490,9 +5896,9 @@ int node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, sg_me
     for (uint32_t g = 0; g < G; ++g) {
         sg_handle* h = nd->shards[g];
         NHIP(nd, hipSetDevice(nd->devices[g]));
-        if (!nd->r_mcnt[g] && hipMalloc(&nd->r_mcnt[g], sizeof(uint64_t)) != hipSuccess)
+        if (!nd->sh[g].r_mcnt && !nd->sh[g].r_mcnt.alloc_bytes(sizeof(uint64_t)))
             return nfail(nd, SG_E_NOMEM, "metric row counter");
-        const int rc = sg_local_metrics_raw_enqueue(h, now_ms, nullptr, 0, nd->r_mcnt[g], nd->streams[g]);
+        const int rc = sg_local_metrics_raw_enqueue(h, now_ms, nullptr, 0, nd->sh[g].r_mcnt, nd->sh[g].stream);
         if (rc) {
             node_sync_shards(nd, g);
             return node_child(nd, h, rc);
@@ -6502,26 +5908,16 @@ int node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, sg_me
     uint64_t sum = 0;
     for (uint32_t g = 0; g < G; ++g) {
         NHIP(nd, hipSetDevice(nd->devices[g]));
-        NHIP(nd, hipMemcpyAsync(&cnt[g], nd->r_mcnt[g], sizeof(uint64_t), hipMemcpyDeviceToHost, nd->streams[g]));
-        NHIP(nd, hipStreamSynchronize(nd->streams[g]));
+        NHIP(nd, hipMemcpyAsync(&cnt[g], nd->sh[g].r_mcnt, sizeof(uint64_t), hipMemcpyDeviceToHost, nd->sh[g].stream));
+        NHIP(nd, hipStreamSynchronize(nd->sh[g].stream));
         sum += cnt[g];
     }
     NHIP(nd, hipSetDevice(nd->devices[0]));
     *n_rows = sum;  // a sufficient capacity: the merged table can only be shorter (ENTRY_NODE rows of a second collapse)
     if (sum > cap) return nfail(nd, SG_E_CAPACITY, "metric row buffer too small (*n_rows rows suffice)");
     if (sum == 0) return SG_OK;
-    if (sum > nd->mrows_cap) {
-        dfree(nd->d_mrows);
-        nd->mrows_cap = 0;
-        if (hipMalloc(&nd->d_mrows, sizeof(sg_metric_node) * sum) != hipSuccess) return nfail(nd, SG_E_NOMEM, "node metric rows");
-        nd->mrows_cap = sum;
-    }
-    if (h_out && sum > nd->mout_cap) {
-        dfree(nd->d_mout);
-        nd->mout_cap = 0;
-        if (hipMalloc(&nd->d_mout, sizeof(sg_metric_node) * sum) != hipSuccess) return nfail(nd, SG_E_NOMEM, "node metric table");
-        nd->mout_cap = sum;
-    }
+    if (!nd->d_mrows.reserve(sum)) return nfail(nd, SG_E_NOMEM, "node metric rows");
+    if (h_out && !nd->d_mout.reserve(sum)) return nfail(nd, SG_E_NOMEM, "node metric table");
     // 2. every shard's rows (its listener state advances), a remote shard's through a buffer on its device
     std::vector<uint64_t> off(G, 0);
     uint64_t at = 0;
@@ -6532,17 +5928,12 @@ int node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, sg_me
         sg_handle* h = nd->shards[g];
         const bool remote = nd->devices[g] != nd->devices[0];
         NHIP(nd, hipSetDevice(nd->devices[g]));
-        if (remote && cnt[g] > nd->r_mrows_cap[g]) {
-            dfree(nd->r_mrows[g]);
-            nd->r_mrows_cap[g] = 0;
-            if (hipMalloc(&nd->r_mrows[g], sizeof(sg_metric_node) * cnt[g]) != hipSuccess) {
-                node_sync_shards(nd, g);
-                return nfail(nd, SG_E_NOMEM, "shard metric rows");
-            }
-            nd->r_mrows_cap[g] = cnt[g];
+        if (remote && !nd->sh[g].r_mrows.reserve(cnt[g])) {
+            node_sync_shards(nd, g);
+            return nfail(nd, SG_E_NOMEM, "shard metric rows");
         }
-        sg_metric_node* dst = remote ? nd->r_mrows[g] : nd->d_mrows + off[g];
-        const int rc = sg_local_metrics_raw_enqueue(h, now_ms, dst, cnt[g], nd->r_mcnt[g], nd->streams[g]);
+        sg_metric_node* dst = remote ? nd->sh[g].r_mrows : nd->d_mrows + off[g];
+        const int rc = sg_local_metrics_raw_enqueue(h, now_ms, dst, cnt[g], nd->sh[g].r_mcnt, nd->sh[g].stream);
         if (rc) {
             node_sync_shards(nd, g);
             return node_child(nd, h, rc);
@@ -6551,9 +5942,9 @@ int node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, sg_me
     for (uint32_t g = 0; g < G; ++g) {
         if (!cnt[g]) continue;
         NHIP(nd, hipSetDevice(nd->devices[g]));
-        NHIP(nd, hipStreamSynchronize(nd->streams[g]));
+        NHIP(nd, hipStreamSynchronize(nd->sh[g].stream));
         if (nd->devices[g] != nd->devices[0])
-            NHIP(nd, hipMemcpyPeer(nd->d_mrows + off[g], nd->devices[0], nd->r_mrows[g], nd->devices[g],
+            NHIP(nd, hipMemcpyPeer(nd->d_mrows + off[g], nd->devices[0], nd->sh[g].r_mrows, nd->devices[g],
                                    sizeof(sg_metric_node) * cnt[g]));
     }
     // 3. the merge
@@ -6598,18 +5989,18 @@ int sg_node_local_load_rules(sg_node* nd, const sg_local_config* cfg, const sg_l
     // the merge's scratch: (second, resource) bitmap and its prefix counts, the slots' sums
     const uint32_t W = (n + 63) / 64;
     if (W > nd->m_words || !nd->d_mbits) {
-        dfree(nd->d_mbits);
-        dfree(nd->d_mpre);
+        nd->d_mbits.reset();
+        nd->d_mpre.reset();
         nd->m_words = 0;
         const size_t words = (size_t)kMinuteS * (W ? W : 1);
-        if (hipMalloc(&nd->d_mbits, sizeof(unsigned long long) * words) != hipSuccess ||
-            hipMalloc(&nd->d_mpre, sizeof(uint32_t) * words) != hipSuccess)
+        if (!nd->d_mbits.alloc_bytes(sizeof(unsigned long long) * words) ||
+            !nd->d_mpre.alloc_bytes(sizeof(uint32_t) * words))
             return nfail(nd, SG_E_NOMEM, "metric merge scratch");
     }
     nd->m_words = W;
-    if (!nd->d_mslots && hipMalloc(&nd->d_mslots, sizeof(MergeSlots)) != hipSuccess)
+    if (!nd->d_mslots && !nd->d_mslots.alloc_bytes(sizeof(MergeSlots)))
         return nfail(nd, SG_E_NOMEM, "metric merge scratch");
-    if (!nd->d_lerr && hipMalloc(&nd->d_lerr, sizeof(int)) != hipSuccess) return nfail(nd, SG_E_NOMEM, "error word");
+    if (!nd->d_lerr && !nd->d_lerr.alloc_bytes(sizeof(int))) return nfail(nd, SG_E_NOMEM, "error word");
     nd->l_loaded = true;
     return SG_OK;
 }
@@ -6679,8 +6070,8 @@ int sg_node_local_decide_batch(sg_node* nd, const sg_local_event* ev, uint64_t n
     node_drain(nd);
     NHIP(nd, hipSetDevice(nd->devices[0]));
     const uint32_t G = (uint32_t)nd->shards.size();
-    if (!nd->d_lsub_ev && (hipMalloc(&nd->d_lsub_ev, sizeof(sg_local_event) * nd->cfg.max_batch) != hipSuccess ||
-                           hipMalloc(&nd->d_lsub_out, sizeof(sg_local_result) * nd->cfg.max_batch) != hipSuccess))
+    if (!nd->d_lsub_ev && (!nd->d_lsub_ev.alloc_bytes(sizeof(sg_local_event) * nd->cfg.max_batch) ||
+                           !nd->d_lsub_out.alloc_bytes(sizeof(sg_local_result) * nd->cfg.max_batch)))
         return nfail(nd, SG_E_NOMEM, "node local slices");
     NHIP(nd, hipStreamSynchronize((hipStream_t)stream));  // the caller's batch is in place (synchronous call)
     // 1. the batch validated as a whole and split by owner: a refused batch reaches no shard
@@ -6742,14 +6133,9 @@ int sg_node_local_decide_batch_host(sg_node* nd, const sg_local_event* ev, uint6
     if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
     NHIP(nd, hipSetDevice(nd->devices[0]));
     node_drain(nd);
-    if (!nd->d_lev_h && (hipMalloc(&nd->d_lev_h, sizeof(sg_local_event) * nd->cfg.max_batch) != hipSuccess ||
-                         hipMalloc(&nd->d_lout_h, sizeof(sg_local_result) * nd->cfg.max_batch) != hipSuccess))
-        return nfail(nd, SG_E_NOMEM, "node host-path buffers");
-    NHIP(nd, hipMemcpy(nd->d_lev_h, ev, sizeof(sg_local_event) * n, hipMemcpyHostToDevice));
-    const int rc = sg_node_local_decide_batch(nd, nd->d_lev_h, n, nd->d_lout_h, nullptr);
-    if (rc) return rc;
-    NHIP(nd, hipMemcpy(out, nd->d_lout_h, sizeof(sg_local_result) * n, hipMemcpyDeviceToHost));
-    return SG_OK;
+    return host_batch(nd, nd->devices[0], ev, n, out, [&](sg_local_event* d_ev, sg_local_result* d_out) {
+        return sg_node_local_decide_batch(nd, d_ev, n, d_out, nullptr);
+    });
 }
 
 int sg_node_local_read_state(sg_node* nd, uint32_t res, int64_t* second, int64_t* borrow, int64_t* minute, int64_t* head) {
