@@ -1050,7 +1050,8 @@ int sg_rls_should_rate_limit(sg_handle* h, const sg_rls_request* req, uint32_t n
                              uint64_t n_desc, int32_t* overall, sg_rls_status* status);
 
 /* Testing aid: copy an internal buffer of the last batch to host memory.
- * what: 0 = records (request order, u64), 1 = records sorted by flowId, 2 = window-period table
+ * what: 0 = records (request order, u64; on the binned flow path with compact front records, u32
+ * {bin digit | key in bin | acquire code} in the buffer's first half), 1 = records sorted by flowId, 2 = window-period table
  * (u32 [8][65536]), 3 = first period per window length (i64[8]), 4 = periods per window length (u32[8]). */
 int sg_debug_copy(sg_handle* h, int what, void* dst, uint64_t bytes);
 

@@ -95,6 +95,7 @@ struct sg_handle {
     };
     FlowWs ws[2];
     uint64_t* last_sorted = nullptr;  // whichever of ws[0].rec / ws[0].rec_sorted holds the last sort result
+    uint64_t last_rec4_n = 0;         // > 0: that batch (of this many requests) left 4-byte sorted records (BatchArgs::rec4)
     DevBuf<int64_t> d_last_ts;        // {last_ts, front_ts}
     int64_t* d_front_ts = nullptr;    // d_last_ts + 1. Pipelined limiter batches: last timestamp of the latest accepted front half
     DevBuf<FidSlot> d_fid;            // flowId → rule index (wire codec), 2^k slots
@@ -334,10 +335,11 @@ struct sg_handle {
     bool d2h_kernel = false;          // sg_flow_submit: results to pinned host buffers by k_copy_out (env SG_D2H=1; the
                                       // copy engine measured faster: 2.64 vs 2.45 G decisions/s end to end)
     int d2h_blocks = 64;              // its workgroups (env SG_D2H_BLOCKS)
-    int front_eighths = 4;            // CU partition of the pipeline streams (pipe_setup; round 6: the binned front half
+    int front_sixteenths = 8;         // CU partition of the pipeline streams (pipe_setup; round 6: the binned front half
                                       // (k_bin_sort) takes 4/8, -2.5 % against 3/8; the two-pass sort measures the same at 3 or 4)
-    bool cu_blocked = false;          // env SG_CU_BLOCKED=1 (tuning): the front half gets CUs i with i / (cus / 8) < k
-                                      // (contiguous eighths); both read once in sg_create
+    bool cu_blocked = false;          // env SG_CU_BLOCKED=1 (tuning): the front half gets CUs i with i * 16 / cus < k
+                                      // (contiguous sixteenths); both read once in sg_create
+    bool rec4 = true;                 // env SG_REC4=0: 8-byte front records on the binned path too (BatchArgs::rec4)
     int walk_cus = 0;                 // CUs of the walkers' streams when partitioned (0 = all)
     struct DevTicket {                // sg_flow_enqueue batches in flight
         uint64_t ticket = 0;
@@ -598,7 +600,9 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
     if (const char* d = std::getenv("SG_SEG_MARK")) h->seg_mark_pass = std::atoi(d) != 0;
     if (const char* d = std::getenv("SG_LIM_PIPE")) h->lim_pipe = std::atoi(d) != 0;
     if (const char* d = std::getenv("SG_BIN")) h->bin_mode = std::atoi(d);
-    if (const char* d = std::getenv("SG_FRONT_EIGHTHS")) h->front_eighths = std::atoi(d);
+    if (const char* d = std::getenv("SG_FRONT_EIGHTHS")) h->front_sixteenths = 2 * std::atoi(d);
+    if (const char* d = std::getenv("SG_FRONT_SIXTEENTHS")) h->front_sixteenths = std::atoi(d);
+    if (const char* d = std::getenv("SG_REC4")) h->rec4 = std::atoi(d) != 0;
     if (const char* d = std::getenv("SG_CU_BLOCKED")) h->cu_blocked = std::atoi(d) == 1;
     if (const char* d = std::getenv("SG_PREP_TILES")) h->prep_tiles = std::max(1, std::min(64, std::atoi(d)));
     if (const char* d = std::getenv("SG_D2H_BLOCKS")) h->d2h_blocks = std::max(1, std::atoi(d));
@@ -1304,17 +1308,18 @@ int pipe_setup(sg_handle* h) {
     auto& w = h->ws[1];
     if (!w.rec) {
         if (!flow_ws_alloc(h, w)) return fail(h, SG_E_NOMEM, "pipeline workspace");
-        // CU partition between the halves (env SG_FRONT_EIGHTHS = k: the front half gets CUs i with i % 8 < k,
-        // the walkers the rest; 0 = no masks, both halves on every CU)
+        // CU partition between the halves (env SG_FRONT_SIXTEENTHS = k: the front half gets the CUs whose sixteenth
+        // 2 * (i % 8) + (i / 8) % 2 is below k, the walkers the rest; 0 = no masks, both halves on every CU). An even
+        // k is SG_FRONT_EIGHTHS = k / 2, the same CUs as i % 8 < k / 2; an odd k adds every other CU of the next eighth.
         int cus = 0;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-        const int k8 = h->front_eighths;
+        const int k16 = h->front_sixteenths;
         const bool blocked = h->cu_blocked;
-        if (k8 > 0 && k8 < 8 && cus >= 8) {
+        if (k16 > 0 && k16 < 16 && cus >= 8) {
             std::vector<uint32_t> fm((cus + 31) / 32, 0u), bm((cus + 31) / 32, 0u);
             int nb = 0;
             for (int i = 0; i < cus; ++i) {
-                if ((blocked ? i / (cus / 8) : i % 8) < k8) fm[i / 32] |= 1u << (i % 32);
+                if ((blocked ? i * 16 / cus : 2 * (i % 8) + (i / 8) % 2) < k16) fm[i / 32] |= 1u << (i % 32);
                 else {
                     bm[i / 32] |= 1u << (i % 32);
                     ++nb;
@@ -1472,6 +1477,7 @@ bool bin_setup(sg_handle* h, sg_handle::FlowWs& w, BatchArgs& a, hipStream_t str
     a.bin_buf = w.bin_buf;
     a.hist0_bits = kBinDigit;
     a.hist0_shift = a.bin_dshift;
+    a.rec4 = (h->rec4 && h->abits == kRec4Abits && h->ibits <= 24) ? 1 : 0;
     return true;
 }
 
@@ -1566,6 +1572,7 @@ int enqueue_flow(sg_handle* h, const sg_req* req, uint64_t n, sg_result* out, hi
     rc = flow_front(h, a, w.hist, stream, stats);
     if (rc) return rc;
     h->last_sorted = a.rec_sorted;
+    h->last_rec4_n = a.rec4 ? n : 0;
     return flow_back(h, a, stream, h->aux, h->fork, h->join, err_dst, stats);
 }
 
@@ -1632,7 +1639,10 @@ int enqueue_flow_pipelined(sg_handle* h, const sg_req* req, uint64_t n, sg_resul
     rc = flow_front(h, a, w.hist, h->s_front, false);
     h->lim_x_armed = false;
     if (rc) return rc;
-    if (x == 0) h->last_sorted = a.rec_sorted;
+    if (x == 0) {
+        h->last_sorted = a.rec_sorted;
+        h->last_rec4_n = a.rec4 ? n : 0;
+    }
     HIP_TRY(h, hipEventRecord(h->front_done[x], h->s_front));
     HIP_TRY(h, hipStreamWaitEvent(h->s_back, h->front_done[x], 0));
     a.walk_cus = h->walk_cus;
@@ -2187,6 +2197,7 @@ int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int
     HIP_TRY(h, launch_param_batch(p, sg, h->ws[0].rec, h->ws[0].rec_sorted, h->ws[0].hist, p.gshift, p.gshift + gbits, &sorted, stream,
                                   h->aux, h->fork, h->join));
     h->last_sorted = sorted;
+    h->last_rec4_n = 0;
     HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     const int err = *h->h_err & ~kErrNonPositive;
@@ -2328,6 +2339,7 @@ int sg_pace_decide_batch(sg_handle* h, const sg_pace_req* req, uint64_t n, int32
     HIP_TRY(h, launch_pace_batch(p, h->ws[0].rec, h->ws[0].rec_sorted, h->ws[0].hist, p.gshift, p.gshift + gbits, &sorted, stream,
                                  h->aux, h->fork, h->join));
     h->last_sorted = sorted;
+    h->last_rec4_n = 0;
     HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     if (*h->h_err & kErrTime)
@@ -3532,6 +3544,7 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
     rc = local_sort(h, L, sgm, b.rec_sorted, stream);
     if (rc) return rc;
     h->last_sorted = L.rec_sorted;
+    h->last_rec4_n = 0;
     if (h->stats_on) HIP_TRY(h, hipEventRecord(h->ev[2], stream));
     HIP_TRY(h, launch_local_walk(L, sgm, h->l_has_cx || h->l_has_cx_ps || track, h->aux, stream, h->fork, h->join));
     if (h->stats_on) HIP_TRY(h, hipEventRecord(h->ev[3], stream));
@@ -4541,6 +4554,18 @@ int sg_debug_copy(sg_handle* h, int what, void* dst, uint64_t bytes) {
     }
     if (bytes > cap) return SG_E_INVAL;
     HIP_TRY(h, hipSetDevice(h->device));
+    if (what == 1 && h->last_rec4_n > 0 && src == h->ws[0].rec_sorted && h->ws[0].bin_buf) {
+        // the compact layout keeps 4-byte sorted records: the 8-byte view is rebuilt from them and the batch's segment
+        // lists into the regular bins' buffer (free once the batch is done)
+        drain_async(h);
+        HIP_TRY(h, hipDeviceSynchronize());
+        BatchArgs a = flow_args(h, h->ws[0], nullptr, h->last_rec4_n, nullptr);
+        a.rec4 = 1;
+        HIP_TRY(h, launch_rec4_expand(a, h->ws[0].bin_buf, nullptr));
+        HIP_TRY(h, hipDeviceSynchronize());
+        src = h->ws[0].bin_buf;
+        if (bytes > h->last_rec4_n * 8) return SG_E_INVAL;
+    }
     HIP_TRY(h, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return SG_OK;
 }

@@ -159,6 +159,14 @@ struct BatchArgs {
     uint32_t* hot_key;     // [kBinHot] flowId of each hot slot
     uint64_t* bin_buf;     // the regular bins after the scatter (k_bin_sort's input, rec_sorted's index space)
     const uint32_t* bin_tot;  // [1 << kBinDigit] digit totals (k_chunkscan)
+    // Compact records (rec4 = 1, needs bin_on, abits == 8 and ibits <= 24; env SG_REC4=0: off). Between k_prep and
+    // the scatter a record's position is its request index, so k_prep<true> writes 4 bytes per request at
+    // reinterpret_cast<uint32_t*>(rec)[i] — {bin digit : kBinDigit | key - (bin << bin_bsh) : kBinMaxBsh | acquire
+    // code : 7 | prio : 1} (kRec4*); the bin scatter (k_bin_scatter4) widens the regular bins' records to 8 bytes in
+    // bin_buf for k_bin_sort; and rec_sorted holds, at the same element positions as in the 8-byte layout, 4-byte
+    // compact words {request index : 24 | acquire code : 7 | prio : 1} (reinterpret_cast<uint32_t*>(rec_sorted)):
+    // no walker needs a sorted record's key, the segment lists carry it. Rejected requests have no sorted copy.
+    int rec4;
 };
 
 constexpr int kBinDigit = 10;                        // bin digit width: one radix_pass<10>
@@ -166,6 +174,13 @@ constexpr uint32_t kBinRegular = 512;                // regular bins (key ranges
 constexpr uint32_t kBinHot = (1u << kBinDigit) - kBinRegular - 1;  // hot slots: one flowId each
 constexpr uint32_t kBinDrop = (1u << kBinDigit) - 1; // rejected requests
 constexpr int kBinMaxBsh = 11;                       // keys per regular bin <= 2048 (k_bin_sort's LDS counters)
+// The 4-byte front record (BatchArgs::rec4): acquire code (acquire : 7 | prio : 1) in the low byte, the key within its
+// regular bin above it, the bin digit on top.
+constexpr int kRec4Abits = 8;
+constexpr int kRec4KeyShift = kRec4Abits;
+constexpr int kRec4DigitShift = kRec4KeyShift + kBinMaxBsh;
+static_assert(kRec4DigitShift + kBinDigit <= 32, "digit, key in bin and acquire code fit a 32-bit record");
+static_assert(kBinHot + kBinRegular + 1 == (1u << kBinDigit), "hot slots, regular bins and kBinDrop fill the digit");
 // The hot set's table: 512 buckets of 4 {flowId, slot} entries (16 KB), a flowId only in its home bucket (k_hot_update
 // leaves a flowId whose bucket is full out of the hot set), so k_prep's lookup is two independent 16-B LDS reads.
 constexpr int kHotBucketBits = 9;
@@ -932,6 +947,16 @@ hipError_t radix_sort_records(uint64_t* a, uint64_t* b, uint64_t n, int lo_bit, 
 const uint32_t* radix_tot(const uint32_t* hist_ws, uint64_t n, int D);
 hipError_t radix_bin_pass(uint64_t* src, uint64_t* out, uint64_t* reg, uint32_t R, uint64_t n, int shift,
                           uint32_t* hist_ws, bool hist_ready, bool csum_ready, hipStream_t stream);
+// The same pass in the compact layout (BatchArgs::rec4; k_prep counted the digits): 4-byte front records in; the
+// regular bins leave as 8-byte records {key | request index | acquire code} (the index from the record's position, the
+// key from the bin and the key in bin), the hot bins as 4-byte compact words in `out`, rejected requests not at all.
+struct Bin4 {
+    uint64_t* reg;            // the regular bins' output (bin_buf)
+    uint32_t R;
+    int kshift, bsh, dshift;
+};
+hipError_t radix_bin_pass4(const uint32_t* src, uint32_t* out, const Bin4& b4, uint64_t n, uint32_t* hist_ws,
+                           bool csum_ready, hipStream_t stream);
 hipError_t launch_seg(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_seg_flow(const BatchArgs& a, hipStream_t stream);  // k_seg_mark + k_seg_classify
 // Binned front half after k_prep: the scatter by bin digit (regular bins to a.bin_buf, hot bins and rejected requests
@@ -939,6 +964,8 @@ hipError_t launch_seg_flow(const BatchArgs& a, hipStream_t stream);  // k_seg_ma
 // next batch's hot flowIds: this batch's longest segments).
 hipError_t launch_bin_front(const BatchArgs& a, uint32_t* hist_ws, bool hist_ready, bool csum_ready, hipStream_t stream);
 hipError_t launch_hot_reset(uint2* hot_tab, hipStream_t stream);
+// Testing aid: a compact-layout batch's sorted records (BatchArgs::rec4) as n 8-byte records in `out`.
+hipError_t launch_rec4_expand(const BatchArgs& a, uint64_t* out, hipStream_t stream);
 hipError_t launch_walk_long(const BatchArgs& a, hipStream_t stream);   // on an aux stream, concurrent with
 bool tiny_walker_enabled(const BatchArgs& a);
 hipError_t launch_walk_tiny(const BatchArgs& a, hipStream_t stream);

@@ -98,6 +98,27 @@ __device__ __forceinline__ Decoded decode_c(const BatchArgs& a, uint32_t c) {
     return d;
 }
 
+// The sorted records as the walkers read them: 8 bytes each, or (R4: BatchArgs::rec4, the binned path's compact
+// layout) the 4-byte compact word alone at the same element positions — there every segment's flowId and end come
+// from the segment lists (short_key / short_end, long_key / long_end), never from a record.
+template <bool R4>
+struct RecOf {
+    using T = uint64_t;
+};
+template <>
+struct RecOf<true> {
+    using T = uint32_t;
+};
+template <bool R4>
+__device__ __forceinline__ const typename RecOf<R4>::T* sorted_recs(const BatchArgs& a) {
+    return reinterpret_cast<const typename RecOf<R4>::T*>(a.rec_sorted);
+}
+__device__ __forceinline__ Decoded decode(const BatchArgs& a, uint32_t c) { return decode_c(a, c); }
+__device__ __forceinline__ uint32_t rec_index(const BatchArgs& a, uint64_t r) {
+    return (uint32_t)((r >> a.abits) & a.imask);
+}
+__device__ __forceinline__ uint32_t rec_index(const BatchArgs&, uint32_t c) { return c >> 8; }
+
 // ------------------------------------------------------------------------------------------- prep
 
 // One block per 4096-request tile (the radix sort's tile). With a.hist0 set the block also counts the
@@ -168,6 +189,7 @@ __global__ void __launch_bounds__(256) k_prep(BatchArgs a) {
         uint64_t rec;
         int32_t st;
         uint32_t d = kBinDrop;  // BIN: a rejected request's bin
+        uint32_t r4 = 0;        // BIN, a.rec4: the 4-byte record below its digit (kRec4*)
         if (key == SG_KEY_BAD || r.acquire <= 0) {
             st = SG_STATUS_BAD_REQUEST;
             rec = sentinel;
@@ -182,6 +204,7 @@ __global__ void __launch_bounds__(256) k_prep(BatchArgs a) {
             st = SG_STATUS_BLOCKED;  // walkers write only non-BLOCKED
             if constexpr (BIN) {  // the flowId's hot slot, else its key range
                 d = key >> a.bin_bsh;
+                r4 = ((key - (d << a.bin_bsh)) << kRec4KeyShift) | (uint32_t)ac;
                 if (!(a.dbg & 131072)) {  // (timing experiment: no hot lookup, every flowId regular)
                     const uint4* hb = reinterpret_cast<const uint4*>(htab + hot_hash(key) * kHotWays);
                     const uint4 e0 = hb[0], e1 = hb[1];
@@ -199,7 +222,8 @@ __global__ void __launch_bounds__(256) k_prep(BatchArgs a) {
             st_stream(o + 1, 0);
             st_stream(o + 2, 0);
         }
-        st_stream(a.rec + i, rec);
+        if (BIN && a.rec4) st_stream(reinterpret_cast<uint32_t*>(a.rec) + i, r4 | (d << kRec4DigitShift));
+        else st_stream(a.rec + i, rec);
         if (a.hist0) ldig[it * 256 + threadIdx.x] = (uint16_t)(BIN ? d : (uint32_t)(rec >> a.hist0_shift) & dmask);
     }
     if (a.hist0) {
@@ -378,7 +402,7 @@ __device__ __forceinline__ void open_period_serial(PeriodState& ps, const Bucket
 // ------------------------------------------------------------------------ serial walker (short)
 
 // Outputs start as BLOCKED (k_prep), so only OK / SHOULD_WAIT results are written here.
-template <bool L>
+template <bool L, bool R4 = false>
 __device__ uint32_t walk_serial(const BatchArgs& a, uint32_t k, uint64_t s, uint64_t e) {
     uint32_t opened = 0;
     const Rule R = a.rules[k];
@@ -395,10 +419,11 @@ __device__ uint32_t walk_serial(const BatchArgs& a, uint32_t k, uint64_t s, uint
     }
     int64_t ws = 0;
     int I = -1;
-    uint64_t nxt = a.rec_sorted[s];
+    const typename RecOf<R4>::T* rs = sorted_recs<R4>(a);
+    typename RecOf<R4>::T nxt = rs[s];
     for (uint64_t j = s; j < e; ++j) {
-        const uint64_t cur = nxt;
-        if (j + 1 < e) nxt = a.rec_sorted[j + 1];  // issue the next record's load before deciding this one
+        const typename RecOf<R4>::T cur = nxt;
+        if (j + 1 < e) nxt = rs[j + 1];  // issue the next record's load before deciding this one
         const Decoded d = decode(a, cur);
         const uint32_t q = pc.of(d.idx);
         if (q != pc.q) {
@@ -620,7 +645,8 @@ struct WaveWalker {
         }
     }
 
-    __device__ void chunk(uint64_t rec, bool act) {
+    template <class RT>
+    __device__ void chunk(RT rec, bool act) {
         Decoded d;
         d.idx = 0;
         d.acq = 0;
@@ -695,31 +721,32 @@ __device__ __forceinline__ uint64_t wave_search(uint64_t lo, uint64_t hi, Pred p
 #else
 #define SG_WAVE_ATTR __device__ __noinline__
 #endif
-template <bool L>
+template <bool L, bool R4 = false>
 SG_WAVE_ATTR void walk_wave(const BatchArgs& a, uint32_t k, uint64_t s, uint64_t e, uint32_t item) {
+    using RT = typename RecOf<R4>::T;
     WaveWalker<L> w(a, k);
     const int lane = w.lane;
     // period ends of this segment from k_long_bounds: lane q holds the first position of period q + 1
     const bool tab = a.long_pend != nullptr && item < kLongTab && w.pc.np <= (uint32_t)kLongPeriods;
     uint32_t pend_l = 0;
     if (tab && lane < kLongPeriods) pend_l = a.long_pend[(size_t)item * kLongPeriods + lane];
-    const uint64_t* rec = a.rec_sorted;
+    const RT* rec = sorted_recs<R4>(a);
     constexpr uint64_t kBlock = 64ull * kWaveUnroll;
-    uint64_t cur[kWaveUnroll];
+    RT cur[kWaveUnroll];
 #pragma unroll
     for (int u = 0; u < kWaveUnroll; ++u) {
         const uint64_t j = s + (uint64_t)u * 64 + lane;
-        cur[u] = j < e ? rec[j] : 0ull;
+        cur[u] = j < e ? rec[j] : (RT)0;
     }
     uint32_t skip_tried_q = 0xFFFFFFFFu;
     uint64_t pos = s;
     while (pos < e) {
         uint64_t npos = pos + kBlock;
-        uint64_t nxt[kWaveUnroll];
+        RT nxt[kWaveUnroll];
 #pragma unroll
         for (int u = 0; u < kWaveUnroll; ++u) {  // prefetch the next block before deciding this one
             const uint64_t j = npos + (uint64_t)u * 64 + lane;
-            nxt[u] = j < e ? rec[j] : 0ull;
+            nxt[u] = j < e ? rec[j] : (RT)0;
         }
         bool skipped = false;
 #pragma unroll
@@ -739,7 +766,7 @@ SG_WAVE_ATTR void walk_wave(const BatchArgs& a, uint32_t k, uint64_t s, uint64_t
                     pe = pe < after ? after : pe;
                 } else {
                     pe = gallop_search(after, e, [&](uint64_t p) {
-                        return (uint32_t)((rec[p] >> a.abits) & a.imask) >= nb;
+                        return rec_index(a, rec[p]) >= nb;
                     }, lane);
                 }
                 if (pe - after >= kSkipMin) {
@@ -751,7 +778,7 @@ SG_WAVE_ATTR void walk_wave(const BatchArgs& a, uint32_t k, uint64_t s, uint64_t
 #pragma unroll
                     for (int v = 0; v < kWaveUnroll; ++v) {
                         const uint64_t j = pe + (uint64_t)v * 64 + lane;
-                        nxt[v] = j < e ? rec[j] : 0ull;
+                        nxt[v] = j < e ? rec[j] : (RT)0;
                     }
                     slot = (uint32_t)bcast32((int)slot, 0);
                     if (slot + np <= a.skip_cap) {
@@ -766,7 +793,7 @@ SG_WAVE_ATTR void walk_wave(const BatchArgs& a, uint32_t k, uint64_t s, uint64_t
 #pragma unroll
                         for (int v = 0; v < kWaveUnroll; ++v) {
                             const uint64_t j = npos + (uint64_t)v * 64 + lane;
-                            nxt[v] = j < e ? rec[j] : 0ull;
+                            nxt[v] = j < e ? rec[j] : (RT)0;
                         }
                     }
                 }
@@ -1014,6 +1041,9 @@ constexpr uint32_t kBinRegCap = kBinWaves * 64 * kBinRows;  // bins up to this s
 constexpr uint32_t kBinStage = 14336;            // records of one output window staged in LDS (112 KB)
 constexpr uint32_t kBinLdsWords = (kBinWaves * kBinKeys * 2 + kBinStage * 8) / 8;  // u16 counters + stage, in u64
 static_assert(kBinWaves * kBinKeys * 4 <= kBinLdsWords * 8, "the big path's u32 counters fit the same LDS");
+// With 4-byte sorted records (BatchArgs::rec4) a whole register-path bin fits one stage: no output windows.
+constexpr uint32_t kBinLdsWords4 = (kBinWaves * kBinKeys * 2 + kBinRegCap * 4) / 8;
+static_assert(kBinWaves * kBinKeys * 4 <= kBinLdsWords4 * 8 && kBinLdsWords4 <= kBinLdsWords, "LDS of the compact layout");
 
 // Exclusive scan of the 1024 digit totals into dbase (every block: 4 KB, L2-resident).
 __device__ __forceinline__ void bin_digit_bases(const BatchArgs& a, uint32_t* dbase, uint32_t* wsum) {
@@ -1141,9 +1171,10 @@ __device__ __forceinline__ void bin_emit(const BatchArgs& a, const uint32_t* lba
 // coalesced stream. A larger bin (a flowId that outgrew the hot set) counts in u32, reads its rows twice in groups and
 // stores each record straight to its position. The list slots' global atomics (one per class per block) are issued
 // before the placement and waited for after it. Block R: the hot bins' segments (one flowId each, in order already).
+template <bool R4>
 __global__ void __launch_bounds__(kBinThreads, 1) k_bin_sort(BatchArgs a) {
     constexpr int kL = kClasses + 1;
-    __shared__ uint64_t lds[kBinLdsWords];
+    __shared__ uint64_t lds[R4 ? kBinLdsWords4 : kBinLdsWords];
     __shared__ uint32_t dbase[1 << kBinDigit];
     __shared__ uint32_t wsum[kBinWaves];
     __shared__ uint32_t lcnt[kL], lbase[kL];
@@ -1237,6 +1268,17 @@ __global__ void __launch_bounds__(kBinThreads, 1) k_bin_sort(BatchArgs a) {
         }
         if (diag) tp4 = __builtin_amdgcn_s_memrealtime();
         // 4. the sorted bin through LDS, kBinStage records at a time (the stage lies past the counters)
+        if constexpr (R4) {  // the compact word of every record (the low 32 bits), the whole bin in one stage
+            uint32_t* stage = reinterpret_cast<uint32_t*>(lds + (kBinWaves * kBinKeys * 2) / 8);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(a.rec_sorted) + s0;
+#pragma unroll
+            for (int u = 0; u < kBinRows; ++u) {
+                const uint32_t p = (pos[u / 2] >> ((u & 1) * 16)) & 0xFFFFu;
+                if (p != 0xFFFFu) stage[p] = (uint32_t)v[u];
+            }
+            __syncthreads();
+            for (uint32_t p = tid; p < len; p += kBinThreads) dst[p] = stage[p];
+        } else {
         uint64_t* stage = lds + (kBinWaves * kBinKeys * 2) / 8;
         uint64_t* dst = a.rec_sorted + s0;
         for (uint32_t w0 = 0; w0 < len; w0 += kBinStage) {
@@ -1249,6 +1291,7 @@ __global__ void __launch_bounds__(kBinThreads, 1) k_bin_sort(BatchArgs a) {
             const uint32_t m = min(kBinStage, len - w0);
             for (uint32_t p = tid; p < m; p += kBinThreads) dst[w0 + p] = stage[p];
             __syncthreads();
+        }
         }
     } else {
         uint32_t(*cnt)[kBinKeys] = reinterpret_cast<uint32_t(*)[kBinKeys]>(lw);
@@ -1274,7 +1317,7 @@ __global__ void __launch_bounds__(kBinThreads, 1) k_bin_sort(BatchArgs a) {
         __syncthreads();
         if (tid < kL && lcnt[tid]) gb = atomicAdd(tid == kClasses ? a.long_count : a.short_count + tid, lcnt[tid]);
         if (diag) tk3 = __builtin_amdgcn_s_memrealtime();
-        uint64_t* dst = a.rec_sorted + s0;
+        typename RecOf<R4>::T* dst = reinterpret_cast<typename RecOf<R4>::T*>(a.rec_sorted) + s0;
         for (uint32_t r0 = c0; r0 < c1; r0 += 64u * kBinRows) {
 #pragma unroll
             for (int u = 0; u < kBinRows; ++u) v[u] = src[min(r0 + (uint32_t)u * 64 + (uint32_t)lane, last)];
@@ -1286,7 +1329,7 @@ __global__ void __launch_bounds__(kBinThreads, 1) k_bin_sort(BatchArgs a) {
                 const uint64_t peers = match_key(d) & __ballot(valid);
                 const uint32_t c = cnt[wave][d];
                 if (valid) {
-                    dst[c + (uint32_t)__popcll(peers & lt)] = v[u];
+                    dst[c + (uint32_t)__popcll(peers & lt)] = (typename RecOf<R4>::T)v[u];
                     if (lane == __builtin_ctzll(peers)) cnt[wave][d] = c + (uint32_t)__popcll(peers);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1410,7 +1453,7 @@ __device__ __forceinline__ void stage_periods(const BatchArgs& a) {
 
 // Long-segment walker: one wave per segment of more than short_max records (grid-stride over the list,
 // grid sized to what is resident at once). Runs concurrently with k_walk_short (separate stream).
-template <bool L>
+template <bool L, bool R4>
 __device__ __forceinline__ void walk_long_body(const BatchArgs& a) {
     const int lane = lane_id();
     const uint32_t n_long = *a.long_count;
@@ -1422,7 +1465,7 @@ __device__ __forceinline__ void walk_long_body(const BatchArgs& a) {
         const uint64_t s = a.long_list[item];
         uint32_t k;
         uint64_t e;
-        if (a.long_key && a.seg_end) {  // segment key and end from k_seg / k_seg_classify
+        if (R4 || (a.long_key && a.seg_end)) {  // segment key and end from k_seg / k_seg_classify / k_bin_sort
             k = a.long_key[item];
             e = a.long_end ? a.long_end[item] : a.seg_end[k];
         } else {  // segment end: the first record with another flowId
@@ -1432,7 +1475,7 @@ __device__ __forceinline__ void walk_long_body(const BatchArgs& a) {
             }, lane);
         }
         const uint64_t t0 = (a.dbg & 64) ? __builtin_amdgcn_s_memrealtime() : 0;
-        walk_wave<L>(a, k, s, e, item);
+        walk_wave<L, R4>(a, k, s, e, item);
         if (a.dbg & 64) {
             const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
             const uint64_t len = e - s;
@@ -1449,8 +1492,10 @@ __device__ __forceinline__ void walk_long_body(const BatchArgs& a) {
 // Period ends of the long segments (one thread per segment and period): the wave walker jumps over a
 // window period that can admit nothing more without searching for where it ends (that search was a
 // chain of dependent loads per period). Runs on the wave walker's stream just before it.
+template <bool R4>
 __global__ void __launch_bounds__(256) k_long_bounds(BatchArgs a) {
     if (*a.err) return;
+    const typename RecOf<R4>::T* rs = sorted_recs<R4>(a);
     const uint32_t n_long = min(*a.long_count, kLongTab);
     const uint32_t total = n_long * (uint32_t)kLongPeriods;
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
@@ -1463,7 +1508,7 @@ __global__ void __launch_bounds__(256) k_long_bounds(BatchArgs a) {
         uint64_t lo = a.long_list[item], hi = a.long_end ? a.long_end[item] : a.seg_end[k];
         while (lo < hi) {  // first record of the segment in period q + 1 or later
             const uint64_t mid = (lo + hi) >> 1;
-            if ((uint32_t)((a.rec_sorted[mid] >> a.abits) & a.imask) >= nb) hi = mid;
+            if (rec_index(a, rs[mid]) >= nb) hi = mid;
             else lo = mid + 1;
         }
         a.long_pend[t] = (uint32_t)lo;
@@ -1473,11 +1518,12 @@ __global__ void __launch_bounds__(256) k_long_bounds(BatchArgs a) {
 #ifndef SG_WLONG_BLOCKS
 #define SG_WLONG_BLOCKS 2
 #endif
+template <bool R4>
 __global__ void __launch_bounds__(256, SG_WLONG_BLOCKS) k_walk_long(BatchArgs a) {
     if (*a.err || (a.dbg & 4096)) return;
     stage_periods(a);
-    if (g_blds) walk_long_body<true>(a);
-    else walk_long_body<false>(a);
+    if (g_blds) walk_long_body<true, R4>(a);
+    else walk_long_body<false, R4>(a);
 }
 
 // Serial walk of one flowId segment with the ring's {period, PASS, WAITING} of all SM >= S slots held in
@@ -1545,9 +1591,12 @@ constexpr int kBlk = 4;  // records per block of the short walker's double-buffe
 // per-record step (one decision) while any lane can take it, then opens the parked lanes' periods in one
 // pass. The period-open code (ring sums over S slots, bucket close) thus runs ~once per period of the
 // wave instead of in almost every record step (64 lanes each change period every few records).
-template <int SM, bool L>
+template <int SM, bool L, bool R4 = false>
 __device__ __forceinline__ void walk_reg(const BatchArgs& a, bool act, uint32_t k, uint64_t s, uint64_t e,
-                                         const Rule& R, const Occ& occ, SlotSnap* snap, uint64_t* buf, int64_t T0) {
+                                         const Rule& R, const Occ& occ, SlotSnap* snap, typename RecOf<R4>::T* buf,
+                                         int64_t T0) {
+    using RT = typename RecOf<R4>::T;
+    const RT* rs = sorted_recs<R4>(a);
     Bucket* ring = a.ring + (size_t)k * a.stride;
     BucketHot* hot = a.hot + (size_t)k * a.stride;
     const int S = R.S;
@@ -1567,12 +1616,12 @@ __device__ __forceinline__ void walk_reg(const BatchArgs& a, bool act, uint32_t 
     // conditional load's value meets a constant in a phi, and that copy waits for the load at once, which
     // turned the prefetch into a full memory round trip every kBlk records.
     const uint64_t n1 = a.n - 1;
-    uint64_t nb[kBlk];
+    RT nb[kBlk];
     uint64_t p = s;  // position of buf[0]'s block
     int left = kBlk; // records of the current block not yet consumed (buf[0] is the next one)
     bool more = act && p + kBlk < e;  // the segment continues past this block
 #pragma unroll
-    for (int u = 0; u < kBlk; ++u) nb[u] = a.rec_sorted[min(p + kBlk + u, n1)];
+    for (int u = 0; u < kBlk; ++u) nb[u] = rs[min(p + kBlk + u, n1)];
     bool live = act;  // records left
     uint32_t qn = 0;  // period of the next record (valid when live)
     Decoded dn;       // the next record, decoded
@@ -1587,7 +1636,7 @@ __device__ __forceinline__ void walk_reg(const BatchArgs& a, bool act, uint32_t 
     auto advance = [&]() {  // consume buf[0]
 #pragma unroll
         for (int v = 0; v < kBlk - 1; ++v) buf[v] = buf[v + 1];  // resident values: plain moves
-        buf[kBlk - 1] = ~0ull;
+        buf[kBlk - 1] = (RT)~0ull;
         if (--left == 0) {
             if (!more) {
                 live = false;
@@ -1599,7 +1648,7 @@ __device__ __forceinline__ void walk_reg(const BatchArgs& a, bool act, uint32_t 
             left = kBlk;
             more = p + kBlk < e;
 #pragma unroll
-            for (int u = 0; u < kBlk; ++u) nb[u] = a.rec_sorted[min(p + kBlk + u, n1)];
+            for (int u = 0; u < kBlk; ++u) nb[u] = rs[min(p + kBlk + u, n1)];
         }
     };
     if (live) peek();
@@ -1692,27 +1741,28 @@ __device__ __forceinline__ void walk_reg(const BatchArgs& a, bool act, uint32_t 
 // issued since (a store round trip per period open).
 __device__ __forceinline__ void wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
-template <int R>
+// W: words per record in memory (2: the low word of an 8-byte record; 1: the 4-byte compact record).
+template <int R, int W>
 __device__ __forceinline__ void glds_rows(const uint32_t* src, uint32_t* wrecs) {
     if constexpr (R > 0) {
-        // row R - 1: the low word of record R - 1. The immediate offset (8 (R - 1) bytes) is added to the LDS
+        // row R - 1: the low word of record R - 1. The immediate offset (4 W (R - 1) bytes) is added to the LDS
         // address too, so the LDS base is moved back by as much.
-        glds_rows<R - 1>(src, wrecs);
+        glds_rows<R - 1, W>(src, wrecs);
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(wrecs + (R - 1) * 64 - 2 * (R - 1)),
-                                         4, 8 * (R - 1), 0);
+                                         (__attribute__((address_space(3))) void*)(wrecs + (R - 1) * 64 - W * (R - 1)),
+                                         4, 4 * W * (R - 1), 0);
     }
 }
 
-template <int R>
+template <int R, bool R4>
 __device__ __forceinline__ void stage_records(const BatchArgs& a, uint32_t* wrecs, uint64_t p) {
-    glds_rows<R>(reinterpret_cast<const uint32_t*>(a.rec_sorted + p), wrecs);
+    glds_rows<R, R4 ? 1 : 2>(reinterpret_cast<const uint32_t*>(sorted_recs<R4>(a) + p), wrecs);
 }
 
 // walk_reg with the records read from LDS: the group staged each lane's first kRecW compact records (with the
 // ring gather, one wait for both); a lane that has used its window parks, and when no lane can go on the wave
 // stages the parked lanes' next windows at once. Same decisions as walk_serial.
-template <int SM, bool L>
+template <int SM, bool L, bool R4>
 __device__ __forceinline__ void walk_lds(const BatchArgs& a, bool act, uint32_t k, uint64_t s, uint64_t e,
                                          const Rule& R, const Occ& occ, SlotSnap* snap, uint32_t* wrecs, int lane,
                                          int64_t T0, int rows) {
@@ -1756,7 +1806,7 @@ __device__ __forceinline__ void walk_lds(const BatchArgs& a, bool act, uint32_t 
             if (!__ballot(live)) break;
             // every live lane waits for its next window: stage them all, one wait
             if (park) {
-                stage_records<kRecW>(a, wrecs, p);
+                stage_records<kRecW, R4>(a, wrecs, p);
                 wb = p;
                 win = kRecW;
             }
@@ -1860,7 +1910,7 @@ constexpr int kShortBlocksPerCu = SG_SHORT_BLOCKS;  // occupancy target (VGPR bu
 // one group ahead (they ride along with the previous group's loads, so a group costs one memory round trip
 // before its walk: ring, rule, occupy counters, segment end and records together) and first record windows
 // sized to the length class.
-template <int SM, bool L>
+template <int SM, bool L, bool R4>
 __device__ __forceinline__ void walk_short_lds(const BatchArgs& a, SlotSnap* snap_all, uint32_t* recs_all) {
     static_assert(SM > 0, "LDS ring snapshot");
     const int lane = lane_id();
@@ -1912,9 +1962,9 @@ __device__ __forceinline__ void walk_short_lds(const BatchArgs& a, SlotSnap* sna
         // first window: the class's longest segment (<= 4, <= 16 records) or kRecW
         static_assert(kRecW >= (int)kClassMax[1], "the first window of class 1 must fit the lane's LDS rows");
         const int rows = c == 0 ? (int)kClassMax[0] : c == 1 ? (int)kClassMax[1] : kRecW;
-        if (c == 0) stage_records<kClassMax[0]>(a, wrecs, s);
-        else if (c == 1) stage_records<kClassMax[1]>(a, wrecs, s);
-        else stage_records<kRecW>(a, wrecs, s);
+        if (c == 0) stage_records<kClassMax[0], R4>(a, wrecs, s);
+        else if (c == 1) stage_records<kClassMax[1], R4>(a, wrecs, s);
+        else stage_records<kRecW, R4>(a, wrecs, s);
         // the next group's descriptors (unconditional: a conditional load would be copied, and wait, at the merge)
         desc(min(g + nwaves, total - 1), c_n, act_n, s_n, k_n, e_n);
         {
@@ -1955,7 +2005,7 @@ __device__ __forceinline__ void walk_short_lds(const BatchArgs& a, SlotSnap* sna
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const uint64_t tw1 = (a.dbg & 64) ? __builtin_amdgcn_s_memrealtime() : 0;
-        walk_lds<SM, L>(a, act, k, s, e, R, occ, snap + lane * SM, wrecs, lane, T0, rows);
+        walk_lds<SM, L, R4>(a, act, k, s, e, R, occ, snap + lane * SM, wrecs, lane, T0, rows);
         if (a.dbg & 64) {  // per class: groups, gather time, walk time (100 MHz ticks)
             const uint64_t tw2 = __builtin_amdgcn_s_memrealtime();
             if (lane == 0) {
@@ -1968,12 +2018,13 @@ __device__ __forceinline__ void walk_short_lds(const BatchArgs& a, SlotSnap* sna
     }
 }
 
-template <int SM, bool L, bool C>
+template <int SM, bool L, bool C, bool R4>
 __device__ __forceinline__ void walk_short_body(const BatchArgs& a, SlotSnap* snap_all, uint32_t* recs_all) {
+    using RT = typename RecOf<R4>::T;
     if constexpr (SM > 0 && C) {
         const int64_t T0 = a.p0[0] * (int64_t)a.wl[0];
         if (a.narrow && narrow_span(a, T0)) {
-            walk_short_lds<SM, L>(a, snap_all, recs_all);
+            walk_short_lds<SM, L, R4>(a, snap_all, recs_all);
             return;
         }
     }
@@ -2014,9 +2065,9 @@ __device__ __forceinline__ void walk_short_body(const BatchArgs& a, SlotSnap* sn
             const uint64_t e = a.short_end ? a.short_end[li] : a.seg_end[k];
             const Rule R = a.rules[k];
             const Occ occ = a.occ[k];
-            uint64_t buf[kBlk];
+            RT buf[kBlk];
 #pragma unroll
-            for (int u = 0; u < kBlk; ++u) buf[u] = a.rec_sorted[min(s + u, a.n - 1)];
+            for (int u = 0; u < kBlk; ++u) buf[u] = sorted_recs<R4>(a)[min(s + u, a.n - 1)];
             {
                 // piece t*64 + lane: bucket q = piece % SM of the ring of lane j = piece / SM, from the hot mirror
                 // ({start, PASS | WAITING << 32}); slots past the handle's stride read slot 0 again (ignored: q >= S)
@@ -2049,7 +2100,7 @@ __device__ __forceinline__ void walk_short_body(const BatchArgs& a, SlotSnap* sn
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
             const uint64_t tw1 = (a.dbg & 64) ? __builtin_amdgcn_s_memrealtime() : 0;
-            walk_reg<SM, L>(a, act, k, s, e, R, occ, snap + lane * SM, buf, T0);
+            walk_reg<SM, L, R4>(a, act, k, s, e, R, occ, snap + lane * SM, buf, T0);
             if (a.dbg & 64) {  // per class: groups, gather time, walk time (100 MHz ticks)
                 const uint64_t tw2 = __builtin_amdgcn_s_memrealtime();
                 if (lane == 0) {
@@ -2063,15 +2114,19 @@ __device__ __forceinline__ void walk_short_body(const BatchArgs& a, SlotSnap* sn
         }
         if (!act) continue;
         const uint64_t s = a.short_list[a.class_off[c] + i];
-        const uint32_t k = (uint32_t)(a.rec_sorted[s] >> a.kshift);
-        const uint64_t lim = s + (uint64_t)min(a.short_max, c < kClasses - 1 ? kClassMax[c] : 0xFFFFFFFFu) + 1;
-        uint64_t e = s + 1;
-        while (e < a.n && e < lim && (uint32_t)(a.rec_sorted[e] >> a.kshift) == k) ++e;
-        walk_serial<L>(a, k, s, e);
+        if constexpr (R4) {  // compact records carry no flowId: the segment's key and end from the lists
+            walk_serial<L, true>(a, a.short_key[a.class_off[c] + i], s, a.short_end[a.class_off[c] + i]);
+        } else {
+            const uint32_t k = (uint32_t)(a.rec_sorted[s] >> a.kshift);
+            const uint64_t lim = s + (uint64_t)min(a.short_max, c < kClasses - 1 ? kClassMax[c] : 0xFFFFFFFFu) + 1;
+            uint64_t e = s + 1;
+            while (e < a.n && e < lim && (uint32_t)(a.rec_sorted[e] >> a.kshift) == k) ++e;
+            walk_serial<L>(a, k, s, e);
+        }
     }
 }
 
-template <int SM, bool C>
+template <int SM, bool C, bool R4 = false>
 #ifndef SG_SHORT_C_BLOCKS
 #define SG_SHORT_C_BLOCKS 2
 #endif
@@ -2081,8 +2136,8 @@ __global__ void __launch_bounds__(256, C ? SG_SHORT_C_BLOCKS : kShortBlocksPerCu
     __shared__ uint32_t recs_all[SM > 0 && C ? 4 * kRecW * 64 : 1];
     if (*a.err || (a.dbg & 8192)) return;
     stage_periods(a);
-    if (g_blds) walk_short_body<SM, true, C>(a, snap_all, recs_all);
-    else walk_short_body<SM, false, C>(a, snap_all, recs_all);
+    if (g_blds) walk_short_body<SM, true, C, R4>(a, snap_all, recs_all);
+    else walk_short_body<SM, false, C, R4>(a, snap_all, recs_all);
 }
 
 // Tiny-segment walker: one thread per flowId of length class 0 (<= kClassMax[0] records, most touched flowIds of a
@@ -2091,8 +2146,10 @@ __global__ void __launch_bounds__(256, C ? SG_SHORT_C_BLOCKS : kShortBlocksPerCu
 // LDS beyond the period tables and runs at more waves per SIMD: a group of 64 such segments in the lane-per-segment
 // walker paid two memory round trips and a wave-wide period phase for a handful of decisions. Same decisions as
 // walk_serial (ClusterFlowChecker.acquireClusterToken :67-111).
-template <int SM, bool L>
+template <int SM, bool L, bool R4>
 __device__ __forceinline__ void walk_tiny_body(const BatchArgs& a) {
+    using RT = typename RecOf<R4>::T;
+    const RT* rs = sorted_recs<R4>(a);
     constexpr int kR = (int)kClassMax[0];
     const uint32_t cnt = a.short_count[0];
     const uint64_t base = a.class_off[0];
@@ -2103,8 +2160,8 @@ __device__ __forceinline__ void walk_tiny_body(const BatchArgs& a) {
         const uint32_t e = a.short_end[base + t];
         const Rule R = a.rules[k];
         const Occ occ = a.occ[k];
-        uint64_t r0 = a.rec_sorted[s], r1 = a.rec_sorted[min(s + 1, a.n - 1)];
-        uint64_t r2 = a.rec_sorted[min(s + 2, a.n - 1)], r3 = a.rec_sorted[min(s + 3, a.n - 1)];
+        RT r0 = rs[s], r1 = rs[min(s + 1, a.n - 1)];
+        RT r2 = rs[min(s + 2, a.n - 1)], r3 = rs[min(s + 3, a.n - 1)];
         static_assert(kR == 4, "four record registers");
         Bucket* ring = a.ring + (size_t)k * a.stride;
         BucketHot* hot = a.hot + (size_t)k * a.stride;
@@ -2199,22 +2256,25 @@ __device__ __forceinline__ void walk_tiny_body(const BatchArgs& a) {
     }
 }
 
-template <int SM>
+template <int SM, bool R4 = false>
 #ifndef SG_TINY_BLOCKS
 #define SG_TINY_BLOCKS 4
 #endif
 __global__ void __launch_bounds__(256, SG_TINY_BLOCKS) k_walk_tiny(BatchArgs a) {
     if (*a.err || !tiny_active(a)) return;
     stage_periods(a);
-    if (g_blds) walk_tiny_body<SM, true>(a);
-    else walk_tiny_body<SM, false>(a);
+    if (g_blds) walk_tiny_body<SM, true, R4>(a);
+    else walk_tiny_body<SM, false, R4>(a);
 }
 
 // One wave per skipped piece: Σ acquire and Σ prioritized acquire over its records, added with 64-bit
 // atomics (pieces of one range share a bucket).
 constexpr int kSkipU = 8;
+template <bool R4>
 __global__ void __launch_bounds__(256) k_skip_apply(BatchArgs a) {
+    using RT = typename RecOf<R4>::T;
     if (*a.err) return;
+    const RT* rs = sorted_recs<R4>(a);
     const uint32_t cnt = min(*a.skip_count, a.skip_cap);
     const int lane = lane_id();
     const uint32_t wave = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
@@ -2225,11 +2285,11 @@ __global__ void __launch_bounds__(256) k_skip_apply(BatchArgs a) {
         // kSkipU rows of 64 records loaded together (one row per round trip left the wave latency-bound: a 4096-record
         // piece took 64 of them)
         for (uint64_t j0 = (uint64_t)sk.z; j0 < sk.w; j0 += 64ull * kSkipU) {
-            uint64_t r[kSkipU];
+            RT r[kSkipU];
 #pragma unroll
             for (int u = 0; u < kSkipU; ++u) {
                 const uint64_t j = j0 + (uint64_t)u * 64 + lane;
-                r[u] = j < sk.w ? a.rec_sorted[j] : 0ull;
+                r[u] = j < sk.w ? rs[j] : (RT)0;
             }
 #pragma unroll
             for (int u = 0; u < kSkipU; ++u) {
@@ -2391,15 +2451,58 @@ void lds_poison(hipStream_t stream) {
 }
 
 hipError_t launch_bin_front(const BatchArgs& a, uint32_t* hist_ws, bool hist_ready, bool csum_ready, hipStream_t stream) {
-    hipError_t e = radix_bin_pass(a.rec, a.rec_sorted, a.bin_buf, a.bin_R, a.n, a.bin_dshift, hist_ws, hist_ready,
-                                  csum_ready, stream);
+    hipError_t e;
+    if (a.rec4) {
+        if (!hist_ready || a.abits != kRec4Abits) return hipErrorInvalidValue;  // k_prep<true> counts the digits
+        e = radix_bin_pass4(reinterpret_cast<const uint32_t*>(a.rec), reinterpret_cast<uint32_t*>(a.rec_sorted),
+                            Bin4{a.bin_buf, a.bin_R, a.kshift, a.bin_bsh, a.bin_dshift}, a.n, hist_ws, csum_ready,
+                            stream);
+    } else {
+        e = radix_bin_pass(a.rec, a.rec_sorted, a.bin_buf, a.bin_R, a.n, a.bin_dshift, hist_ws, hist_ready, csum_ready,
+                           stream);
+    }
     if (e != hipSuccess) return e;
     BatchArgs b = a;
     b.bin_tot = radix_tot(hist_ws, a.n, kBinDigit);
     lds_poison(stream);
-    hipLaunchKernelGGL(k_bin_sort, dim3(a.bin_R + 1), dim3(kBinThreads), 0, stream, b);
+    if (a.rec4) hipLaunchKernelGGL(k_bin_sort<true>, dim3(a.bin_R + 1), dim3(kBinThreads), 0, stream, b);
+    else hipLaunchKernelGGL(k_bin_sort<false>, dim3(a.bin_R + 1), dim3(kBinThreads), 0, stream, b);
     lds_poison(stream);
     hipLaunchKernelGGL(k_hot_update, dim3(1), dim3(1024), 0, stream, b);
+    return hipGetLastError();
+}
+
+// Testing aid (sg_debug_copy, off the timed path): the compact layout's sorted records widened into `out` as the
+// 8-byte records of the other layout, {flowId | request index | acquire code} — every listed segment's compact words
+// under its flowId from the batch's segment lists (one wave per segment); positions no segment covers (the rejected
+// requests' bin) hold the bare sentinel key.
+__global__ void __launch_bounds__(256) k_rec4_expand(BatchArgs a, uint64_t* out) {
+    const uint64_t sentinel = (uint64_t)a.K << a.kshift;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < a.n; j += (uint64_t)gridDim.x * blockDim.x)
+        out[j] = sentinel;
+}
+
+__global__ void __launch_bounds__(256) k_rec4_expand_segs(BatchArgs a, uint64_t* out) {
+    const uint32_t* rs = sorted_recs<true>(a);
+    const int lane = lane_id();
+    const uint32_t wave = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    const uint32_t nwaves = gridDim.x * (blockDim.x / 64);
+    for (int l = 0; l <= kClasses; ++l) {
+        const bool lng = l == kClasses;
+        const uint32_t cnt = lng ? *a.long_count : a.short_count[l];
+        for (uint32_t i = wave; i < cnt; i += nwaves) {
+            const uint64_t li = lng ? (uint64_t)i : a.class_off[l] + i;
+            const uint32_t s = lng ? a.long_list[li] : a.short_list[li];
+            const uint32_t e = lng ? a.long_end[li] : a.short_end[li];
+            const uint64_t k = lng ? a.long_key[li] : a.short_key[li];
+            for (uint64_t j = (uint64_t)s + lane; j < e && j < a.n; j += 64) out[j] = (k << a.kshift) | rs[j];
+        }
+    }
+}
+
+hipError_t launch_rec4_expand(const BatchArgs& a, uint64_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_rec4_expand, dim3(1024), dim3(256), 0, stream, a, out);
+    hipLaunchKernelGGL(k_rec4_expand_segs, dim3(1024), dim3(256), 0, stream, a, out);
     return hipGetLastError();
 }
 
@@ -2459,8 +2562,17 @@ static unsigned walker_grid(const void* kern, int walk_cus) {
 
 // Persistent walkers: at most as many blocks as fit on the chip at once (each wave loops over its queue).
 hipError_t launch_walk_long(const BatchArgs& a, hipStream_t stream) {
-    if (a.long_pend && a.long_key && a.seg_end) hipLaunchKernelGGL(k_long_bounds, dim3(1024), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(k_walk_long, dim3(walker_grid((const void*)k_walk_long, a.walk_cus)), dim3(256), 0, stream, a);
+    if (a.rec4) {
+        if (!a.long_key || !a.long_end) return hipErrorInvalidValue;  // compact records carry no flowId
+        if (a.long_pend) hipLaunchKernelGGL(k_long_bounds<true>, dim3(1024), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_walk_long<true>, dim3(walker_grid((const void*)k_walk_long<true>, a.walk_cus)), dim3(256),
+                           0, stream, a);
+        return hipGetLastError();
+    }
+    if (a.long_pend && a.long_key && a.seg_end)
+        hipLaunchKernelGGL(k_long_bounds<false>, dim3(1024), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_walk_long<false>, dim3(walker_grid((const void*)k_walk_long<false>, a.walk_cus)), dim3(256), 0,
+                       stream, a);
     return hipGetLastError();
 }
 
@@ -2470,6 +2582,14 @@ static bool short_compact(const BatchArgs& a) { return a.abits == 8 && a.imask <
 template <int SM>
 static hipError_t launch_short_sm(const BatchArgs& a, hipStream_t stream) {
     const bool c = SM > 0 && short_compact(a);
+    if (a.rec4) {  // compact sorted records: the segments' flowIds and ends come from the lists
+        if (!a.short_key || !a.short_end) return hipErrorInvalidValue;
+        const void* kern4 = c ? (const void*)k_walk_short<SM, true, true> : (const void*)k_walk_short<SM, false, true>;
+        const unsigned blocks4 = walker_grid(kern4, a.walk_cus);
+        if (c) hipLaunchKernelGGL((k_walk_short<SM, true, true>), dim3(blocks4), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((k_walk_short<SM, false, true>), dim3(blocks4), dim3(256), 0, stream, a);
+        return hipGetLastError();
+    }
     const void* kern = c ? (const void*)k_walk_short<SM, true> : (const void*)k_walk_short<SM, false>;
     const unsigned blocks = walker_grid(kern, a.walk_cus);
     if (c) hipLaunchKernelGGL((k_walk_short<SM, true>), dim3(blocks), dim3(256), 0, stream, a);
@@ -2479,8 +2599,12 @@ static hipError_t launch_short_sm(const BatchArgs& a, hipStream_t stream) {
 
 template <int SM>
 static hipError_t launch_tiny_sm(const BatchArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL((k_walk_tiny<SM>), dim3(walker_grid((const void*)k_walk_tiny<SM>, a.walk_cus)), dim3(256), 0,
-                       stream, a);
+    if (a.rec4)
+        hipLaunchKernelGGL((k_walk_tiny<SM, true>), dim3(walker_grid((const void*)k_walk_tiny<SM, true>, a.walk_cus)),
+                           dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((k_walk_tiny<SM>), dim3(walker_grid((const void*)k_walk_tiny<SM>, a.walk_cus)), dim3(256), 0,
+                           stream, a);
     return hipGetLastError();
 }
 
@@ -2510,7 +2634,8 @@ hipError_t launch_walk_short(const BatchArgs& a, hipStream_t stream) {
 }
 
 hipError_t launch_skip_apply(const BatchArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(k_skip_apply, dim3(2048), dim3(256), 0, stream, a);
+    if (a.rec4) hipLaunchKernelGGL(k_skip_apply<true>, dim3(2048), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(k_skip_apply<false>, dim3(2048), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

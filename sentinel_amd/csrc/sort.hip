@@ -319,6 +319,138 @@ __global__ void __launch_bounds__(kSortThreads) k_radix_scatter(const uint64_t* 
     }
 }
 
+// The bin pass of the compact layout (BatchArgs::rec4, kRec4*): k_radix_scatter<kBinDigit, false> with BinSplit, except
+// that a record is read as 32 bits at its request index and widened when it is placed in LDS — {key | bin digit |
+// request index | acquire code}, the index from its position in the tile, the key from the bin and the key in bin —
+// and that only the regular bins leave as 8-byte records (k_bin_sort sorts them by that key): a hot bin's records go
+// to `out` as the 4-byte compact word {request index | acquire code} at the same element positions (their flowId is
+// the hot slot's, which k_bin_sort lists), and rejected requests (kBinDrop) get no sorted copy.
+__global__ void __launch_bounds__(kSortThreads) k_bin_scatter4(const uint32_t* in, uint32_t* out, uint64_t n,
+                                                               const uint32_t* hist, uint32_t ntiles, const uint32_t* tot,
+                                                               Bin4 b4) {
+    constexpr int D = kBinDigit;
+    constexpr int kBins = 1 << D;
+    constexpr int kPer = kBins / kSortThreads;  // digits per thread
+    using Cnt = uint16_t;                       // wave counts <= 1024
+    __shared__ uint64_t stage[kTile];
+    __shared__ Cnt wcnt[kSortWaves][kBins];  // per-wave running digit count, then per-wave base
+    __shared__ uint32_t dstart[kBins];       // tile-local start of each digit's run
+    __shared__ uint32_t gbase[kBins];        // global start of each digit's run of this tile
+    __shared__ uint32_t wtot[kSortWaves];
+    __shared__ uint32_t btot[kSortWaves];
+    const uint32_t tile = xcd_tile(blockIdx.x, ntiles);
+    if (tile >= ntiles) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t tv[kPer];  // totals of digits tid*kPer .. (k_chunkscan)
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) tv[i] = tot[tid * kPer + i];
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) {
+        const int d = tid + i * kSortThreads;
+        gbase[d] = hist[(size_t)tile * kBins + d];  // the tile's row of column-relative run offsets (k_rescan)
+#pragma unroll
+        for (int w = 0; w < kSortWaves; ++w) wcnt[w][d] = 0;
+    }
+    // digit bases: exclusive scan of the totals (digits tid*kPer .. contiguous per thread), added after the barrier
+    uint32_t bsum = 0;
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) bsum += tv[i];
+    uint32_t bx = bsum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)bx, (unsigned)o, 64);
+        if (lane >= o) bx += y;
+    }
+    if (lane == 63) btot[wave] = bx;
+    const uint64_t base = (uint64_t)tile * kTile;
+    const uint64_t wbase = base + (uint64_t)wave * kWaveRecs;
+    const uint64_t lt = (1ull << lane) - 1ull;
+    uint32_t rec[kRounds];
+    uint32_t rank[kRounds];
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const uint64_t idx = wbase + (uint64_t)r * 64 + lane;
+        rec[r] = idx < n ? in[idx] : 0u;
+    }
+    __syncthreads();
+    {
+        uint32_t b = bx - bsum;
+        for (int w = 0; w < wave; ++w) b += btot[w];
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            gbase[tid * kPer + i] += b;
+            b += tv[i];
+        }
+    }
+    // 1. rank within the wave (wave-private counters: LDS ops of one wave execute in order)
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const bool valid = wbase + (uint64_t)r * 64 + lane < n;
+        const uint32_t d = (rec[r] >> kRec4DigitShift) & (kBins - 1);
+        const uint64_t peers = match_digit<D>(d) & __ballot(valid);
+        const uint32_t c = wcnt[wave][d];
+        rank[r] = c + (uint32_t)__popcll(peers & lt);
+        if (valid && lane == __builtin_ctzll(peers)) wcnt[wave][d] = (Cnt)(c + (uint32_t)__popcll(peers));
+    }
+    __syncthreads();
+    // 2. digits tid*kPer .. +kPer-1: per-wave bases, tile totals, tile-local digit starts (block scan)
+    {
+        uint32_t tot[kPer], sum = 0;
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            const int d = tid * kPer + i;
+            uint32_t t = 0;
+#pragma unroll
+            for (int w = 0; w < kSortWaves; ++w) {
+                const uint32_t c = wcnt[w][d];
+                wcnt[w][d] = (Cnt)t;
+                t += c;
+            }
+            tot[i] = t;
+            sum += t;
+        }
+        uint32_t x = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)x, (unsigned)o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wtot[wave] = x;
+        __syncthreads();
+        uint32_t off = x - sum;
+        for (int w = 0; w < wave; ++w) off += wtot[w];
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            dstart[tid * kPer + i] = off;
+            off += tot[i];
+        }
+    }
+    __syncthreads();
+    // 3. place the records digit-sorted in LDS, widened to 8 bytes
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const uint64_t idx = wbase + (uint64_t)r * 64 + lane;
+        if (idx < n) {
+            const uint32_t d = (rec[r] >> kRec4DigitShift) & (kBins - 1);
+            const uint32_t kib = (rec[r] >> kRec4KeyShift) & ((1u << kBinMaxBsh) - 1u);
+            const uint32_t key = d < b4.R ? (d << b4.bsh) + kib : 0u;
+            const uint64_t v = ((uint64_t)key << b4.kshift) | (idx << kRec4Abits) | (uint64_t)(rec[r] & ((1u << kRec4Abits) - 1u));
+            stage[dstart[d] + (uint32_t)wcnt[wave][d] + rank[r]] = v | ((uint64_t)d << b4.dshift);
+        }
+    }
+    __syncthreads();
+    // 4. write out in digit order
+    const uint32_t cnt = (uint32_t)min((uint64_t)kTile, n - base);
+    const uint64_t keep = ~((uint64_t)(kBins - 1) << b4.dshift);
+    for (uint32_t p = tid; p < cnt; p += kSortThreads) {
+        const uint64_t v = stage[p];
+        const uint32_t d = (uint32_t)(v >> b4.dshift) & (kBins - 1);
+        const uint32_t gp = gbase[d] + (p - dstart[d]);
+        if (d < b4.R) b4.reg[gp] = v & keep;
+        else if (d != kBinDrop) out[gp] = (uint32_t)(v & keep);
+    }
+}
+
 bool radix_csum_atomic() {  // read per sort (a getenv per batch): tests switch it per engine
     const char* e = std::getenv("SG_CSUM_ATOMIC");
     return e ? std::atoi(e) != 0 : true;
@@ -389,6 +521,23 @@ hipError_t radix_bin_pass(uint64_t* src, uint64_t* out, uint64_t* reg, uint32_t 
                           uint32_t* hist_ws, bool hist_ready, bool csum_ready, hipStream_t stream) {
     static_assert(kBinDigit == 10, "radix_pass<10>");
     return radix_pass<10>(src, out, n, shift, hist_ws, stream, hist_ready, nullptr, csum_ready, BinSplit{reg, R});
+}
+
+hipError_t radix_bin_pass4(const uint32_t* src, uint32_t* out, const Bin4& b4, uint64_t n, uint32_t* hist_ws,
+                           bool csum_ready, hipStream_t stream) {
+    constexpr int D = kBinDigit;
+    const uint32_t ntiles = (uint32_t)((n + kTile - 1) / kTile);
+    const uint32_t nchunks = (ntiles + kChunkTiles - 1) / kChunkTiles;
+    uint32_t* hist = hist_ws;                               // radix_pass's layout: k_prep's rows, chunk sums, totals
+    uint32_t* csum = hist_ws + (size_t)ntiles * (1u << D);
+    uint32_t* tot = csum + (size_t)nchunks * (1u << D);
+    if (!csum_ready) hipLaunchKernelGGL(k_colsum<D>, dim3(nchunks), dim3(1u << D), 0, stream, hist, ntiles, csum);
+    hipLaunchKernelGGL(k_chunkscan<D>, dim3((1u << D) / 64), dim3(1024), 0, stream, csum, nchunks, tot);
+    hipLaunchKernelGGL(k_rescan<D>, dim3(nchunks), dim3(1u << D), 0, stream, hist, csum, ntiles);
+    const uint32_t grid = 8 * ((ntiles + 7) / 8);  // xcd_tile: blocks past ntiles return at once
+    lds_poison(stream);
+    hipLaunchKernelGGL(k_bin_scatter4, dim3(grid), dim3(kSortThreads), 0, stream, src, out, n, hist, ntiles, tot, b4);
+    return hipGetLastError();
 }
 
 // Sorts n records on bits [lo_bit, hi_bit) (bits above hi_bit must be zero or already grouped),
