@@ -352,6 +352,7 @@ typedef struct sg_local_event {
 #define SG_LOCAL_BLOCK_DEGRADE 2  /* DegradeException                                         */
 #define SG_LOCAL_PASS_WAIT     3  /* PriorityWaitException: passes after wait_ms              */
                                   /* 4: SG_LOCAL_BLOCK_PARAM (sg_slot_decide_batch, below)     */
+                                  /* 5: SG_LOCAL_BLOCK_AUTHORITY (sg_local_load_authority_rules) */
 typedef struct sg_local_result {
     int32_t status;               /* entries: SG_LOCAL_*; exits: 0                            */
     int32_t wait_ms;
@@ -668,10 +669,47 @@ int sg_local_read_state(sg_handle* h, uint32_t res, int64_t* second, int64_t* bo
 int sg_local_load_flow_rules(sg_handle* h, const sg_local_flow_rule* rules, uint32_t n, int32_t n_origins,
                              int32_t n_contexts);
 
+/* ---- AuthoritySlot: origin black and white lists ----
+ *   sg_local_load_authority_rules ← AuthorityRuleManager.loadRules (loadAuthorityConf, AuthorityRuleManager.java
+ *     :108-139): replaces every authority rule (n == 0 clears them). Rules are taken in array order; a rule with
+ *     strategy < 0 or no limitApp item is invalid and ignored (isValidRule :147-150), and the first valid rule of a
+ *     resource wins: later ones are ignored as the reference ignores "redundant" rules. Returns the number of rules
+ *     kept (>= 0) or an error; a failed load leaves the previous rules in force. Statistics, nodes, flow controllers
+ *     and param tables are kept. sg_local_load_rules (fresh resources) drops the authority rules as it drops the
+ *     flow rules.
+ *     The check (AuthorityRuleChecker.passCheck, AuthorityRuleChecker.java:30-65) per entry: an entry without origin
+ *     (origin 0) passes; SG_AUTHORITY_BLACK blocks an origin that equals one of the rule's items, SG_AUTHORITY_WHITE
+ *     one that equals none; any other strategy >= 0 never blocks but still holds the resource's single rule.
+ *     origins[] holds the limitApp items as the caller's origin ids: any id >= 1, an id above the handle's origin
+ *     count simply never matches (the id a shim gives a limitApp item that is not in its origin dictionary: a white
+ *     list of unknown names still blocks every origin). An id <= 0, a range outside origins[0 .. n_origin_ids) or a
+ *     resource index >= the resource count is SG_E_INVAL, as is a call before sg_local_load_rules. n_origins: as in
+ *     sg_local_load_flow_rules; the handle's origin count becomes the larger of the two and never shrinks.
+ *     AuthoritySlot (@Spi order -6000, AuthoritySlot.java:39-43) runs after ClusterBuilderSlot and before
+ *     ParamFlowSlot, FlowSlot and DegradeSlot: a rejected entry (SG_LOCAL_BLOCK_AUTHORITY, wait_ms 0, whatever its
+ *     prioritized flag) has created the resource's ClusterNode, its origin node and its context's DefaultNode and
+ *     adds BLOCK to them (StatisticSlot.java:96-116), and reaches nothing else: no param metric, token or thread
+ *     count, no flow controller (warm-up sync, latestPassedTime, occupied window), no token of the embedded server,
+ *     no breaker. It raises no thread count and has no exit event. */
+#define SG_AUTHORITY_WHITE 0
+#define SG_AUTHORITY_BLACK 1
+#define SG_LOCAL_BLOCK_AUTHORITY 5   /* AuthorityException; wait_ms 0 */
+typedef struct sg_authority_rule {
+    uint32_t resource;      /* resource index (sg_local_load_rules order)                      */
+    int32_t  strategy;      /* RuleConstant.AUTHORITY_*; < 0: invalid, ignored                 */
+    uint32_t origin_begin;  /* the limitApp items: origins[origin_begin .. + origin_count)     */
+    uint32_t origin_count;  /* 0: blank limitApp, invalid, ignored                             */
+} sg_authority_rule;
+int sg_local_load_authority_rules(sg_handle* h, const sg_authority_rule* rules, uint32_t n, const int32_t* origins,
+                                  uint32_t n_origin_ids, int32_t n_origins);
+
 /* ---- the whole slot chain in one batch (the ProcessorSlot chain's SPI order, Constants.java:76-83 and
- * ParamFlowSlot @Spi(order = -3000)): StatisticSlot.entry around ParamFlowSlot → FlowSlot → DegradeSlot.
+ * ParamFlowSlot @Spi(order = -3000)): StatisticSlot.entry around AuthoritySlot → ParamFlowSlot → FlowSlot →
+ * DegradeSlot. SystemSlot (between AuthoritySlot and ParamFlowSlot in the reference) is not part of it: it reads
+ * Constants.ENTRY_NODE, which depends on every earlier decision of every resource.
  *   sg_slot_decide_batch ← SphU.entry(resource, count, prioritized, args...) / Entry.exit(count, args...) for a
- *     time-ordered batch. Per entry: ParamFlowSlot.checkFlow (the param rules sg_pslot_load_rules loaded for the
+ *     time-ordered batch. Per entry: AuthoritySlot (the authority rules above; an AuthorityException ends the chain
+ *     before any other slot, SG_LOCAL_BLOCK_AUTHORITY); ParamFlowSlot.checkFlow (the param rules sg_pslot_load_rules loaded for the
  *     resource, args of the event; args_null or no rules: nothing) — a ParamFlowException ends the chain
  *     (SG_LOCAL_BLOCK_PARAM, wait_ms = the index of the param rule that threw); FlowSlot (the flow rules above);
  *     DegradeSlot; then StatisticSlot (StatisticSlot.java:55-122): a pass raises curThreadNum and PASS on the
@@ -846,6 +884,9 @@ int sg_node_conc_read_state(sg_node* nd, uint32_t key, int32_t* now_calls, uint6
  *                                   batch every rule set is accepted. n_contexts >= 1 starts before the node's first
  *                                   batch (SG_E_UNSUPPORTED after it). A shard that fails midway (allocation, device)
  *                                   leaves the earlier shards on the new rules: load again.
+ *   sg_node_local_load_authority_rules ← sg_local_load_authority_rules on the front (validation: a refused load
+ *                                   reaches no shard), then on every shard; returns the rules kept. Routing and owners
+ *                                   do not change: a rejected entry is an ordinary event of its resource's owner.
  *   sg_node_local_set_entry_types ← sg_local_set_entry_types on every shard
  *   sg_node_local_owner_of        owner shard of a resource
  *   sg_node_local_decide_batch(_host) ← sg_local_decide_batch over the node, synchronous. Before any shard is touched the
@@ -889,6 +930,8 @@ int sg_node_conc_read_state(sg_node* nd, uint32_t key, int32_t* now_calls, uint6
 int sg_node_local_load_rules(sg_node* nd, const sg_local_config* cfg, const sg_local_rule* rules, uint32_t n);
 int sg_node_local_load_flow_rules(sg_node* nd, const sg_local_flow_rule* rules, uint32_t n, int32_t n_origins,
                                   int32_t n_contexts);
+int sg_node_local_load_authority_rules(sg_node* nd, const sg_authority_rule* rules, uint32_t n, const int32_t* origins,
+                                       uint32_t n_origin_ids, int32_t n_origins);
 int sg_node_local_set_entry_types(sg_node* nd, const uint8_t* inbound, uint32_t n);
 int sg_node_local_owner_of(const sg_node* nd, uint32_t resource, uint32_t* shard);
 int sg_node_local_decide_batch(sg_node* nd, const sg_local_event* ev, uint64_t n, sg_local_result* out, void* stream);

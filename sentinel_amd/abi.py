@@ -163,6 +163,10 @@ CLUSTER_CLIENT, CLUSTER_SERVER, CLUSTER_NOT_STARTED = 0, 1, -1
 SLOT_EXT_DTYPE = np.dtype([("context", "<u4"), ("arg_begin", "<u4"), ("arg_count", "<u4"), ("args_null", "<i4")],
                           align=True)
 LOCAL_BLOCK_PARAM = 4
+LOCAL_BLOCK_AUTHORITY = 5  # AuthorityException (sg_local_load_authority_rules)
+AUTHORITY_WHITE, AUTHORITY_BLACK = 0, 1
+AUTHORITY_RULE_DTYPE = np.dtype([("resource", "<u4"), ("strategy", "<i4"), ("origin_begin", "<u4"),
+                                 ("origin_count", "<u4")], align=True)
 ENTRY_NODE_RESOURCE = 0xFFFFFFFF  # sg_local_metrics rows of Constants.ENTRY_NODE
 CONTROL_DEFAULT, CONTROL_WARM_UP, CONTROL_RATE_LIMITER, CONTROL_WARM_UP_RATE_LIMITER = 0, 1, 2, 3
 LIMIT_APP_DEFAULT, LIMIT_APP_OTHER = 0, -1

@@ -208,6 +208,8 @@ struct sg_handle {
     std::vector<int64_t> l_rule_slot; // loaded flow rule i → its LCtl index, -2 stateless fast-path rule, -1 ignored
     DevBuf<LFlowRule> d_lfrules;
     DevBuf<LCtl> d_lctl;
+    DevBuf<LAuth> d_lauth;            // [K] AuthoritySlot's rule of each resource, null = no authority rule kept
+    DevBuf<int32_t> d_lauth_ids;      // its lists' origin ids above 64
     DevBuf<int64_t> d_llast_fetch;    // [K] StatisticNode.lastFetchTime
     DevBuf<LRule> d_lrules;
     DevBuf<LHead> d_lhead;
@@ -227,6 +229,7 @@ struct sg_handle {
         DevBuf<CxSide> cxside;        // [max_batch] LArgs::cxside (with pslot)
         DevBuf<uint32_t> cxw_next;    // LArgs::cxw_next
         DevBuf<uint32_t> cx_list;     // [max_batch + 1] LArgs::cx_list, then cx_count (cx resources loaded)
+        DevBuf<uint8_t> auth_rej;     // [max_batch] LArgs::auth_rej (authority rules loaded)
     };
     LocalWs lws[2];
     // node pool (origin nodes, context DefaultNodes; created by the batches, kept across flow-rule reloads)
@@ -2948,6 +2951,8 @@ int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local
     h->d_lrules.reset();
     h->d_lfrules.reset();
     h->d_lctl.reset();
+    h->d_lauth.reset();  // fresh resources: the authority rules go as the flow rules do
+    h->d_lauth_ids.reset();
     h->d_lhead.reset();
     h->d_lsec.reset();
     h->d_lbor.reset();
@@ -3393,6 +3398,15 @@ int local_args(sg_handle* h, const LocalBufs& b, const sg_local_event* ev, const
         L.lim_ring = h->d_lim_ring;
         for (int j = 0; j < kMaxLim; ++j) L.lim_qps[j] = h->lim_qps[j];
         L.c3_last_ts = h->d_last_ts;
+    }
+    // AuthoritySlot: only an event with an origin id can be rejected, and a handle with no origin id declared
+    // refuses such events (so the pipelined path, which needs l_n_origins == 0, never carries the table)
+    if (h->d_lauth && h->l_n_origins > 0) {
+        if (!b.lw->auth_rej && !b.lw->auth_rej.alloc_bytes(h->cfg.max_batch))
+            return fail(h, SG_E_NOMEM, "authority verdicts of the local batch");
+        L.auth = h->d_lauth;
+        L.auth_ids = h->d_lauth_ids;
+        L.auth_rej = b.lw->auth_rej;
     }
     L.flags = b.lw->flags;
     L.cxw_next = b.lw->cxw_next;
@@ -4089,6 +4103,39 @@ int sg_local_load_flow_rules(sg_handle* h, const sg_local_flow_rule* rules, uint
     return kept;
 }
 
+// AuthorityRuleManager.loadRules: the rule compiler is authority_rules.h (host only); the device table is swapped in
+// only after a successful upload, and nothing else of the handle is touched (statistics, nodes, controllers and param
+// tables stay).
+int sg_local_load_authority_rules(sg_handle* h, const sg_authority_rule* rules, uint32_t n, const int32_t* origins,
+                                  uint32_t n_origin_ids, int32_t n_origins) {
+    if (!h || (!rules && n) || (!origins && n_origin_ids)) return SG_E_INVAL;
+    if (!h->d_llast_ts) return fail(h, SG_E_INVAL, "sg_local_load_rules first");
+    if (n_origins < 0) return fail(h, SG_E_INVAL, "n_origins < 0");
+    drain_async(h);  // batches on the pipeline decide under the rules they were enqueued with
+    const uint32_t K = (uint32_t)h->ltab.size();
+    std::vector<LAuth> tab;
+    std::vector<int32_t> ids;
+    const int kept = authority_compile(rules, n, origins, n_origin_ids, K, tab, ids);
+    if (kept < 0)
+        return fail(h, kept, "an authority rule's resource index, an origin id <= 0 or an origin range outside origins[]");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    DevBuf<LAuth> d_tab;
+    DevBuf<int32_t> d_ids;
+    if (kept > 0) {
+        if (!d_tab.alloc(K) || (!ids.empty() && !d_ids.alloc(ids.size())))
+            return fail(h, SG_E_NOMEM, "authority rule allocation");
+        hipError_t e = hipMemcpy(d_tab, tab.data(), sizeof(LAuth) * K, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !ids.empty())
+            e = hipMemcpy(d_ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(h, SG_E_DEVICE, std::string("authority rule upload: ") + hipGetErrorString(e));
+    }
+    h->d_lauth = std::move(d_tab);
+    h->d_lauth_ids = std::move(d_ids);
+    if (n_origins > h->l_n_origins) h->l_n_origins = n_origins;  // never shrinks (the ids keep their meaning)
+    return kept;
+}
+
 // ------------------------------------------------------------------------ concurrent cluster tokens
 
 namespace {
@@ -4672,6 +4719,8 @@ struct sg_node {
     std::vector<sg_local_rule> l_rules;
     std::vector<sg_local_flow_rule> l_frules;   // the flow rules in force (the front's rollback)
     bool l_has_frules = false;
+    std::vector<sg_authority_rule> l_arules;    // the authority rules in force and their origin ids (the same)
+    std::vector<int32_t> l_aorigins;
     int32_t l_n_origins = 0, l_n_contexts = 0;
     std::vector<uint32_t> l_owner;      // [K] owner shard of each resource
     DevBuf<uint8_t> d_l_owner;          // the same on devices[0]
@@ -5878,6 +5927,8 @@ void node_local_front_rollback(sg_node* nd) {
     if (nd->l_has_frules)
         (void)sg_local_load_flow_rules(f, nd->l_frules.data(), (uint32_t)nd->l_frules.size(), nd->l_n_origins,
                                        nd->l_n_contexts);
+    (void)sg_local_load_authority_rules(f, nd->l_arules.data(), (uint32_t)nd->l_arules.size(), nd->l_aorigins.data(),
+                                        (uint32_t)nd->l_aorigins.size(), nd->l_n_origins);
 }
 
 // k_merge_* over `n` raw rows on devices[0] into d_out (device); *n_out rows. Waits for the result.
@@ -5999,6 +6050,8 @@ int sg_node_local_load_rules(sg_node* nd, const sg_local_config* cfg, const sg_l
     nd->l_rules.assign(rules, rules + n);
     nd->l_frules.clear();
     nd->l_has_frules = false;
+    nd->l_arules.clear();
+    nd->l_aorigins.clear();
     nd->l_n_origins = nd->l_n_contexts = 0;
     nd->l_last_ts = -1;
     nd->l_batches = 0;
@@ -6063,6 +6116,25 @@ int sg_node_local_load_flow_rules(sg_node* nd, const sg_local_flow_rule* rules, 
     nd->l_has_frules = true;
     nd->l_n_origins = n_origins;
     nd->l_n_contexts = n_contexts;
+    return kept;
+}
+
+int sg_node_local_load_authority_rules(sg_node* nd, const sg_authority_rule* rules, uint32_t n, const int32_t* origins,
+                                       uint32_t n_origin_ids, int32_t n_origins) {
+    if (!nd || (!rules && n) || (!origins && n_origin_ids)) return SG_E_INVAL;
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    node_drain(nd);
+    // the front first (validation: a refused load reaches no shard), then every shard. Authority rules form no key
+    // groups, so no resource changes its owner.
+    const int kept = sg_local_load_authority_rules(nd->front, rules, n, origins, n_origin_ids, n_origins);
+    if (kept < 0) return node_child(nd, nd->front, kept);
+    for (sg_handle* h : nd->shards) {
+        const int rc = sg_local_load_authority_rules(h, rules, n, origins, n_origin_ids, n_origins);
+        if (rc < 0) return node_child(nd, h, rc);
+    }
+    nd->l_arules.assign(rules, rules + n);
+    nd->l_aorigins.assign(origins, origins + n_origin_ids);
+    if (n_origins > nd->l_n_origins) nd->l_n_origins = n_origins;
     return kept;
 }
 

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/sentinel_gpu.h"
+#include "authority_rules.h"
 #include "search_dev.h"
 
 namespace sg {
@@ -743,6 +744,10 @@ struct LArgs {
     uint64_t* pslot;          // [n] or null: k_local_prep's ParamFlowSlot lookup of each entry of a resource with one
                               // QPS param rule (kPsNoCheck / kPsEarlyFail / kPsUnknown, else the (rule, value) slot)
     CxSide* cxside;           // [n] or null: k_lcx_side's words of the sorted records of the cx resources
+    // AuthoritySlot (null auth: no authority rule loaded, or no origin id declared — nothing can be rejected)
+    const LAuth* auth;        // [K] each resource's black / white list (authority_rules.h)
+    const int32_t* auth_ids;  // the lists' origin ids above 64, sorted per resource
+    uint8_t* auth_rej;        // [n] k_local_prep's verdict of each event: 1 = an entry AuthoritySlot rejects
     // the embedded token server (ClusterStateManager SERVER, emb = 1): the handle's cluster flow state
     int32_t emb;
     const Rule* c3_rules;

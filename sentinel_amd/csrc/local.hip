@@ -214,12 +214,33 @@ __global__ void __launch_bounds__(256) k_local_prep(LArgs a) {
             if (kind == 0 && (e.resource >> 31)) atomicOr(a.flags, kLFlagPrio);
             if (kind == 0 && e.count <= 0) atomicOr(a.flags, kLFlagNonPos);
         }
+        // AuthoritySlot (@Spi order -6000, AuthoritySlot.java:39-43 → AuthorityRuleChecker.passCheck :30-65): a pure
+        // function of (resource, origin), decided here once per entry; the cx walkers read the byte. An empty origin
+        // passes; a black list blocks a listed origin, a white list one that is not listed.
+        bool rejected = false;
+        if (a.auth) {
+            if (res < a.K && e.kind == SG_LOCAL_ENTRY && e.origin > 0) {
+                const LAuth w = a.auth[res];
+                const uint32_t state = w.cs >> 30;
+                if (state == kAuthWhite || state == kAuthBlack) {
+                    const bool contain = (uint32_t)e.origin <= kAuthMaskIds
+                                             ? ((w.mask >> (e.origin - 1)) & 1ull) != 0
+                                             : sorted_has(a.auth_ids + w.begin, w.cs & kAuthCount, e.origin);
+                    rejected = contain == (state == kAuthBlack);
+                }
+            }
+            a.auth_rej[i] = rejected ? 1 : 0;
+        }
         // ParamFlowSlot lookup of an entry of a resource with one QPS param rule (resolved paramIdx, local): the
         // walkers' dead periods read the (rule, value) slot instead of the arguments (ParamFlowChecker.passSingleValue
-        // Check's early exits and the CacheMap putIfAbsent happen at the check: every such entry reaches it first)
+        // Check's early exits and the CacheMap putIfAbsent happen at the check: every such entry reaches it first).
+        // An entry AuthoritySlot rejects never reaches ParamFlowSlot (no initParamMetricsFor, no CacheMap insert): it
+        // gets the "no check" code, which is all a dead period needs to treat it right — BLOCK counts only.
         if (a.pslot) {
             uint64_t code = kPsUnknown;
-            if (res < a.K && e.kind == SG_LOCAL_ENTRY && a.rules[res].ps && a.has_ps) {
+            if (rejected) {
+                code = kPsNoCheck;
+            } else if (res < a.K && e.kind == SG_LOCAL_ENTRY && a.rules[res].ps && a.has_ps) {
                 const uint32_t rb = a.ps.res_begin[res];
                 if (a.ps.res_begin[res + 1] == rb + 1) {
                     const uint32_t ri = a.ps.res_rules[rb];
@@ -254,8 +275,10 @@ __global__ void __launch_bounds__(256) k_local_prep(LArgs a) {
             a.pslot[i] = code;
         }
         // default result: FlowException for entries (the common outcome of a saturated resource; the walkers
-        // write every other outcome), plain 0 for exits and events of unknown resources
-        const uint32_t dst = (res < a.K && e.kind == SG_LOCAL_ENTRY) ? SG_LOCAL_BLOCK_FLOW : SG_LOCAL_PASS;
+        // write every other outcome), AuthorityException for an entry AuthoritySlot rejects (the dead periods leave
+        // it in place), plain 0 for exits and events of unknown resources
+        const uint32_t dst = rejected ? SG_LOCAL_BLOCK_AUTHORITY
+                                      : (res < a.K && e.kind == SG_LOCAL_ENTRY) ? SG_LOCAL_BLOCK_FLOW : SG_LOCAL_PASS;
         st_stream(reinterpret_cast<uint64_t*>(a.out + i), (uint64_t)dst);  // {status, wait_ms 0}
         st_stream(a.rec + i, rec);
         if (a.hist0) ldig[it * 256 + threadIdx.x] = (uint16_t)((uint32_t)(rec >> a.kshift) & dmask);
@@ -1496,8 +1519,13 @@ struct CxNodes<true> {
                                : *::new (slots + kCxNdBytes) LNode(a, LNode::None{})) {}
 };
 
+// An entry AuthoritySlot rejects (LArgs::auth_rej; the slot sits before ParamFlowSlot, FlowSlot and DegradeSlot) runs
+// none of the checks: no param rule, no flow controller, no embedded-server token, no breaker, no occupy path and no
+// onPass — only StatisticSlot's BlockException updates (StatisticSlot.java:96-116), status SG_LOCAL_BLOCK_AUTHORITY,
+// wait 0 whatever its prioritized flag. Returns false for such an entry (the caller starts no dead period on it: no
+// controller was synced), true otherwise.
 template <bool W>
-__device__ void cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd, const LEvent& e, int64_t t, int origin,
+__device__ bool cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd, const LEvent& e, int64_t t, int origin,
                          int ctx, const sg_slot_ext* x, uint32_t qs, uint32_t qm, uint2 nodes, unsigned char* slots) {
     const LRule& R = nd.R;
     const uint32_t on_idx = nodes.x, cn_idx = nodes.y;
@@ -1506,8 +1534,9 @@ __device__ void cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd,
     CxNodes<W> nn(a, nd, on_idx, cn_idx, slots);
     LNode& on = nn.on;
     LNode& cn = nn.cn;
-    const bool params = R.ps && a.has_ps && x && !x->args_null;
-    int32_t status = SG_LOCAL_PASS;
+    const bool rejected = a.auth_rej && a.auth_rej[e.idx];
+    const bool params = !rejected && R.ps && a.has_ps && x && !x->args_null;
+    int32_t status = rejected ? SG_LOCAL_BLOCK_AUTHORITY : SG_LOCAL_PASS;
     int64_t wait = 0;
     if (params) {  // ParamFlowSlot (@Spi order -3000): before FlowSlot
         // the resource's one QPS rule, its (rule, value) slot looked up by k_local_prep (LArgs::pslot), else every rule
@@ -1648,6 +1677,7 @@ __device__ void cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd,
     lstore(a, e.idx, status, wait > INT32_MAX ? INT32_MAX : (int32_t)wait);
     if (have_on) on.finish();
     if (have_cn) cn.finish();
+    return !rejected;
 }
 
 // One exit of a cx resource: StatisticSlot.exit (:124-165) on the ClusterNode (+ DegradeSlot.exit), the origin node
@@ -1887,8 +1917,8 @@ __global__ void __launch_bounds__(256) k_lwalk_cx(LArgs a_arg, BatchArgs sg) {
             if (e.kind != SG_LOCAL_ENTRY) nd.at(qs, qm);
             const uint2 nodes = event_nodes(a, e.idx);
             if (e.kind == SG_LOCAL_ENTRY) {
-                cx_entry<false>(a, bndp, nd, e, le.ts_ms, le.origin, ctx, x, qs, qm, nodes, nullptr);
-                if (dead_ok && !dead && nd.cs.q == qs && nd.cm.q == qm && cxw_saturated(a, nd)) {
+                const bool decided = cx_entry<false>(a, bndp, nd, e, le.ts_ms, le.origin, ctx, x, qs, qm, nodes, nullptr);
+                if (decided && dead_ok && !dead && nd.cs.q == qs && nd.cm.q == qm && cxw_saturated(a, nd)) {
                     dead = true;
                     dqs = qs;
                     dqm = qm;
@@ -1923,18 +1953,16 @@ __global__ void __launch_bounds__(256) k_lwalk_cx(LArgs a_arg, BatchArgs sg) {
 // collection arguments keep the serial step.
 
 // The wave walker's serial step as a called function: its registers (the entry's origin / context nodes, the
-// controllers) stay out of the walker's loop, whose dead-period chunks then run without spilling.
-__device__ __noinline__ bool cxw_step(const LArgs& a, const uint32_t* const* bndp, LNode& nd, const LEvent& es,
-                                      int64_t te, int64_t ce, int og, const sg_slot_ext* xp, uint32_t qs0, uint32_t qm0,
-                                      uint2 nn, unsigned char* slots) {
+// controllers) stay out of the walker's loop, whose dead-period chunks then run without spilling. Returns 0 for an
+// exit, 1 for an entry the chain decided, 2 for an entry AuthoritySlot rejected.
+__device__ __noinline__ int cxw_step(const LArgs& a, const uint32_t* const* bndp, LNode& nd, const LEvent& es,
+                                     int64_t te, int64_t ce, int og, const sg_slot_ext* xp, uint32_t qs0, uint32_t qm0,
+                                     uint2 nn, unsigned char* slots) {
     const int ctx = xp ? (int)xp->context : 0;
-    if (es.kind == SG_LOCAL_ENTRY) {
-        cx_entry<true>(a, bndp, nd, es, te, og, ctx, xp, qs0, qm0, nn, slots);
-        return true;
-    }
+    if (es.kind == SG_LOCAL_ENTRY) return cx_entry<true>(a, bndp, nd, es, te, og, ctx, xp, qs0, qm0, nn, slots) ? 1 : 2;
     nd.at(qs0, qm0);
     cx_exit<true>(a, bndp, nd, es, te, ce, og, ctx, xp, qs0, qm0, nn, slots);
-    return false;
+    return 0;
 }
 
 // Whether resource k's periods can go dead; *prule = its one QPS ParamFlowRule (-1: none).
@@ -2384,7 +2412,7 @@ __device__ void cx_wave(const LArgs& a, const BatchArgs& sg, const uint32_t* con
             xe.args_null = bcast32(xx.args_null, q);
             const uint2 nn = make_uint2((uint32_t)bcast32((int)nodes.x, q), (uint32_t)bcast32((int)nodes.y, q));
             const sg_slot_ext* xp = a.ext ? &xe : nullptr;
-            const bool entry = cxw_step(a, bndp, nd, es, te, ce, og, xp, qs0, qm0, nn, slots);
+            const int entry = cxw_step(a, bndp, nd, es, te, ce, og, xp, qs0, qm0, nn, slots);
             if (dg) {
                 if (entry) ++c_sent;
                 else ++c_sexit;
@@ -2559,9 +2587,9 @@ __device__ void cx_wave(const LArgs& a, const BatchArgs& sg, const uint32_t* con
             const int rend = diff ? __builtin_ctzll(diff) : nact;
             if (dead && (qs0 != dead_qs || qm0 != dead_qm)) end_dead();  // the dead period ended
             while (p < rend && !dead) {
-                const bool entry = step(p, qs0, qm0);
+                const int entry = step(p, qs0, qm0);
                 ++p;
-                if (entry && dead_ok && nd.cs.q == qs0 && nd.cm.q == qm0 && cxw_saturated(a, nd)) {
+                if (entry == 1 && dead_ok && nd.cs.q == qs0 && nd.cm.q == qm0 && cxw_saturated(a, nd)) {
                     dead = true;
                     dead_qs = qs0;
                     dead_qm = qm0;

@@ -46,6 +46,17 @@ __device__ __forceinline__ uint64_t gallop_search(uint64_t lo, uint64_t hi, Pred
     return search64(b0, b1 < hi ? b1 : hi, pred, lane);
 }
 
+// One lane's own search: is v in the sorted a[0 .. n)? (AuthoritySlot's origin ids above 64: a handful per resource.)
+__device__ __forceinline__ bool sorted_has(const int32_t* a, uint32_t n, int32_t v) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && a[lo] == v;
+}
+
 // sum / intervalInSecond (LeapArray averages: ClusterMetric.getAvg, StatisticNode.passQps, …) as Java computes it.
 // For a power-of-two interval (1 s, 2 s, 0.5 s, …) the quotient is the product with the exact reciprocal, built from
 // the exponent bits; the fp64 division sequence (~13 instructions a record on the walkers' hot path) runs only

@@ -42,7 +42,7 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_node_local_load_rules", "sg_node_local_load_flow_rules", "sg_node_local_set_entry_types",
            "sg_node_local_owner_of", "sg_node_local_decide_batch", "sg_node_local_decide_batch_host",
            "sg_node_local_read_state", "sg_node_local_metrics", "sg_node_local_metrics_device",
-           "sg_node_local_merge_rows"]
+           "sg_node_local_merge_rows", "sg_local_load_authority_rules", "sg_node_local_load_authority_rules"]
 
 _lib = None
 
@@ -170,6 +170,8 @@ def load_library():
         "sg_node_conc_read_state": (C.c_int, [vp, u32, C.POINTER(C.c_int32), C.POINTER(u64)]),
         "sg_node_local_load_rules": (C.c_int, [vp, vp, vp, u32]),
         "sg_node_local_load_flow_rules": (C.c_int, [vp, vp, u32, C.c_int32, C.c_int32]),
+        "sg_local_load_authority_rules": (C.c_int, [vp, vp, u32, vp, u32, C.c_int32]),
+        "sg_node_local_load_authority_rules": (C.c_int, [vp, vp, u32, vp, u32, C.c_int32]),
         "sg_node_local_set_entry_types": (C.c_int, [vp, vp, u32]),
         "sg_node_local_owner_of": (C.c_int, [vp, u32, C.POINTER(C.c_uint32)]),
         "sg_node_local_decide_batch": (C.c_int, [vp, vp, u64, vp, vp]),
@@ -340,6 +342,15 @@ class NodeEngine:
         """sg_node_local_load_flow_rules; returns the number of rules kept."""
         rules = np.ascontiguousarray(rules, dtype=abi.LOCAL_FLOW_RULE_DTYPE).reshape(-1)
         rc = self._L.sg_node_local_load_flow_rules(self.h, abi.ptr(rules), len(rules), n_origins, n_contexts)
+        self._check(min(rc, 0))
+        return rc
+
+    def local_load_authority_rules(self, rules: np.ndarray, origins, n_origins=0) -> int:
+        """sg_node_local_load_authority_rules; returns the number of rules kept."""
+        rules = np.ascontiguousarray(rules, dtype=abi.AUTHORITY_RULE_DTYPE).reshape(-1)
+        origins = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
+        rc = self._L.sg_node_local_load_authority_rules(self.h, abi.ptr(rules), len(rules), abi.ptr(origins),
+                                                        len(origins), n_origins)
         self._check(min(rc, 0))
         return rc
 
@@ -876,6 +887,16 @@ class FlowEngine:
         self._check(min(rc, 0))
         return rc
 
+    def local_load_authority_rules(self, rules: np.ndarray, origins, n_origins=0) -> int:
+        """AuthorityRuleManager.loadRules for the local chain (sg_local_load_authority_rules): `rules` index their
+        limitApp items in `origins` (origin ids >= 1); returns the number of rules kept."""
+        rules = np.ascontiguousarray(rules, dtype=abi.AUTHORITY_RULE_DTYPE).reshape(-1)
+        origins = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
+        rc = self._L.sg_local_load_authority_rules(self.h, abi.ptr(rules), len(rules), abi.ptr(origins), len(origins),
+                                                   n_origins)
+        self._check(min(rc, 0))
+        return rc
+
     def local_set_entry_types(self, inbound):
         """EntryType of each resource's entries (1 = IN: counted by Constants.ENTRY_NODE); default OUT."""
         v = np.ascontiguousarray(inbound, dtype=np.uint8)
@@ -886,8 +907,8 @@ class FlowEngine:
         self._check(self._L.sg_local_set_cluster_state(self.h, state))
 
     def slot_decide_host(self, ev, ext, args, values) -> np.ndarray:
-        """The whole slot chain (sg_slot_decide_batch_host): StatisticSlot around ParamFlowSlot → FlowSlot →
-        DegradeSlot for HOST events with their context / argument records (ext may be None)."""
+        """The whole slot chain (sg_slot_decide_batch_host): StatisticSlot around AuthoritySlot → ParamFlowSlot →
+        FlowSlot → DegradeSlot for HOST events with their context / argument records (ext may be None)."""
         ev = np.ascontiguousarray(ev, dtype=abi.LOCAL_EVENT_DTYPE).reshape(-1)
         out = np.zeros(len(ev), abi.LOCAL_RES_DTYPE)
         if len(ev) == 0:
