@@ -876,6 +876,9 @@ int sg_node_conc_read_state(sg_node* nd, uint32_t key, int32_t* now_calls, uint6
  * devices[0], the shards in SG_CLUSTER_NOT_STARTED.
  *   sg_node_local_load_rules      ← sg_local_load_rules on the front, then on every shard: fresh statistics, so owners
  *                                   may change freely. A shard that fails leaves the local chain unloaded (load again).
+ *                                   It also clears the node's param rules (sg_node_pslot_load_rules) on the front and on
+ *                                   every shard — a param rule's state lives on its resource's owner, which may move —
+ *                                   where one handle's sg_local_load_rules keeps them: load them again after it.
  *   sg_node_local_load_flow_rules ← sg_local_load_flow_rules (returns the rules kept). The resources keep their
  *                                   statistics, which live on their owner, so after the node has decided a local batch no
  *                                   resource may move: rules whose key groups (RELATE references) give any resource
@@ -924,9 +927,44 @@ int sg_node_conc_read_state(sg_node* nd, uint32_t key, int32_t* now_calls, uint6
  *                                   or SG_ENTRY_NODE_RESOURCE — else SG_E_INVAL and d_out untouched. More rows than cap:
  *                                   SG_E_CAPACITY, *n_out = the rows needed, d_out untouched. Runs on `stream` and waits
  *                                   for it.
- * Out of scope here: sg_slot_ext / ParamFlowSlot arguments over the node (every event is in context 0 with null
- * args), the embedded token server over the node, a pipelined sg_node_local_enqueue. Cross-device shards are built
- * (peer copies, per-shard buffers) and unmeasured on hardware, as the rest of the node handle. */
+ *   sg_node_pslot_load_rules      ← sg_pslot_load_rules on the front (validation: a refused load reaches no shard and the
+ *                                   front goes back to the rules in force), then on every shard: the whole rule set under
+ *                                   the node's rule and resource indices. SG_E_INVAL before sg_node_local_load_rules or
+ *                                   when n_resources differs from the node's resource count. Param rules form no key
+ *                                   groups on a node that is no embedded server, so no resource changes its owner; a
+ *                                   rule's state (token buckets, throttle times, thread counts, a resolved negative
+ *                                   paramIdx) lives on the owner of its resource. A flow-rule reload refused by the
+ *                                   front leaves the front on these rules too. A shard that fails midway (allocation,
+ *                                   device) leaves the earlier shards on the new rules: load again.
+ *   sg_node_slot_decide_batch(_host) ← sg_slot_decide_batch over the node, synchronous; sg_node_local_decide_batch is
+ *                                   this call with ext = NULL, and the two share the node's last timestamp and batch
+ *                                   count. Besides that call's refusals, before any shard is touched: a context >=
+ *                                   max(n_contexts, 1), and — with param rules on the node, for an event with args_null
+ *                                   == 0 of a resource below the resource count — arg_begin + arg_count > n_args or an
+ *                                   argument's value_begin + m > n_values (m: value_count of a COLLECTION, 1 of a VALUE,
+ *                                   0 of a null argument; 64-bit sums; a record outside [0, n_args) is never read):
+ *                                   SG_E_INVAL. n_args or n_values >= 2^32: SG_E_CAPACITY. Each event's ext record moves
+ *                                   with it. A shard on devices[0] reads the caller's args and values in place (ranges
+ *                                   may be shared between events and may overlap: nothing is copied, no index changes).
+ *                                   A shard on another device gets its slice's own arrays, compacted on devices[0] and
+ *                                   peer-copied with the slice: with param rules on the node, every event of the slice
+ *                                   with args_null == 0 and a resource below the resource count brings its arg records
+ *                                   (value_begin rebased, value_count and kind as given) and their values, at the
+ *                                   exclusive scans over slice order, its ext.arg_begin rebased; a range several events
+ *                                   share is copied once per event. Without param rules no argument is copied and the
+ *                                   shard gets null arrays (one handle never reads them then). An event of a resource
+ *                                   not below the resource count goes to shard 0 and is answered as one handle answers
+ *                                   it; its argument range is neither validated nor read. A slice whose compacted args
+ *                                   or values reach 2^32: SG_E_CAPACITY; a buffer that cannot grow: SG_E_NOMEM — both
+ *                                   before any shard runs. Test aid: env SG_NODE_COMPACT_ARGS=1 (read at sg_node_create)
+ *                                   compacts for every shard, so one GPU exercises that path. Failures inside a shard:
+ *                                   as sg_node_local_decide_batch.
+ *   sg_node_local_read_origin_state, sg_node_local_read_context_state, sg_node_local_read_controller,
+ *   sg_node_pslot_thread_count, sg_node_pslot_param_idx, sg_node_param_read_state
+ *                                 ← the single-handle calls (same arguments, layouts and return values; the node's rule
+ *                                   and resource indices) on the owner of the resource, or of the rule's resource.
+ * Out of scope here: the embedded token server over the node, a pipelined sg_node_local_enqueue. Cross-device shards
+ * are built (peer copies, per-shard buffers) and unmeasured on hardware, as the rest of the node handle. */
 int sg_node_local_load_rules(sg_node* nd, const sg_local_config* cfg, const sg_local_rule* rules, uint32_t n);
 int sg_node_local_load_flow_rules(sg_node* nd, const sg_local_flow_rule* rules, uint32_t n, int32_t n_origins,
                                   int32_t n_contexts);
@@ -941,6 +979,22 @@ int sg_node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* out, uint
 int sg_node_local_metrics_device(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, uint64_t cap, uint64_t* n_rows);
 int sg_node_local_merge_rows(sg_node* nd, const sg_metric_node* d_rows, uint64_t n, sg_metric_node* d_out, uint64_t cap,
                              uint64_t* n_out, void* stream);
+int sg_node_pslot_load_rules(sg_node* nd, const sg_pslot_rule* rules, uint32_t n, const sg_param_hot_item* hot,
+                             uint32_t n_hot, uint32_t n_resources);
+int sg_node_slot_decide_batch(sg_node* nd, const sg_local_event* ev, const sg_slot_ext* ext, uint64_t n,
+                              const sg_pslot_arg* args, uint64_t n_args, const uint64_t* values, uint64_t n_values,
+                              sg_local_result* out, void* stream);
+int sg_node_slot_decide_batch_host(sg_node* nd, const sg_local_event* ev, const sg_slot_ext* ext, uint64_t n,
+                                   const sg_pslot_arg* args, uint64_t n_args, const uint64_t* values, uint64_t n_values,
+                                   sg_local_result* out);
+int sg_node_local_read_origin_state(sg_node* nd, uint32_t res, int32_t origin, int64_t* second, int64_t* borrow,
+                                    int64_t* minute, int64_t* head);
+int sg_node_local_read_context_state(sg_node* nd, uint32_t res, int32_t context, int64_t* second, int64_t* borrow,
+                                     int64_t* minute, int64_t* head);
+int sg_node_local_read_controller(sg_node* nd, uint32_t rule, int64_t* state3);
+int sg_node_pslot_thread_count(sg_node* nd, uint32_t resource, int32_t param_idx, uint64_t value, int64_t* count);
+int sg_node_pslot_param_idx(sg_node* nd, uint32_t rule, int32_t* param_idx);
+int sg_node_param_read_state(sg_node* nd, uint32_t rule, uint64_t value, int64_t* last_time, int64_t* tokens);
 
 /* ---------- token-server wire codec ----------
  * The default token server frames every message with a 2-byte big-endian length

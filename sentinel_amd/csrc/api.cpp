@@ -4649,7 +4649,9 @@ struct sg_node {
         DevBuf<sg_result> r_out;
         DevBuf<uint8_t> r_nreq, r_nout; // the same for the param / concurrent slices (see d_sub_nreq)
         DevBuf<uint64_t> r_vals;
-        DevBuf<double> r_snap;          // its part of the node snapshot
+        DevBuf<sg_slot_ext> r_ext;      // the slot chain's slice: ext records and compacted args (values in r_vals)
+        DevBuf<sg_pslot_arg> r_args;
+        DevBuf<double> r_snap;         // its part of the node snapshot
         DevBuf<sg_metric_node> r_mrows; // its metric rows
         DevBuf<uint64_t> r_mcnt;        // its row count (on its device wherever that is)
     };
@@ -4729,6 +4731,19 @@ struct sg_node {
     DevBuf<sg_local_event> d_lsub_ev;      // [max_batch] the shards' slices
     DevBuf<sg_local_result> d_lsub_out;    // [max_batch] their results
     DevBuf<int> d_lerr;
+    // the whole slot chain over the node (sg_node_slot_decide_batch, sg_node_pslot_load_rules): the param rules in
+    // force (every shard holds all of them under the node's indices; the front's rollback), the slices' ext records,
+    // and the compacted argument arrays of the shards that cannot read the caller's (node.hip k_lcmp_*)
+    bool l_ps_loaded = false;
+    std::vector<sg_pslot_rule> l_prules;
+    std::vector<sg_param_hot_item> l_phot;
+    bool compact_args = false;             // test aid (env SG_NODE_COMPACT_ARGS=1, read at sg_node_create): every shard
+                                           // gets compacted arrays, so one GPU exercises that path
+    DevBuf<sg_slot_ext> d_lsub_ext;        // [max_batch]
+    std::vector<DevBuf<sg_pslot_arg>> d_cargs;  // per shard, on devices[0] (grown on demand)
+    std::vector<DevBuf<uint64_t>> d_cvals;
+    DevBuf<unsigned long long> d_ctsum;    // the shards' tile sums, one region per shard
+    DevBuf<unsigned long long> d_ctot;     // [kMaxShards][2] arg and value totals
     // the node's metric rows: every shard's raw rows one after the other, merged by k_merge_*
     DevBuf<unsigned long long> d_mbits;     // [60][W]
     DevBuf<uint32_t> d_mpre;                // [60][W]
@@ -4903,6 +4918,9 @@ int sg_node_create(const sg_config* cfg, const int32_t* devices, uint32_t n_shar
     nd->cfg = *cfg;
     nd->devices.assign(devices, devices + n_shards);
     nd->sh.reserve(n_shards);
+    if (const char* p = std::getenv("SG_NODE_COMPACT_ARGS")) nd->compact_args = std::atoi(p) != 0;
+    nd->d_cargs.resize(n_shards);
+    nd->d_cvals.resize(n_shards);
     auto bail = [&](int rc) {
         delete nd;
         return rc;
@@ -5606,7 +5624,8 @@ int node_slice_alloc(sg_node* nd, uint32_t g, uint64_t nv) {
 
 // Shard g's part of a node token batch, run by `decide(h, req, vals, out, stream)` on the shard's slice [base, base +
 // cnt) of the routed requests (req_b / out_b bytes each; nv values from svals): peer copies in and out for a shard
-// off the front's device. Every shard with work runs in its own host thread — a shard's call waits on the host
+// off the front's device; `decide` gets the shard's index first (what else its slice needs, it moves itself). Every
+// shard with work runs in its own host thread — a shard's call waits on the host
 // between its own kernels (the param fixed point's rounds, the concurrent batch's error check), so the shards overlap
 // whether they share a device or not. The first failure is reported after all have finished.
 template <class Decide>
@@ -5645,7 +5664,7 @@ int node_run_shards(sg_node* nd, const std::vector<uint64_t>& base, const std::v
             msg[g] = hipGetErrorString(e);
             return;
         }
-        const int r = decide(h, req, vcnt[g] ? vals : nullptr, vcnt[g], cnt[g], out, nd->sh[g].stream);
+        const int r = decide(g, h, req, vcnt[g] ? vals : nullptr, vcnt[g], cnt[g], out, nd->sh[g].stream);
         if (r) {
             rc[g] = r;
             child[g] = 1;
@@ -5714,7 +5733,8 @@ int sg_node_cparam_decide_batch(sg_node* nd, const sg_cparam_req* req, uint64_t 
     if (rc) return rc;
     sg_result* sub_out = reinterpret_cast<sg_result*>(nd->d_sub_nout.get());
     rc = node_run_shards(nd, base, cnt, vbase, vcnt, sizeof(sg_cparam_req), sizeof(sg_result), q.sub_cp, sub_out,
-                         [](sg_handle* h, const void* r, const uint64_t* v, uint64_t nv, uint64_t c, void* o, hipStream_t st) {
+                         [](uint32_t, sg_handle* h, const void* r, const uint64_t* v, uint64_t nv, uint64_t c, void* o,
+                            hipStream_t st) {
                              return sg_cparam_decide_batch(h, static_cast<const sg_cparam_req*>(r), c, v, nv,
                                                            static_cast<sg_result*>(o), st);
                          });
@@ -5804,7 +5824,8 @@ int sg_node_conc_decide_batch(sg_node* nd, const sg_conc_req* req, uint64_t n, s
     if (rc) return rc;
     sg_conc_result* sub_out = reinterpret_cast<sg_conc_result*>(nd->d_sub_nout.get());
     rc = node_run_shards(nd, base, cnt, vbase, vcnt, sizeof(sg_conc_req), sizeof(sg_conc_result), q.sub_cc, sub_out,
-                         [](sg_handle* h, const void* r, const uint64_t*, uint64_t, uint64_t c, void* o, hipStream_t st) {
+                         [](uint32_t, sg_handle* h, const void* r, const uint64_t*, uint64_t, uint64_t c, void* o,
+                            hipStream_t st) {
                              return sg_conc_decide_batch(h, static_cast<const sg_conc_req*>(r), c,
                                                          static_cast<sg_conc_result*>(o), st);
                          });
@@ -5896,6 +5917,9 @@ int sg_node_conc_read_state(sg_node* nd, uint32_t key, int32_t* now_calls, uint6
 // (sg_local_owners: a key group lives on one owner), the node routes a batch by owner with a stable multisplit
 // (node.hip k_lroute_*), and the node's MetricTimerListener table is the shards' raw rows merged on the device
 // (k_merge_*). The front handle carries no local traffic: it is the staging copy of the rules that names the owners.
+// The whole chain — AuthoritySlot, and ParamFlowSlot with per-event contexts and arguments (sg_node_slot_decide_batch,
+// sg_node_pslot_load_rules) — runs the same way: each event's sg_slot_ext moves with it, and a shard reads the caller's
+// argument arrays in place (devices[0]) or its slice's compacted copy (node.hip k_lcmp_*).
 
 namespace {
 
@@ -5920,7 +5944,22 @@ int node_local_set_owners(sg_node* nd, const std::vector<uint32_t>& own) {
     return SG_OK;
 }
 
-// The front back on the rules in force (it holds no statistics: a fresh load of both rule sets).
+// The handle without param rules, as before its first sg_pslot_load_rules (one handle has no call for this: its
+// sg_local_load_rules keeps the param rules; the node's clears them, since the owners of their state may move). The
+// next batch takes the param flags off the rule image (local_apply_params).
+void pslot_unload(sg_handle* h) {
+    if (!h->ps_loaded) return;
+    drain_async(h);
+    h->ps_loaded = false;
+    if (h->ps_cluster) h->l_groups_stale = true;  // the slot chain's key groups included the cluster-mode param rules
+    h->ps_cluster = false;
+    h->ps_cluster_refs.clear();
+    h->ps_res_rules.clear();
+    h->ps_groups_stale = true;
+    if (h->l_ps_applied == 0) h->l_has_cx_ps = false;
+}
+
+// The front back on the rules in force (it holds no statistics: a fresh load of every rule set).
 void node_local_front_rollback(sg_node* nd) {
     sg_handle* f = nd->front;
     if (sg_local_load_rules(f, &nd->l_cfg, nd->l_rules.data(), (uint32_t)nd->l_rules.size()) != SG_OK) return;
@@ -5929,6 +5968,12 @@ void node_local_front_rollback(sg_node* nd) {
                                        nd->l_n_contexts);
     (void)sg_local_load_authority_rules(f, nd->l_arules.data(), (uint32_t)nd->l_arules.size(), nd->l_aorigins.data(),
                                         (uint32_t)nd->l_aorigins.size(), nd->l_n_origins);
+    if (nd->l_ps_loaded)
+        (void)sg_pslot_load_rules(f, nd->l_prules.data(), (uint32_t)nd->l_prules.size(),
+                                  nd->l_phot.empty() ? nullptr : nd->l_phot.data(), (uint32_t)nd->l_phot.size(),
+                                  (uint32_t)nd->l_rules.size());
+    else
+        pslot_unload(f);
 }
 
 // k_merge_* over `n` raw rows on devices[0] into d_out (device); *n_out rows. Waits for the result.
@@ -6033,6 +6078,183 @@ int node_local_metrics(sg_node* nd, int64_t now_ms, sg_metric_node* d_out, sg_me
     return SG_OK;
 }
 
+// sg_slot_decide_batch over the node (ext nullable: sg_node_local_decide_batch). Device pointers on devices[0].
+int node_slot_decide(sg_node* nd, const sg_local_event* ev, const sg_slot_ext* ext, uint64_t n, const sg_pslot_arg* args,
+                     uint64_t n_args, const uint64_t* values, uint64_t n_values, sg_local_result* out, void* stream) {
+    if (!nd) return SG_E_INVAL;
+    if (n == 0) return SG_OK;
+    if (!ev || !out) return nfail(nd, SG_E_INVAL, "null buffer");
+    if (n > nd->cfg.max_batch) return nfail(nd, SG_E_CAPACITY, "batch larger than max_batch");
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    if (!args) n_args = 0;
+    if (!values) n_values = 0;
+    if (n_args >= (1ull << 32) || n_values >= (1ull << 32))
+        return nfail(nd, SG_E_CAPACITY, "more than 2^32 argument records or values");
+    node_drain(nd);
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    const uint32_t G = (uint32_t)nd->shards.size();
+    if (!nd->d_lsub_ev && (!nd->d_lsub_ev.alloc_bytes(sizeof(sg_local_event) * nd->cfg.max_batch) ||
+                           !nd->d_lsub_out.alloc_bytes(sizeof(sg_local_result) * nd->cfg.max_batch)))
+        return nfail(nd, SG_E_NOMEM, "node local slices");
+    if (ext && !nd->d_lsub_ext && !nd->d_lsub_ext.alloc(nd->cfg.max_batch))
+        return nfail(nd, SG_E_NOMEM, "node ext slices");
+    NHIP(nd, hipStreamSynchronize((hipStream_t)stream));  // the caller's batch is in place (synchronous call)
+    // 1. the batch validated as a whole and split by owner: a refused batch reaches no shard
+    const bool with_args = ext && nd->l_ps_loaded;  // one handle reads the arguments only with param rules loaded
+    LRouteArgs r{};
+    r.ev = ev;
+    r.n = n;
+    r.K = (uint32_t)nd->l_rules.size();
+    r.owner = nd->d_l_owner;
+    r.G = (int)G;
+    r.tile_cnt = nd->d_tile_cnt;
+    r.shard_base = nd->d_base;
+    r.shard_tot = nd->d_base + kMaxShards + 1;
+    r.sub_ev = nd->d_lsub_ev;
+    r.sub_pos = nd->d_sub_pos;
+    r.err = nd->d_lerr;
+    r.last_ts = nd->l_last_ts;
+    r.n_origins = nd->l_n_origins;
+    r.n_wl = std::min(nd->front->l_n_wl, 2);
+    for (int w = 0; w < r.n_wl; ++w) r.wl[w] = nd->front->l_wl[w];
+    r.ext = ext;
+    r.sub_ext = nd->d_lsub_ext;
+    r.n_contexts = nd->l_n_contexts;
+    r.has_ps = with_args ? 1 : 0;
+    r.args = args;
+    r.n_args = n_args;
+    r.n_values = n_values;
+    NHIP(nd, hipMemsetAsync(nd->d_lerr, 0, sizeof(int), nd->s0));
+    NHIP(nd, launch_lroute(r, nd->s0));
+    int64_t last = 0;
+    NHIP(nd, hipMemcpyAsync(nd->h_base, nd->d_base, sizeof(uint32_t) * (2 * kMaxShards + 1), hipMemcpyDeviceToHost, nd->s0));
+    NHIP(nd, hipMemcpyAsync(nd->h_front_err, nd->d_lerr, sizeof(int), hipMemcpyDeviceToHost, nd->s0));
+    NHIP(nd, hipMemcpyAsync(&last, &ev[n - 1].ts_ms, sizeof(int64_t), hipMemcpyDeviceToHost, nd->s0));
+    NHIP(nd, hipStreamSynchronize(nd->s0));
+    const int err = *nd->h_front_err;
+    if (err & kErrTime)
+        return nfail(nd, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than the node's earlier batches");
+    if (err & kErrPeriods) return nfail(nd, SG_E_UNSUPPORTED, "batch spans more than 65536 window periods");
+    if (err & kErrBounds) return nfail(nd, SG_E_INVAL, "an event's origin id lies outside 0..n_origins");
+    if (err & kErrExt)
+        return nfail(nd, SG_E_INVAL, "an event's context lies outside 0..n_contexts - 1, or its arguments outside the "
+                                     "arg / value arrays");
+    std::vector<uint64_t> base(G), cnt(G), zero(G, 0);
+    for (uint32_t g = 0; g < G; ++g) {
+        base[g] = nd->h_base[g];
+        cnt[g] = nd->h_base[kMaxShards + 1 + g];
+    }
+    // 2. the arguments of the shards that cannot read the caller's arrays (off devices[0]; all under the test aid):
+    // their slices' own arrays, counted, refused or allocated before any shard runs, then gathered
+    std::vector<char> compact(G, 0);
+    std::vector<uint64_t> na(G, 0), nv(G, 0);
+    if (ext) {
+        bool any = false;
+        std::vector<LCompactArgs> ca(G);
+        uint64_t tile0 = 0;
+        for (uint32_t g = 0; g < G; ++g) {
+            compact[g] = cnt[g] && (nd->compact_args || nd->devices[g] != nd->devices[0]);
+            if (!compact[g] || !with_args) continue;
+            if (!any) {
+                const uint64_t words = 2 * (lcompact_tiles(nd->cfg.max_batch) + kMaxShards);
+                if (!nd->d_ctsum && (!nd->d_ctsum.alloc(words) || !nd->d_ctot.alloc(2 * kMaxShards)))
+                    return nfail(nd, SG_E_NOMEM, "argument compaction scratch");
+                any = true;
+            }
+            LCompactArgs& c = ca[g];
+            c.ev = nd->d_lsub_ev + base[g];
+            c.ext = nd->d_lsub_ext + base[g];
+            c.n = cnt[g];
+            c.K = r.K;
+            c.args = args;
+            c.values = values;
+            c.tsum = nd->d_ctsum + 2 * tile0;
+            c.tot = nd->d_ctot + 2 * g;
+            tile0 += lcompact_tiles(cnt[g]);
+            NHIP(nd, launch_lcompact_count(c, nd->s0));
+        }
+        if (any) {
+            unsigned long long tot[2 * kMaxShards];
+            NHIP(nd, hipMemcpyAsync(tot, nd->d_ctot, sizeof(tot), hipMemcpyDeviceToHost, nd->s0));
+            NHIP(nd, hipStreamSynchronize(nd->s0));
+            for (uint32_t g = 0; g < G; ++g) {
+                if (!compact[g]) continue;
+                na[g] = tot[2 * g];
+                nv[g] = tot[2 * g + 1];
+                if (na[g] >= (1ull << 32) || nv[g] >= (1ull << 32))
+                    return nfail(nd, SG_E_CAPACITY, "a shard's slice carries more than 2^32 argument records or values");
+            }
+            for (uint32_t g = 0; g < G; ++g) {
+                if (!compact[g]) continue;
+                if (!nd->d_cargs[g].reserve(na[g] ? na[g] : 1) || !nd->d_cvals[g].reserve(nv[g] ? nv[g] : 1))
+                    return nfail(nd, SG_E_NOMEM, "a shard's compacted arguments");
+                ca[g].out_args = nd->d_cargs[g];
+                ca[g].out_vals = nd->d_cvals[g];
+                NHIP(nd, launch_lcompact_gather(ca[g], nd->s0));
+            }
+            NHIP(nd, hipStreamSynchronize(nd->s0));
+        }
+        // a remote shard's ext records, arg records and values on its own device
+        for (uint32_t g = 0; g < G; ++g) {
+            if (!cnt[g] || nd->devices[g] == nd->devices[0]) continue;
+            sg_node::Shard& s = nd->sh[g];
+            NHIP(nd, hipSetDevice(nd->devices[g]));
+            if (!s.r_ext.reserve(cnt[g]) || !s.r_args.reserve(na[g] ? na[g] : 1) || !s.r_vals.reserve(nv[g] ? nv[g] : 1)) {
+                (void)hipSetDevice(nd->devices[0]);
+                return nfail(nd, SG_E_NOMEM, "shard argument buffers");
+            }
+        }
+        NHIP(nd, hipSetDevice(nd->devices[0]));
+    }
+    // 3. every shard with work decides its slice (its own host thread and stream; peer copies off devices[0])
+    const int d0 = nd->devices[0];
+    int rc = node_run_shards(
+        nd, base, cnt, zero, zero, sizeof(sg_local_event), sizeof(sg_local_result), nd->d_lsub_ev, nd->d_lsub_out,
+        [&](uint32_t g, sg_handle* h, const void* e, const uint64_t*, uint64_t, uint64_t c, void* o, hipStream_t st) {
+            const sg_local_event* sev = static_cast<const sg_local_event*>(e);
+            sg_local_result* so = static_cast<sg_local_result*>(o);
+            if (!ext) return sg_local_decide_batch(h, sev, c, so, st);
+            const sg_slot_ext* sx = nd->d_lsub_ext + base[g];
+            const sg_pslot_arg* sa = args;  // in place: the caller's arrays, no index changes
+            const uint64_t* sv = values;
+            uint64_t sna = n_args, snv = n_values;
+            if (compact[g]) {
+                sa = with_args ? nd->d_cargs[g].get() : nullptr;
+                sv = with_args ? nd->d_cvals[g].get() : nullptr;
+                sna = na[g];
+                snv = nv[g];
+            }
+            if (h->device != d0) {  // the slice's records go with it
+                sg_node::Shard& s = nd->sh[g];
+                hipError_t pe = hipMemcpyPeer(s.r_ext, h->device, sx, d0, sizeof(sg_slot_ext) * c);
+                if (pe == hipSuccess && sna) pe = hipMemcpyPeer(s.r_args, h->device, sa, d0, sizeof(sg_pslot_arg) * sna);
+                if (pe == hipSuccess && snv) pe = hipMemcpyPeer(s.r_vals, h->device, sv, d0, sizeof(uint64_t) * snv);
+                if (pe != hipSuccess) return fail(h, SG_E_DEVICE, hipGetErrorString(pe));
+                sx = s.r_ext;
+                sa = sna ? s.r_args.get() : nullptr;
+                sv = snv ? s.r_vals.get() : nullptr;
+            }
+            return sg_slot_decide_batch(h, sev, sx, c, sa, sna, sv, snv, so, st);
+        });
+    if (rc) return rc;
+    // 4. the results back in caller order
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    NHIP(nd, launch_route_gather8(nd->d_lsub_out, nd->d_sub_pos, n, out, nd->s0));
+    NHIP(nd, hipStreamSynchronize(nd->s0));
+    nd->l_last_ts = last;
+    ++nd->l_batches;
+    return SG_OK;
+}
+
+// The owner shard's handle of a resource / of a param rule's resource (null: no such index).
+sg_handle* node_local_owner(sg_node* nd, uint32_t res) {
+    return nd->l_loaded && res < nd->l_owner.size() ? nd->shards[nd->l_owner[res]] : nullptr;
+}
+
+sg_handle* node_prule_owner(sg_node* nd, uint32_t rule) {
+    return nd->l_ps_loaded && rule < nd->l_prules.size() ? node_local_owner(nd, nd->l_prules[rule].resource) : nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -6055,12 +6277,19 @@ int sg_node_local_load_rules(sg_node* nd, const sg_local_config* cfg, const sg_l
     nd->l_n_origins = nd->l_n_contexts = 0;
     nd->l_last_ts = -1;
     nd->l_batches = 0;
+    // the owners may move, and a param rule's state lives on its resource's owner: the node's param rules go too
+    // (one handle keeps them over sg_local_load_rules; load them again with sg_node_pslot_load_rules)
+    nd->l_ps_loaded = false;
+    nd->l_prules.clear();
+    nd->l_phot.clear();
+    pslot_unload(nd->front);
     std::vector<uint32_t> own;
     rc = node_local_owners(nd, own);
     if (rc) return rc;
     for (uint32_t g = 0; g < G; ++g) {
         rc = sg_local_load_rules(nd->shards[g], cfg, rules, n);
         if (rc) return node_child(nd, nd->shards[g], rc);
+        pslot_unload(nd->shards[g]);
     }
     rc = node_local_set_owners(nd, own);
     if (rc) return rc;
@@ -6159,67 +6388,7 @@ int sg_node_local_owner_of(const sg_node* nd, uint32_t resource, uint32_t* shard
 }
 
 int sg_node_local_decide_batch(sg_node* nd, const sg_local_event* ev, uint64_t n, sg_local_result* out, void* stream) {
-    if (!nd) return SG_E_INVAL;
-    if (n == 0) return SG_OK;
-    if (!ev || !out) return nfail(nd, SG_E_INVAL, "null buffer");
-    if (n > nd->cfg.max_batch) return nfail(nd, SG_E_CAPACITY, "batch larger than max_batch");
-    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
-    node_drain(nd);
-    NHIP(nd, hipSetDevice(nd->devices[0]));
-    const uint32_t G = (uint32_t)nd->shards.size();
-    if (!nd->d_lsub_ev && (!nd->d_lsub_ev.alloc_bytes(sizeof(sg_local_event) * nd->cfg.max_batch) ||
-                           !nd->d_lsub_out.alloc_bytes(sizeof(sg_local_result) * nd->cfg.max_batch)))
-        return nfail(nd, SG_E_NOMEM, "node local slices");
-    NHIP(nd, hipStreamSynchronize((hipStream_t)stream));  // the caller's batch is in place (synchronous call)
-    // 1. the batch validated as a whole and split by owner: a refused batch reaches no shard
-    LRouteArgs r{};
-    r.ev = ev;
-    r.n = n;
-    r.K = (uint32_t)nd->l_rules.size();
-    r.owner = nd->d_l_owner;
-    r.G = (int)G;
-    r.tile_cnt = nd->d_tile_cnt;
-    r.shard_base = nd->d_base;
-    r.shard_tot = nd->d_base + kMaxShards + 1;
-    r.sub_ev = nd->d_lsub_ev;
-    r.sub_pos = nd->d_sub_pos;
-    r.err = nd->d_lerr;
-    r.last_ts = nd->l_last_ts;
-    r.n_origins = nd->l_n_origins;
-    r.n_wl = std::min(nd->front->l_n_wl, 2);
-    for (int w = 0; w < r.n_wl; ++w) r.wl[w] = nd->front->l_wl[w];
-    NHIP(nd, hipMemsetAsync(nd->d_lerr, 0, sizeof(int), nd->s0));
-    NHIP(nd, launch_lroute(r, nd->s0));
-    int64_t last = 0;
-    NHIP(nd, hipMemcpyAsync(nd->h_base, nd->d_base, sizeof(uint32_t) * (2 * kMaxShards + 1), hipMemcpyDeviceToHost, nd->s0));
-    NHIP(nd, hipMemcpyAsync(nd->h_front_err, nd->d_lerr, sizeof(int), hipMemcpyDeviceToHost, nd->s0));
-    NHIP(nd, hipMemcpyAsync(&last, &ev[n - 1].ts_ms, sizeof(int64_t), hipMemcpyDeviceToHost, nd->s0));
-    NHIP(nd, hipStreamSynchronize(nd->s0));
-    const int err = *nd->h_front_err;
-    if (err & kErrTime)
-        return nfail(nd, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than the node's earlier batches");
-    if (err & kErrPeriods) return nfail(nd, SG_E_UNSUPPORTED, "batch spans more than 65536 window periods");
-    if (err & kErrBounds) return nfail(nd, SG_E_INVAL, "an event's origin id lies outside 0..n_origins");
-    std::vector<uint64_t> base(G), cnt(G), zero(G, 0);
-    for (uint32_t g = 0; g < G; ++g) {
-        base[g] = nd->h_base[g];
-        cnt[g] = nd->h_base[kMaxShards + 1 + g];
-    }
-    // 2. every shard with work decides its slice (its own host thread and stream; peer copies off devices[0])
-    int rc = node_run_shards(nd, base, cnt, zero, zero, sizeof(sg_local_event), sizeof(sg_local_result), nd->d_lsub_ev,
-                             nd->d_lsub_out,
-                             [](sg_handle* h, const void* e, const uint64_t*, uint64_t, uint64_t c, void* o, hipStream_t st) {
-                                 return sg_local_decide_batch(h, static_cast<const sg_local_event*>(e), c,
-                                                              static_cast<sg_local_result*>(o), st);
-                             });
-    if (rc) return rc;
-    // 3. the results back in caller order
-    NHIP(nd, hipSetDevice(nd->devices[0]));
-    NHIP(nd, launch_route_gather8(nd->d_lsub_out, nd->d_sub_pos, n, out, nd->s0));
-    NHIP(nd, hipStreamSynchronize(nd->s0));
-    nd->l_last_ts = last;
-    ++nd->l_batches;
-    return SG_OK;
+    return node_slot_decide(nd, ev, nullptr, n, nullptr, 0, nullptr, 0, out, stream);
 }
 
 int sg_node_local_decide_batch_host(sg_node* nd, const sg_local_event* ev, uint64_t n, sg_local_result* out) {
@@ -6241,6 +6410,138 @@ int sg_node_local_read_state(sg_node* nd, uint32_t res, int64_t* second, int64_t
     node_drain(nd);
     sg_handle* h = nd->shards[nd->l_owner[res]];
     const int rc = node_child(nd, h, sg_local_read_state(h, res, second, borrow, minute, head));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_pslot_load_rules(sg_node* nd, const sg_pslot_rule* rules, uint32_t n, const sg_param_hot_item* hot,
+                             uint32_t n_hot, uint32_t n_resources) {
+    if (!nd || (!rules && n) || (!hot && n_hot)) return SG_E_INVAL;
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    if (n_resources != nd->l_rules.size()) return nfail(nd, SG_E_INVAL, "n_resources differs from the node's resource count");
+    node_drain(nd);
+    // the front first (validation: a refused load reaches no shard, and the front goes back to the rules in force),
+    // then every shard: the whole rule set under the node's rule and resource indices. Param rules form no key
+    // groups here (the shards are in SG_CLUSTER_NOT_STARTED), so no resource changes its owner; a rule's state —
+    // token buckets, throttle times, thread counts, a resolved negative paramIdx — lives on its resource's owner.
+    int rc = sg_pslot_load_rules(nd->front, rules, n, hot, n_hot, n_resources);
+    if (rc) {
+        nd->err = nd->front->err;
+        node_local_front_rollback(nd);
+        (void)hipSetDevice(nd->devices[0]);
+        return rc;
+    }
+    for (sg_handle* h : nd->shards) {
+        rc = sg_pslot_load_rules(h, rules, n, hot, n_hot, n_resources);
+        if (rc) {
+            node_child(nd, h, rc);
+            (void)hipSetDevice(nd->devices[0]);
+            return rc;
+        }
+    }
+    nd->l_prules.assign(rules, rules + n);
+    nd->l_phot.assign(hot, hot + n_hot);
+    nd->l_ps_loaded = true;
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    return SG_OK;
+}
+
+int sg_node_slot_decide_batch(sg_node* nd, const sg_local_event* ev, const sg_slot_ext* ext, uint64_t n,
+                              const sg_pslot_arg* args, uint64_t n_args, const uint64_t* values, uint64_t n_values,
+                              sg_local_result* out, void* stream) {
+    return node_slot_decide(nd, ev, ext, n, args, n_args, values, n_values, out, stream);
+}
+
+int sg_node_slot_decide_batch_host(sg_node* nd, const sg_local_event* ev, const sg_slot_ext* ext, uint64_t n,
+                                   const sg_pslot_arg* args, uint64_t n_args, const uint64_t* values, uint64_t n_values,
+                                   sg_local_result* out) {
+    if (!nd) return SG_E_INVAL;
+    if (n == 0) return SG_OK;
+    if (!ev || !out) return nfail(nd, SG_E_INVAL, "null buffer");
+    if (n > nd->cfg.max_batch) return nfail(nd, SG_E_CAPACITY, "batch larger than max_batch");
+    if (!nd->l_loaded) return nfail(nd, SG_E_INVAL, "sg_node_local_load_rules first");
+    if (!args) n_args = 0;
+    if (!values) n_values = 0;
+    if (n_args >= (1ull << 32) || n_values >= (1ull << 32))
+        return nfail(nd, SG_E_CAPACITY, "more than 2^32 argument records or values");
+    NHIP(nd, hipSetDevice(nd->devices[0]));
+    node_drain(nd);
+    // the events and the results through host_batch (slots 0, 1); ext and the arguments in slots 2, 3; the values,
+    // of any length, in a buffer of this call (as sg_slot_decide_batch_host)
+    sg_slot_ext* d_ext = nullptr;
+    sg_pslot_arg* d_args = nullptr;
+    DevBuf<uint64_t> d_vals;
+    if ((ext && !nd->stage.get(2, nd->cfg.max_batch, d_ext)) || (n_args && !nd->stage.get(3, n_args, d_args)) ||
+        (n_values && !d_vals.alloc(n_values)))
+        return nfail(nd, SG_E_NOMEM, "host-path buffers");
+    if (ext) NHIP(nd, hipMemcpy(d_ext, ext, sizeof(sg_slot_ext) * n, hipMemcpyHostToDevice));
+    if (n_args) NHIP(nd, hipMemcpy(d_args, args, sizeof(sg_pslot_arg) * n_args, hipMemcpyHostToDevice));
+    if (n_values) NHIP(nd, hipMemcpy(d_vals, values, sizeof(uint64_t) * n_values, hipMemcpyHostToDevice));
+    return host_batch(nd, nd->devices[0], ev, n, out, [&](sg_local_event* d_ev, sg_local_result* d_out) {
+        return node_slot_decide(nd, d_ev, d_ext, n, d_args, n_args, d_vals, n_values, d_out, nullptr);
+    });
+}
+
+int sg_node_local_read_origin_state(sg_node* nd, uint32_t res, int32_t origin, int64_t* second, int64_t* borrow,
+                                    int64_t* minute, int64_t* head) {
+    if (!nd) return SG_E_INVAL;
+    sg_handle* h = node_local_owner(nd, res);
+    if (!h) return nfail(nd, SG_E_INVAL, "no such resource");
+    node_drain(nd);
+    const int rc = node_child(nd, h, sg_local_read_origin_state(h, res, origin, second, borrow, minute, head));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_local_read_context_state(sg_node* nd, uint32_t res, int32_t context, int64_t* second, int64_t* borrow,
+                                     int64_t* minute, int64_t* head) {
+    if (!nd) return SG_E_INVAL;
+    sg_handle* h = node_local_owner(nd, res);
+    if (!h) return nfail(nd, SG_E_INVAL, "no such resource");
+    node_drain(nd);
+    const int rc = node_child(nd, h, sg_local_read_context_state(h, res, context, second, borrow, minute, head));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_local_read_controller(sg_node* nd, uint32_t rule, int64_t* state3) {
+    if (!nd) return SG_E_INVAL;
+    if (!nd->l_loaded || !nd->l_has_frules || rule >= nd->l_frules.size())
+        return nfail(nd, SG_E_INVAL, "no such flow rule");
+    sg_handle* h = node_local_owner(nd, nd->l_frules[rule].resource);
+    if (!h) h = nd->shards[0];  // a rule of no resource of the node: any shard answers it as one handle does
+    node_drain(nd);
+    const int rc = node_child(nd, h, sg_local_read_controller(h, rule, state3));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_pslot_thread_count(sg_node* nd, uint32_t resource, int32_t param_idx, uint64_t value, int64_t* count) {
+    if (!nd) return SG_E_INVAL;
+    sg_handle* h = nd->l_ps_loaded ? node_local_owner(nd, resource) : nullptr;
+    if (!h) return nfail(nd, SG_E_INVAL, "no such resource (or no param rules on the node)");
+    node_drain(nd);
+    const int rc = node_child(nd, h, sg_pslot_thread_count(h, resource, param_idx, value, count));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_pslot_param_idx(sg_node* nd, uint32_t rule, int32_t* param_idx) {
+    if (!nd) return SG_E_INVAL;
+    sg_handle* h = node_prule_owner(nd, rule);
+    if (!h) return nfail(nd, SG_E_INVAL, "no such param rule");
+    node_drain(nd);
+    const int rc = node_child(nd, h, sg_pslot_param_idx(h, rule, param_idx));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_param_read_state(sg_node* nd, uint32_t rule, uint64_t value, int64_t* last_time, int64_t* tokens) {
+    if (!nd) return SG_E_INVAL;
+    sg_handle* h = node_prule_owner(nd, rule);
+    if (!h) return nfail(nd, SG_E_INVAL, "no such param rule");
+    node_drain(nd);
+    const int rc = node_child(nd, h, sg_param_read_state(h, rule, value, last_time, tokens));
     (void)hipSetDevice(nd->devices[0]);
     return rc;
 }

@@ -896,8 +896,37 @@ struct LRouteArgs {
     int32_t n_origins;         // origin ids 0..n_origins
     int n_wl;                  // window lengths of the shards' period tables (k_local_prep's kErrPeriods)
     int32_t wl[2];
+    // the whole slot chain (sg_node_slot_decide_batch): each event's 16-byte sg_slot_ext moves with it, and the count
+    // pass refuses what k_local_prep refuses from ext (kErrExt): a context past the node's, and — with param rules
+    // on the node — argument or value ranges past the caller's arrays (64-bit sums; a record outside [0, n_args)
+    // is never read). ext == null: sg_node_local_decide_batch, none of this runs.
+    const sg_slot_ext* ext;    // [n] or null
+    sg_slot_ext* sub_ext;      // [n] the slices' ext records (slice position = the event's)
+    int32_t n_contexts;
+    int32_t has_ps;            // the node has param rules loaded
+    const sg_pslot_arg* args;  // the caller's arrays (read for validation alone)
+    uint64_t n_args, n_values;
 };
+constexpr int kErrExt = 128;   // node routing: an event's context or argument ranges are out of range
 hipError_t launch_lroute(const LRouteArgs& r, hipStream_t stream);
+// One slice's arguments compacted for a shard that cannot read the caller's arrays (node.hip k_lcmp_*): every event of
+// the slice with args_null == 0 and resource < K has its arg records and their values copied to the slice's own
+// arrays, at the exclusive scans of the counts over slice order, and its ext.arg_begin rebased.
+struct LCompactArgs {
+    const sg_local_event* ev;  // the slice (validated by the count pass)
+    sg_slot_ext* ext;          // the slice's ext records; arg_begin is rebased in place by the gather
+    uint64_t n;
+    uint32_t K;
+    const sg_pslot_arg* args;  // the caller's arrays
+    const uint64_t* values;
+    sg_pslot_arg* out_args;    // the slice's arrays (gather)
+    uint64_t* out_vals;
+    unsigned long long* tsum;  // [2][tiles] arg / value counts per 4096-event tile, then their exclusive scans
+    unsigned long long* tot;   // [2] the slice's arg and value totals
+};
+hipError_t launch_lcompact_count(const LCompactArgs& c, hipStream_t stream);
+hipError_t launch_lcompact_gather(const LCompactArgs& c, hipStream_t stream);
+uint64_t lcompact_tiles(uint64_t n);
 hipError_t launch_route_gather8(const sg_local_result* sub_out, const uint32_t* sub_pos, uint64_t total,
                                 sg_local_result* out, hipStream_t stream);
 // The node's metric-row merge (node.hip k_merge_*, cluster.merge_metric_rows without a sort): every row of one fetch

@@ -530,6 +530,9 @@ hipError_t launch_nconc_scatter(const sg_conc_result* sub_out, const uint32_t* s
 //   k_route_gather8   out[pos[j]] = sub_out[j] for the 8-byte results
 // HBM-bound byte work: 32 B read (count), 32 B read + 32 B + 4 B written (scatter), 8 B + 4 B read and 8 B written
 // (gather) per event; no MFMA.
+// The whole slot chain (sg_node_slot_decide_batch) adds each event's 16-byte sg_slot_ext: 16 B more read by the count
+// pass, which validates the contexts and — with param rules on the node — the argument ranges (16 B per arg record
+// read), and 16 B more read and written by the scatter, the record at its event's slice position.
 
 namespace {
 __device__ __forceinline__ uint32_t lroute_shard(const LRouteArgs& r, uint32_t resource) {
@@ -538,6 +541,9 @@ __device__ __forceinline__ uint32_t lroute_shard(const LRouteArgs& r, uint32_t r
 }
 }  // namespace
 
+// kExt: the batch carries sg_slot_ext records (sg_node_slot_decide_batch); without them the kernels are the ones
+// sg_node_local_decide_batch always ran.
+template <bool kExt>
 __global__ void __launch_bounds__(kRouteThreads) k_lroute_count(LRouteArgs r) {
     __shared__ uint32_t cnt[kMaxShards];
     const int tid = threadIdx.x;
@@ -566,6 +572,19 @@ __global__ void __launch_bounds__(kRouteThreads) k_lroute_count(LRouteArgs r) {
         if (t >= t0 && t - t0 >= span)
             for (int w = 0; w < r.n_wl; ++w)
                 if (t / r.wl[w] - t0 / r.wl[w] >= (int64_t)kMaxPeriods) bad |= kErrPeriods;
+        if (kExt) {  // what k_local_prep refuses from the event's context and argument records
+            const sg_slot_ext x = r.ext[i];
+            if ((int64_t)x.context >= (int64_t)(r.n_contexts > 0 ? r.n_contexts : 1)) bad |= kErrExt;
+            if (r.has_ps && !x.args_null && (res & SG_KEY_INDEX) < r.K) {
+                bool ok = (uint64_t)x.arg_begin + x.arg_count <= r.n_args;
+                for (uint32_t k = 0; ok && k < x.arg_count; ++k) {
+                    const sg_pslot_arg g = r.args[x.arg_begin + k];
+                    const uint64_t m = g.kind == SG_ARG_COLLECTION ? g.value_count : (g.kind == SG_ARG_VALUE ? 1 : 0);
+                    ok = (uint64_t)g.value_begin + m <= r.n_values;
+                }
+                if (!ok) bad |= kErrExt;
+            }
+        }
         atomicAdd(&cnt[lroute_shard(r, res)], 1u);
     }
     if (bad) atomicOr(r.err, bad);
@@ -573,6 +592,7 @@ __global__ void __launch_bounds__(kRouteThreads) k_lroute_count(LRouteArgs r) {
     if (tid < r.G) r.tile_cnt[(size_t)blockIdx.x * kMaxShards + tid] = cnt[tid];
 }
 
+template <bool kExt>
 __global__ void __launch_bounds__(kRouteThreads) k_lroute_scatter(LRouteArgs r) {
     __shared__ uint32_t wrun[kRouteThreads / 64][kMaxShards];  // each wave's running count per shard in its range
     __shared__ uint32_t wtot[kRouteThreads / 64][kMaxShards];  // each wave's total per shard (its range's prefix)
@@ -619,6 +639,7 @@ __global__ void __launch_bounds__(kRouteThreads) k_lroute_scatter(LRouteArgs r) 
             const uint32_t pos = r.shard_base[s] + r.tile_cnt[(size_t)blockIdx.x * kMaxShards + s] + before +
                                  wrun[wave][s] + rank;
             r.sub_ev[pos] = r.ev[i];
+            if (kExt) r.sub_ext[pos] = r.ext[i];  // 16 B more read and written: the record keeps its event's position
             r.sub_pos[pos] = (uint32_t)i;
         }
         if (s < (uint32_t)r.G && rank == 0) wrun[wave][s] += (uint32_t)__popcll(peers);
@@ -641,11 +662,174 @@ hipError_t launch_lroute(const LRouteArgs& r, hipStream_t stream) {
     s.shard_base = r.shard_base;
     s.shard_tot = r.shard_tot;
     lds_poison(stream);
-    hipLaunchKernelGGL(k_lroute_count, dim3(tiles), dim3(kRouteThreads), 0, stream, r);
+    if (r.ext) hipLaunchKernelGGL(k_lroute_count<true>, dim3(tiles), dim3(kRouteThreads), 0, stream, r);
+    else hipLaunchKernelGGL(k_lroute_count<false>, dim3(tiles), dim3(kRouteThreads), 0, stream, r);
     hipLaunchKernelGGL(k_route_scan, dim3((unsigned)r.G), dim3(kScanThreads), 0, stream, s, tiles);
     hipLaunchKernelGGL(k_route_bases, dim3(1), dim3(64), 0, stream, s);
     lds_poison(stream);
-    hipLaunchKernelGGL(k_lroute_scatter, dim3(tiles), dim3(kRouteThreads), 0, stream, r);
+    if (r.ext) hipLaunchKernelGGL(k_lroute_scatter<true>, dim3(tiles), dim3(kRouteThreads), 0, stream, r);
+    else hipLaunchKernelGGL(k_lroute_scatter<false>, dim3(tiles), dim3(kRouteThreads), 0, stream, r);
+    return hipGetLastError();
+}
+
+// ---- a slice's arguments compacted (sg_node_slot_decide_batch; a shard off devices[0], or SG_NODE_COMPACT_ARGS) ----
+//
+// A shard on devices[0] reads the caller's arg and value arrays in place. Another shard gets its slice's own arrays,
+// built here on devices[0] in the style of k_nreq_vsum / k_nreq_vscan / k_nreq_gather: every event of the slice with
+// args_null == 0 and resource < K (the ones whose ranges the count pass validated and a shard reads) brings its
+// arg_count records and each record's values (1 for a VALUE, value_count for a COLLECTION, none for a null argument).
+//   k_lcmp_sum     per 4096-event tile: its arg records and values (64-bit: a slice's totals may pass 2^32, which the
+//                  host refuses before any shard runs)
+//   k_lcmp_scan    one block: the exclusive scans of both tile sums, the slice's totals
+//   k_lcmp_gather  per tile: a block scan of the events' counts per 256-event round gives each event its first arg
+//                  record and first value; it copies the records (value_begin rebased, value_count and kind as
+//                  given) and the values, and rebases its ext.arg_begin
+// Positions are exclusive scans over slice order: a pure function of the batch. A range several events share is
+// copied once per event. Per event taken: 32 B + 16 B read per pass (event, ext), 16 B per arg record and 8 B per value
+// read twice (sum, gather) and written once, 16 B of ext written; no MFMA. One thread walks its event's records: the
+// copies of a round are as long as its longest argument list.
+
+namespace {
+
+constexpr uint32_t kCmpTile = 4096;
+
+// The event's ext record; whether its arguments go to the shard.
+__device__ __forceinline__ bool lcmp_takes(const LCompactArgs& c, uint64_t j, sg_slot_ext& x) {
+    x = c.ext[j];
+    return !x.args_null && (c.ev[j].resource & SG_KEY_INDEX) < c.K;
+}
+
+__device__ __forceinline__ uint32_t lcmp_arg_values(const sg_pslot_arg& g) {
+    return g.kind == SG_ARG_COLLECTION ? g.value_count : (g.kind == SG_ARG_VALUE ? 1u : 0u);
+}
+
+// Exclusive scan of (a, v) over the 256 threads of the block (ws: [2][4] wave totals); tot: the block's sums.
+__device__ __forceinline__ void lcmp_block_scan(unsigned long long& a, unsigned long long& v, unsigned long long* ws,
+                                                unsigned long long& tot_a, unsigned long long& tot_v) {
+    const int lane = route_lane(), wave = threadIdx.x >> 6;
+    unsigned long long xa = a, xv = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long ya = (unsigned long long)__shfl_up((long long)xa, (unsigned)o, 64);
+        const unsigned long long yv = (unsigned long long)__shfl_up((long long)xv, (unsigned)o, 64);
+        if (lane >= o) {
+            xa += ya;
+            xv += yv;
+        }
+    }
+    if (lane == 63) {
+        ws[wave] = xa;
+        ws[4 + wave] = xv;
+    }
+    __syncthreads();
+    unsigned long long oa = xa - a, ov = xv - v;
+    tot_a = tot_v = 0;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) {
+            oa += ws[w];
+            ov += ws[4 + w];
+        }
+        tot_a += ws[w];
+        tot_v += ws[4 + w];
+    }
+    __syncthreads();  // ws is written again by the next round
+    a = oa;
+    v = ov;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_lcmp_sum(LCompactArgs c, uint32_t tiles) {
+    __shared__ unsigned long long ws[8];
+    const uint64_t t0 = (uint64_t)blockIdx.x * kCmpTile;
+    const uint64_t t1 = t0 + kCmpTile < c.n ? t0 + kCmpTile : c.n;
+    unsigned long long a = 0, v = 0;
+    for (uint64_t j = t0 + threadIdx.x; j < t1; j += 256) {
+        sg_slot_ext x;
+        if (!lcmp_takes(c, j, x)) continue;
+        a += x.arg_count;
+        for (uint32_t k = 0; k < x.arg_count; ++k) v += lcmp_arg_values(c.args[x.arg_begin + k]);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        a += (unsigned long long)__shfl_xor((long long)a, o, 64);
+        v += (unsigned long long)__shfl_xor((long long)v, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        ws[threadIdx.x >> 6] = a;
+        ws[4 + (threadIdx.x >> 6)] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        c.tsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+        c.tsum[(size_t)tiles + blockIdx.x] = ws[4] + ws[5] + ws[6] + ws[7];
+    }
+}
+
+// One block, thread 0 .. 1: the serial exclusive scan of one of the two tile-sum rows (a slice of max_batch = 2^20
+// events has 256 tiles; the scan is not worth a block's tree).
+__global__ void __launch_bounds__(64) k_lcmp_scan(LCompactArgs c, uint32_t tiles) {
+    if (threadIdx.x >= 2) return;
+    unsigned long long* row = c.tsum + (size_t)threadIdx.x * tiles;
+    unsigned long long run = 0;
+    for (uint32_t t = 0; t < tiles; ++t) {
+        const unsigned long long x = row[t];
+        row[t] = run;
+        run += x;
+    }
+    c.tot[threadIdx.x] = run;
+}
+
+__global__ void __launch_bounds__(256) k_lcmp_gather(LCompactArgs c, uint32_t tiles) {
+    __shared__ unsigned long long ws[8];
+    const uint64_t t0 = (uint64_t)blockIdx.x * kCmpTile;
+    const uint64_t t1 = t0 + kCmpTile < c.n ? t0 + kCmpTile : c.n;
+    unsigned long long run_a = c.tsum[blockIdx.x], run_v = c.tsum[(size_t)tiles + blockIdx.x];
+    // the loop runs block-uniformly (the scan is block-wide)
+    for (uint64_t b0 = t0; b0 < t1; b0 += 256) {
+        const uint64_t j = b0 + threadIdx.x;
+        sg_slot_ext x{};
+        const bool take = j < t1 && lcmp_takes(c, j, x);
+        unsigned long long a = 0, v = 0;
+        if (take) {
+            a = x.arg_count;
+            for (uint32_t k = 0; k < x.arg_count; ++k) v += lcmp_arg_values(c.args[x.arg_begin + k]);
+        }
+        unsigned long long tot_a, tot_v;
+        lcmp_block_scan(a, v, ws, tot_a, tot_v);  // a, v: the event's offsets inside the round
+        a += run_a;
+        v += run_v;
+        run_a += tot_a;
+        run_v += tot_v;
+        if (!take) continue;
+        // the host refused a slice whose totals reach 2^32, so the positions fit the 32-bit fields
+        for (uint32_t k = 0; k < x.arg_count; ++k) {
+            sg_pslot_arg g = c.args[x.arg_begin + k];
+            const uint32_t m = lcmp_arg_values(g);
+            for (uint32_t u = 0; u < m; ++u) c.out_vals[v + u] = c.values[(uint64_t)g.value_begin + u];
+            g.value_begin = (uint32_t)v;
+            c.out_args[a + k] = g;
+            v += m;
+        }
+        x.arg_begin = (uint32_t)a;
+        c.ext[j] = x;
+    }
+}
+
+uint64_t lcompact_tiles(uint64_t n) { return (n + kCmpTile - 1) / kCmpTile; }
+
+hipError_t launch_lcompact_count(const LCompactArgs& c, hipStream_t stream) {
+    const uint32_t tiles = (uint32_t)lcompact_tiles(c.n);
+    if (tiles == 0) return hipSuccess;
+    lds_poison(stream);
+    hipLaunchKernelGGL(k_lcmp_sum, dim3(tiles), dim3(256), 0, stream, c, tiles);
+    hipLaunchKernelGGL(k_lcmp_scan, dim3(1), dim3(64), 0, stream, c, tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_lcompact_gather(const LCompactArgs& c, hipStream_t stream) {
+    const uint32_t tiles = (uint32_t)lcompact_tiles(c.n);
+    if (tiles == 0) return hipSuccess;
+    lds_poison(stream);
+    hipLaunchKernelGGL(k_lcmp_gather, dim3(tiles), dim3(256), 0, stream, c, tiles);
     return hipGetLastError();
 }
 

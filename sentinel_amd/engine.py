@@ -180,6 +180,16 @@ def load_library():
         "sg_node_local_metrics": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64)]),
         "sg_node_local_metrics_device": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64)]),
         "sg_node_local_merge_rows": (C.c_int, [vp, vp, u64, vp, u64, C.POINTER(u64), vp]),
+        "sg_node_front": (vp, [vp]),
+        "sg_node_pslot_load_rules": (C.c_int, [vp, vp, u32, vp, u32, u32]),
+        "sg_node_slot_decide_batch": (C.c_int, [vp, vp, vp, u64, vp, u64, vp, u64, vp, vp]),
+        "sg_node_slot_decide_batch_host": (C.c_int, [vp, vp, vp, u64, vp, u64, vp, u64, vp]),
+        "sg_node_local_read_origin_state": (C.c_int, [vp, u32, C.c_int32, vp, vp, vp, vp]),
+        "sg_node_local_read_context_state": (C.c_int, [vp, u32, C.c_int32, vp, vp, vp, vp]),
+        "sg_node_local_read_controller": (C.c_int, [vp, u32, vp]),
+        "sg_node_pslot_thread_count": (C.c_int, [vp, u32, C.c_int32, u64, C.POINTER(i64)]),
+        "sg_node_pslot_param_idx": (C.c_int, [vp, u32, C.POINTER(C.c_int32)]),
+        "sg_node_param_read_state": (C.c_int, [vp, u32, u64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("SG_LIB_PATH") and not hasattr(L, name):
@@ -423,6 +433,81 @@ class NodeEngine:
             e.rows = n.value
             raise e
         return n.value
+
+    # ---- the whole slot chain over the node (FlowEngine's names, arguments and return shapes; the node's rule and
+    # resource indices; the readers go to the owner shard inside the library)
+    def pslot_load_rules(self, rules, hot=None, n_resources=None):
+        rules = np.ascontiguousarray(rules, dtype=abi.PSLOT_RULE_DTYPE).reshape(-1)
+        hot = np.ascontiguousarray(np.zeros(0, abi.PARAM_HOT_DTYPE) if hot is None else hot, dtype=abi.PARAM_HOT_DTYPE)
+        n_res = int(rules["resource"].max()) + 1 if n_resources is None else n_resources
+        self._check(self._L.sg_node_pslot_load_rules(self.h, abi.ptr(rules), len(rules),
+                                                     abi.ptr(hot) if len(hot) else None, len(hot), n_res))
+
+    def slot_decide_host(self, ev, ext, args, values) -> np.ndarray:
+        """sg_node_slot_decide_batch_host: HOST events with their context / argument records (ext may be None)."""
+        ev = np.ascontiguousarray(ev, dtype=abi.LOCAL_EVENT_DTYPE).reshape(-1)
+        out = np.zeros(len(ev), abi.LOCAL_RES_DTYPE)
+        if len(ev) == 0:
+            return out
+        xp = None
+        if ext is not None:
+            ext = np.ascontiguousarray(ext, dtype=abi.SLOT_EXT_DTYPE).reshape(-1)
+            xp = abi.ptr(ext)
+        args = np.ascontiguousarray(np.zeros(0, abi.PSLOT_ARG_DTYPE) if args is None else args,
+                                    dtype=abi.PSLOT_ARG_DTYPE).reshape(-1)
+        values = np.ascontiguousarray(np.zeros(0, np.uint64) if values is None else values, dtype=np.uint64).reshape(-1)
+        self._check(self._L.sg_node_slot_decide_batch_host(self.h, abi.ptr(ev), xp, len(ev),
+                                                           abi.ptr(args) if len(args) else None, len(args),
+                                                           abi.ptr(values) if len(values) else None, len(values),
+                                                           abi.ptr(out)))
+        return out
+
+    def slot_decide_device(self, ev_ptr: int, ext_ptr: int, n: int, args_ptr: int, n_args: int, values_ptr: int,
+                           n_values: int, out_ptr: int, stream_ptr: int = 0):
+        """DEVICE pointers on devices[0] (ext_ptr 0: no ext)."""
+        self._check(self._L.sg_node_slot_decide_batch(self.h, C.c_void_p(ev_ptr), C.c_void_p(ext_ptr or None), n,
+                                                      C.c_void_p(args_ptr or None), n_args,
+                                                      C.c_void_p(values_ptr or None), n_values, C.c_void_p(out_ptr),
+                                                      C.c_void_p(stream_ptr)))
+
+    def local_context_state(self, res, context, with_exists=False):
+        return self._pool_node_state(self._L.sg_node_local_read_context_state, res, context, with_exists)
+
+    def local_origin_state(self, res, origin, with_exists=False):
+        return self._pool_node_state(self._L.sg_node_local_read_origin_state, res, origin, with_exists)
+
+    def _pool_node_state(self, fn, res, ident, with_exists):
+        S = self.local_S
+        sec = np.zeros((S, 8), np.int64)
+        bor = np.zeros((S, 2), np.int64)
+        mnt = np.zeros((60, 8), np.int64)
+        head = np.zeros(14, np.int64)
+        rc = fn(self.h, res, ident, abi.ptr(sec), abi.ptr(bor), abi.ptr(mnt), abi.ptr(head))
+        if rc < 0:
+            self._check(rc)
+        return (sec, bor, mnt, head, rc == 1) if with_exists else (sec, bor, mnt, head)
+
+    def local_controller(self, rule):
+        out = np.zeros(3, np.int64)
+        self._check(self._L.sg_node_local_read_controller(self.h, rule, abi.ptr(out)))
+        return out
+
+    def pslot_thread_count(self, res, idx, value):
+        v = C.c_int64()
+        self._check(self._L.sg_node_pslot_thread_count(self.h, res, idx, int(value), C.byref(v)))
+        return v.value
+
+    def pslot_param_idx(self, rule):
+        v = C.c_int32()
+        self._check(self._L.sg_node_pslot_param_idx(self.h, rule, C.byref(v)))
+        return v.value
+
+    def param_state(self, rule, value):
+        lt, tk = C.c_int64(), C.c_int64()
+        flags = self._L.sg_node_param_read_state(self.h, rule, value, C.byref(lt), C.byref(tk))
+        if flags < 0:
+            self._check(flags)
+        return flags, lt.value, tk.value
 
 
 class FlowEngine:
