@@ -703,10 +703,58 @@ typedef struct sg_authority_rule {
 int sg_local_load_authority_rules(sg_handle* h, const sg_authority_rule* rules, uint32_t n, const int32_t* origins,
                                   uint32_t n_origin_ids, int32_t n_origins);
 
+/* ---- SystemSlot: system rules over Constants.ENTRY_NODE ----
+ *   sg_local_load_system_rules ← SystemRuleManager.loadRules (SystemPropertyListener.configUpdate and loadSystemConf,
+ *     SystemRuleManager.java:183-282): the defaults are restored, then every rule in array order lowers the threshold of
+ *     each field that is >= 0 (the minimum wins; highest_cpu_usage > 1 is ignored), and every rule SETS
+ *     checkSystemStatus: the last rule decides it — a list whose last rule sets nothing switches checking off although
+ *     earlier thresholds were stored — and an empty list switches it off. Returns checkSystemStatus (0 / 1) or an
+ *     error.
+ *     The first call starts ENTRY_NODE tracking on the handle: a second window [S] in the handle's sample_count /
+ *     interval_ms plus curThreadNum, updated by every event of an inbound resource (sg_local_set_entry_types) as
+ *     StatisticSlot does (StatisticSlot.java:71-75, 88-91, 106-109, 139-141): PASS adds the count and a thread, a
+ *     PriorityWaitException a thread only, any BlockException (authority and system included) BLOCK; an exit adds
+ *     SUCCESS, RT = ts - create_ts, minRt, takes a thread, and EXCEPTION when it carries an error. That first call must
+ *     come after sg_local_load_rules and before the first local batch (SG_E_UNSUPPORTED later: the node would miss
+ *     the earlier entries — as n_contexts). sg_local_load_rules (fresh resources) drops the rules, the
+ *     ENTRY_NODE and the tracking. A handle that never calls it launches no kernel of this section.
+ *     The check (checkSystem :290-340) runs, with checking on, for every inbound entry AuthoritySlot did not reject,
+ *     before ParamFlowSlot, in this order: passQps + count > qps; curThreadNum > maxThread; avgRt > maxRt; load set and
+ *     load > highestSystemLoad and curThread > 1 and curThread > maxSuccessQps * minRt / 1000; cpu set and cpu >
+ *     highestCpuUsage. A blocked entry returns {SG_LOCAL_BLOCK_SYSTEM, wait_ms = SG_SYSTEM_*} whatever its prioritized
+ *     flag; like an authority-rejected entry it adds BLOCK to its ClusterNode, origin node and DefaultNode (and to
+ *     ENTRY_NODE) and reaches nothing else.
+ *     Each batch first runs a scan that tries to prove that no entry of it can block (sg_local_system_last_path = 1):
+ *     such a batch keeps the parallel walkers and ENTRY_NODE is updated from its results afterwards. Any other batch
+ *     with checking on walks every inbound resource in event order on one lane (= 2; env SG_SYS_SERIAL=1 forces
+ *     this). Both leave the same results and state. A sharded handle (sg_set_shard, world > 1) with tracking on
+ *     refuses local batches (SG_E_UNSUPPORTED): ENTRY_NODE spans the shards; the node handle has no system rules.
+ *   sg_local_set_system_status ← SystemStatusListener's system load average and CPU usage (both -1 until set).
+ *   sg_local_read_entry_node   ← ENTRY_NODE's second window ([S][8], layout of sg_local_read_state) and curThreadNum;
+ *     SG_E_INVAL without tracking.
+ *   sg_local_system_last_path  ← the last local batch: 0 tracking off (or no batch), 1 proven clear, 2 serial. */
+typedef struct sg_system_rule {   /* SystemRule.java; every field -1 = not set (its defaults) */
+    double  highest_system_load, highest_cpu_usage, qps;
+    int64_t avg_rt, max_thread;
+} sg_system_rule;
+#define SG_LOCAL_BLOCK_SYSTEM 6   /* SystemBlockException; wait_ms = the limit type below */
+#define SG_SYSTEM_QPS    0        /* "qps"    */
+#define SG_SYSTEM_THREAD 1        /* "thread" */
+#define SG_SYSTEM_RT     2        /* "rt"     */
+#define SG_SYSTEM_LOAD   3        /* "load"   */
+#define SG_SYSTEM_CPU    4        /* "cpu"    */
+int sg_local_load_system_rules(sg_handle* h, const sg_system_rule* rules, uint32_t n);
+int sg_local_set_system_status(sg_handle* h, double load, double cpu_usage);
+int sg_local_read_entry_node(sg_handle* h, int64_t* second, int64_t* cur_thread_num);
+int sg_local_system_last_path(const sg_handle* h, uint32_t* path);
+/* The index of the first entry the last scan could not prove clear (0xFFFFFFFF: none, or no scan ran). */
+int sg_local_system_first_unproven(const sg_handle* h, uint32_t* index);
+
 /* ---- the whole slot chain in one batch (the ProcessorSlot chain's SPI order, Constants.java:76-83 and
- * ParamFlowSlot @Spi(order = -3000)): StatisticSlot.entry around AuthoritySlot → ParamFlowSlot → FlowSlot →
- * DegradeSlot. SystemSlot (between AuthoritySlot and ParamFlowSlot in the reference) is not part of it: it reads
- * Constants.ENTRY_NODE, which depends on every earlier decision of every resource.
+ * ParamFlowSlot @Spi(order = -3000)): StatisticSlot.entry around AuthoritySlot → SystemSlot → ParamFlowSlot →
+ * FlowSlot → DegradeSlot. SystemSlot reads Constants.ENTRY_NODE, which depends on every earlier decision of every
+ * inbound resource: with system rules loaded (above) a batch is first proven clear of system blocks from its arrivals
+ * and exits alone, or else walks its inbound resources in event order.
  *   sg_slot_decide_batch ← SphU.entry(resource, count, prioritized, args...) / Entry.exit(count, args...) for a
  *     time-ordered batch. Per entry: AuthoritySlot (the authority rules above; an AuthorityException ends the chain
  *     before any other slot, SG_LOCAL_BLOCK_AUTHORITY); ParamFlowSlot.checkFlow (the param rules sg_pslot_load_rules loaded for the

@@ -167,6 +167,11 @@ LOCAL_BLOCK_AUTHORITY = 5  # AuthorityException (sg_local_load_authority_rules)
 AUTHORITY_WHITE, AUTHORITY_BLACK = 0, 1
 AUTHORITY_RULE_DTYPE = np.dtype([("resource", "<u4"), ("strategy", "<i4"), ("origin_begin", "<u4"),
                                  ("origin_count", "<u4")], align=True)
+LOCAL_BLOCK_SYSTEM = 6  # SystemBlockException (sg_local_load_system_rules); wait_ms = the limit type
+SYSTEM_QPS, SYSTEM_THREAD, SYSTEM_RT, SYSTEM_LOAD, SYSTEM_CPU = 0, 1, 2, 3, 4
+SYSTEM_RULE_DTYPE = np.dtype([("highest_system_load", "<f8"), ("highest_cpu_usage", "<f8"), ("qps", "<f8"),
+                              ("avg_rt", "<i8"), ("max_thread", "<i8")], align=True)
+assert SYSTEM_RULE_DTYPE.itemsize == 40
 ENTRY_NODE_RESOURCE = 0xFFFFFFFF  # sg_local_metrics rows of Constants.ENTRY_NODE
 CONTROL_DEFAULT, CONTROL_WARM_UP, CONTROL_RATE_LIMITER, CONTROL_WARM_UP_RATE_LIMITER = 0, 1, 2, 3
 LIMIT_APP_DEFAULT, LIMIT_APP_OTHER = 0, -1

@@ -253,6 +253,23 @@ struct sg_handle {
     uint64_t l_ps_applied = 0;        // ps_gen whose param flags d_lrules carries (0: none)
     bool l_has_cx_ps = false;         // some resource is cx because of param rules
     DevBuf<uint8_t> d_linbound;       // [K] EntryType.IN resources (sg_local_set_entry_types), null = none
+    std::vector<uint8_t> l_inbound;   // the same on the host (the system image's key group)
+    // SystemSlot (sg_local_load_system_rules): ENTRY_NODE tracking, the thresholds, the system image
+    bool l_sys_track = false;         // ENTRY_NODE is tracked (from the first system-rule load to sg_local_load_rules)
+    LSysConf l_sys_conf = system_defaults();
+    double l_sys_load = -1, l_sys_cpu = -1;  // SystemStatusListener's values
+    DevBuf<LSys> d_lsys;              // thresholds, status, curThreadNum, scan verdict, apply scratch
+    DevBuf<LBucket> d_lsys_sec;       // [S] ENTRY_NODE's second window
+    DevBuf<unsigned long long> d_lsys_lastp;  // [S] LSys::lastp
+    DevBuf<int64_t> d_lsys_acc;       // [S][8] LSys::acc
+    DevBuf<int64_t> d_lsys_pb;        // [3][kMaxPeriods] SysArgs::pb
+    DevBuf<LRule> d_lrules_sys;       // the system image: d_lrules with every inbound resource in one key group
+    DevBuf<uint32_t> d_lgkey_sys;     // ... and its record keys
+    bool l_sys_image = false;         // the system image is current (tracking on and some resource inbound)
+    int l_sys_force = 0;              // env SG_SYS_SERIAL=1: every tracked batch takes the serial path
+    uint32_t l_sys_path = 0;          // sg_local_system_last_path
+    uint32_t l_sys_first = 0xFFFFFFFFu;  // the last scan's first unproven entry
+    PinnedBuf<uint32_t> h_lsys_verdict;  // pinned {unproven, first_unproven}
     DevBuf<LBucket> d_lentry_acc;     // [60] the ENTRY_NODE's buckets, summed per metric call
     DevBuf<unsigned long long> d_lm_cnt;     // the metric passes' row counter
     DevBuf<int64_t> d_lentry_fetch;   // the ENTRY_NODE's lastFetchTime
@@ -366,6 +383,8 @@ int ensure_layout(sg_handle* h);          // below: record layout of the loaded 
 int flow_status(sg_handle* h, int err);   // below: batch error flags -> SG_E_*
 int drain_async(sg_handle* h);  // below: completes the handle's in-flight host-pipeline batches
 int local_apply_groups(sg_handle* h);  // below: key groups of the local chain
+int local_sys_image(sg_handle* h);     // below: SystemSlot's rule image (after any change of the normal one)
+void local_sys_drop(sg_handle* h);
 }
 
 extern "C" {
@@ -598,6 +617,7 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
         return bail(SG_E_DEVICE);
     if (const char* d = std::getenv("SG_DEBUG")) h->dbg = std::atoi(d);
     if (const char* d = std::getenv("SG_CXW")) h->l_cxw = std::atoi(d) != 0 ? 1 : 0;
+    if (const char* d = std::getenv("SG_SYS_SERIAL")) h->l_sys_force = std::atoi(d) != 0 ? 1 : 0;
     if (const char* d = std::getenv("SG_CXW_MIN")) h->l_cxw_min = (uint32_t)std::strtoul(d, nullptr, 10);
     if (const char* d = std::getenv("SG_D2H")) h->d2h_kernel = std::atoi(d) != 0;
     if (const char* d = std::getenv("SG_SEG_MARK")) h->seg_mark_pass = std::atoi(d) != 0;
@@ -2975,6 +2995,8 @@ int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local
     h->l_batches = 0;
     h->d_lgkey.reset();
     h->d_linbound.reset();  // every resource's entries EntryType.OUT until sg_local_set_entry_types
+    h->l_inbound.clear();
+    local_sys_drop(h);      // the system rules, the ENTRY_NODE and its tracking go with the resources
     h->l_ps_applied = 0;
     if (!h->d_lentry_fetch && (!h->d_lentry_fetch.alloc_bytes(sizeof(int64_t)) ||
                                !h->d_lentry_acc.alloc_bytes(sizeof(LBucket) * kMinuteS)))
@@ -3024,7 +3046,8 @@ int sg_local_set_entry_types(sg_handle* h, const uint8_t* inbound, uint32_t n) {
     h->d_linbound.reset();
     if (n && !h->d_linbound.alloc_bytes(n)) return fail(h, SG_E_NOMEM, "entry types");
     if (n) HIP_TRY(h, hipMemcpy(h->d_linbound, v.data(), n, hipMemcpyHostToDevice));
-    return SG_OK;
+    h->l_inbound = v;
+    return local_sys_image(h);
 }
 
 namespace {
@@ -3185,7 +3208,7 @@ int local_apply_params(sg_handle* h) {
     if (K) HIP_TRY(h, hipMemcpy(h->d_lrules, tab.data(), sizeof(LRule) * K, hipMemcpyHostToDevice));
     h->l_has_cx_ps = any;
     h->l_ps_applied = want;
-    return SG_OK;
+    return local_sys_image(h);
 }
 
 // Node pool: a map with room for every key a batch of n events may add at load <= 1/2 (host rehash when it
@@ -3513,6 +3536,53 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
     rc = local_args(h, b, ev, ext, n, args, n_args, values, n_values, out, emb, L, sgm);
     if (rc) return rc;
     const uint32_t K = L.K;
+    // SystemSlot: with ENTRY_NODE tracked and some resource inbound, the batch is either proven clear of system
+    // blocks (k_sys_scan; the normal image and walkers, ENTRY_NODE folded in afterwards by k_sys_apply_*) or walks the
+    // system image, whose one key group decides every inbound event in order against ENTRY_NODE in memory. The
+    // verdict is read here, before the records are built: they carry the chosen image's keys.
+    if (h->l_sys_track && h->shard_world > 1)
+        return fail(h, SG_E_UNSUPPORTED, "system rules on a sharded handle: ENTRY_NODE spans the shards");
+    h->l_sys_path = 0;
+    bool sys_serial = false, sys_apply = false;
+    SysArgs SA{};
+    if (h->l_sys_track) {
+        h->l_sys_path = 1;
+        h->l_sys_first = 0xFFFFFFFFu;
+    }
+    if (h->l_sys_track && h->l_sys_image) {
+        SA.ev = ev;
+        SA.out = out;
+        SA.n = n;
+        SA.K = K;
+        SA.inbound = h->d_linbound;
+        SA.sys = h->d_lsys;
+        SA.S = L.S;
+        SA.wl = L.wl2;
+        SA.isec = L.isec;
+        SA.pb = h->d_lsys_pb;
+        SA.err = L.err;
+        const LSysConf& c = h->l_sys_conf;
+        const bool armed = c.check && ((c.load_set && h->l_sys_load > c.highest_load) ||
+                                       (c.cpu_set && h->l_sys_cpu > c.highest_cpu));
+        if (h->l_sys_force || armed) {
+            sys_serial = true;
+        } else if (c.check) {
+            HIP_TRY(h, launch_sys_scan(SA, stream));
+            HIP_TRY(h, hipMemcpyAsync(h->h_lsys_verdict, &((LSys*)h->d_lsys)->unproven, 2 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, stream));
+            HIP_TRY(h, hipStreamSynchronize(stream));
+            sys_serial = h->h_lsys_verdict[0] != 0;
+            h->l_sys_first = h->h_lsys_verdict[1];
+        }
+        if (sys_serial) {
+            L.rules = h->d_lrules_sys;
+            L.gkey = h->d_lgkey_sys;
+            L.sys = h->d_lsys;
+            L.inbound = h->d_linbound;
+            h->l_sys_path = 2;
+        }
+        sys_apply = !sys_serial;
+    }
     const bool track = h->l_n_origins > 0 || h->l_n_contexts > 0;
     if (track) {
         const int rc = lnode_prepare(h, n);
@@ -3560,7 +3630,12 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
     h->last_sorted = L.rec_sorted;
     h->last_rec4_n = 0;
     if (h->stats_on) HIP_TRY(h, hipEventRecord(h->ev[2], stream));
-    HIP_TRY(h, launch_local_walk(L, sgm, h->l_has_cx || h->l_has_cx_ps || track, h->aux, stream, h->fork, h->join));
+    HIP_TRY(h, launch_local_walk(L, sgm, h->l_has_cx || h->l_has_cx_ps || track || sys_serial, h->aux, stream, h->fork,
+                                 h->join));
+    if (sys_apply) {
+        SA.auth_rej = L.auth_rej;
+        HIP_TRY(h, launch_sys_apply(SA, stream));
+    }
     if (h->stats_on) HIP_TRY(h, hipEventRecord(h->ev[3], stream));
     HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     if (h->stats_on) {
@@ -3591,7 +3666,7 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
 // waiting to be uploaded, no per-batch phase timing. Other batches drain the pipeline and run synchronously.
 bool local_pipelinable(sg_handle* h) {
     const uint64_t want = h->ps_loaded ? h->ps_gen : 0;
-    return h->l_n_origins == 0 && h->l_n_contexts == 0 && h->l_cluster_state != SG_CLUSTER_SERVER &&
+    return h->l_n_origins == 0 && h->l_n_contexts == 0 && h->l_cluster_state != SG_CLUSTER_SERVER && !h->l_sys_track &&
            !(h->l_groups_stale && (h->l_cluster_rules || h->ps_cluster)) && h->l_ps_applied == want && !h->stats_on;
 }
 
@@ -3986,7 +4061,51 @@ int local_apply_groups(sg_handle* h) {
     h->l_has_cx = has_cx;
     h->l_ps_applied = 0;  // param flags are re-applied to the new rule image by the next batch
     h->l_groups_stale = false;
+    return local_sys_image(h);
+}
+
+// SystemSlot's rule image (serial path): the normal image (key groups and param flags as the device holds them) with
+// every inbound resource, and every key group holding one, in a single key group walked by the lane cx walker in
+// event order (system_rules.h). Rebuilt after every change of the normal image, of the entry types and of the
+// tracking; nothing without tracking or without an inbound resource.
+int local_sys_image(sg_handle* h) {
+    h->l_sys_image = false;
+    const uint32_t K = (uint32_t)h->ltab.size();
+    if (!h->l_sys_track || h->l_inbound.size() != K) return SG_OK;
+    bool any = false;
+    for (uint32_t k = 0; k < K; ++k) any = any || h->l_inbound[k];
+    if (!any) return SG_OK;
+    std::vector<uint32_t> gkey, skey;
+    std::vector<uint8_t> in_group;
+    local_group_keys(h, gkey);
+    system_group_keys(gkey, h->l_inbound, skey, in_group);
+    std::vector<LRule> tab = h->ltab;
+    for (uint32_t k = 0; k < K; ++k) {
+        if (h->ps_loaded && k < h->ps_res_rules.size() && h->ps_res_rules[k]) tab[k].ps = tab[k].cx = 1;
+        if (in_group[k]) tab[k].grp = tab[k].cx = 1;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (!h->d_lrules_sys.alloc(K) || !h->d_lgkey_sys.alloc(K)) return fail(h, SG_E_NOMEM, "system image");
+    HIP_TRY(h, hipMemcpy(h->d_lrules_sys, tab.data(), sizeof(LRule) * K, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_lgkey_sys, skey.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice));
+    h->l_sys_image = true;
     return SG_OK;
+}
+
+void local_sys_drop(sg_handle* h) {
+    h->l_sys_track = false;
+    h->l_sys_conf = system_defaults();
+    h->l_sys_image = false;
+    h->l_sys_path = 0;
+    h->l_sys_first = 0xFFFFFFFFu;
+    h->d_lsys.reset();
+    h->d_lsys_sec.reset();
+    h->d_lsys_lastp.reset();
+    h->d_lsys_acc.reset();
+    h->d_lsys_pb.reset();
+    h->d_lrules_sys.reset();
+    h->d_lgkey_sys.reset();
 }
 
 }  // namespace
@@ -4134,6 +4253,107 @@ int sg_local_load_authority_rules(sg_handle* h, const sg_authority_rule* rules, 
     h->d_lauth_ids = std::move(d_ids);
     if (n_origins > h->l_n_origins) h->l_n_origins = n_origins;  // never shrinks (the ids keep their meaning)
     return kept;
+}
+
+// ---- SystemSlot ----
+
+namespace {
+// The thresholds and status values on the device (LSys up to `threads`; the ENTRY_NODE behind them stays).
+int local_sys_upload(sg_handle* h) {
+    LSys head{};
+    head.conf = h->l_sys_conf;
+    head.load = h->l_sys_load;
+    head.cpu = h->l_sys_cpu;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(h->d_lsys, &head, offsetof(LSys, threads), hipMemcpyHostToDevice));
+    return SG_OK;
+}
+}  // namespace
+
+int sg_local_load_system_rules(sg_handle* h, const sg_system_rule* rules, uint32_t n) {
+    if (!h || (!rules && n)) return SG_E_INVAL;
+    if (!h->d_llast_ts) return fail(h, SG_E_INVAL, "sg_local_load_rules first");
+    drain_async(h);  // (and settles l_batches)
+    if (!h->l_sys_track) {
+        if (h->l_batches > 0)
+            return fail(h, SG_E_UNSUPPORTED, "ENTRY_NODE tracking (the first sg_local_load_system_rules) starts before "
+                                             "the first batch: the node holds every inbound entry since then");
+        const int S = h->lcfg.sample_count;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (!h->d_lsys.alloc(1) || !h->d_lsys_sec.alloc(S) || !h->d_lsys_lastp.alloc(S) ||
+            !h->d_lsys_acc.alloc((size_t)S * 8) || !h->d_lsys_pb.alloc(3 * (size_t)kMaxPeriods) ||
+            (!h->h_lsys_verdict && !h->h_lsys_verdict.alloc(2))) {
+            local_sys_drop(h);
+            return fail(h, SG_E_NOMEM, "ENTRY_NODE");
+        }
+        std::vector<LBucket> sec(S);
+        for (LBucket& b : sec) {
+            b.start = INT64_MIN;
+            for (int e = 0; e < kLEv; ++e) b.c[e] = 0;
+            b.min_rt = kStatMaxRt;
+        }
+        std::vector<int64_t> acc((size_t)S * 8, 0);
+        for (int j = 0; j < S; ++j) acc[(size_t)8 * j + 7] = INT64_MAX;
+        LSys sys{};
+        sys.sec = h->d_lsys_sec;
+        sys.lastp = h->d_lsys_lastp;
+        sys.acc = h->d_lsys_acc;
+        sys.first_unproven = 0xFFFFFFFFu;
+        HIP_TRY(h, hipMemcpy(h->d_lsys_sec, sec.data(), sizeof(LBucket) * S, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_lsys_acc, acc.data(), sizeof(int64_t) * acc.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemset(h->d_lsys_lastp, 0, sizeof(unsigned long long) * S));
+        HIP_TRY(h, hipMemcpy(h->d_lsys, &sys, sizeof(LSys), hipMemcpyHostToDevice));
+        h->l_sys_track = true;
+    }
+    h->l_sys_conf = system_merge(rules, n);
+    int rc = local_sys_upload(h);
+    if (rc) return rc;
+    rc = local_sys_image(h);
+    if (rc) return rc;
+    return h->l_sys_conf.check;
+}
+
+int sg_local_set_system_status(sg_handle* h, double load, double cpu_usage) {
+    if (!h) return SG_E_INVAL;
+    drain_async(h);
+    h->l_sys_load = load;
+    h->l_sys_cpu = cpu_usage;
+    return h->l_sys_track ? local_sys_upload(h) : SG_OK;
+}
+
+int sg_local_read_entry_node(sg_handle* h, int64_t* second, int64_t* cur_thread_num) {
+    if (!h || !second || !cur_thread_num) return SG_E_INVAL;
+    if (!h->l_sys_track) return fail(h, SG_E_INVAL, "ENTRY_NODE is not tracked: sg_local_load_system_rules first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    const int S = h->lcfg.sample_count;
+    std::vector<LBucket> sb(S);
+    LSys sys;
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(sb.data(), h->d_lsys_sec, sizeof(LBucket) * S, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(&sys, h->d_lsys, sizeof(LSys), hipMemcpyDeviceToHost));
+    for (int j = 0; j < S; ++j) {
+        const bool p = sb[j].start != INT64_MIN;
+        int64_t* o = second + 8 * j;
+        o[0] = sb[j].start;
+        for (int e = 0; e < kLEv; ++e) o[1 + e] = p ? sb[j].c[e] : 0;
+        o[7] = p ? sb[j].min_rt : 0;
+    }
+    *cur_thread_num = sys.threads;
+    return SG_OK;
+}
+
+int sg_local_system_last_path(const sg_handle* h, uint32_t* path) {
+    if (!h || !path) return SG_E_INVAL;
+    *path = h->l_sys_path;
+    return SG_OK;
+}
+
+int sg_local_system_first_unproven(const sg_handle* h, uint32_t* index) {
+    if (!h || !index) return SG_E_INVAL;
+    *index = h->l_sys_first;
+    return SG_OK;
 }
 
 // ------------------------------------------------------------------------ concurrent cluster tokens

@@ -8,6 +8,7 @@
 
 #include "../../include/sentinel_gpu.h"
 #include "authority_rules.h"
+#include "system_rules.h"
 #include "search_dev.h"
 
 namespace sg {
@@ -679,6 +680,23 @@ struct alignas(32) LCtl {     // the controller's state: storedTokens, lastFille
     int64_t stored, last_filled, latest, pad;
 };
 
+// SystemSlot on the device (sg_local_load_system_rules): the merged thresholds, SystemStatusListener's two values and
+// Constants.ENTRY_NODE — its second window [S] (no borrow array: no controller ever occupies on it) and
+// curThreadNum. Lives in device memory; the host rewrites the part before `threads` when rules or status change.
+struct LSys {
+    LSysConf conf;
+    double load, cpu;         // getCurrentSystemAvgLoad / getCurrentCpuUsage (-1 until set)
+    int64_t threads;          // ENTRY_NODE.curThreadNum
+    LBucket* sec;             // [S] ENTRY_NODE.rollingCounterInSecond
+    // k_sys_scan's verdict of the batch
+    uint32_t unproven;        // 1: some inbound entry may trip a threshold under the bounds
+    uint32_t first_unproven;  // its index (the first one)
+    // k_sys_apply's scratch, left zeroed by its last kernel
+    int64_t d_threads;        // the batch's thread delta
+    unsigned long long* lastp;  // [S] 1 + the last window period that touched each bucket (0: none)
+    int64_t* acc;             // [S][8] PASS, BLOCK, EXCEPTION, SUCCESS, RT sums of that period; [7] its minRt
+};
+
 struct LArgs {
     const sg_local_event* ev;
     sg_local_result* out;
@@ -748,6 +766,8 @@ struct LArgs {
     const LAuth* auth;        // [K] each resource's black / white list (authority_rules.h)
     const int32_t* auth_ids;  // the lists' origin ids above 64, sorted per resource
     uint8_t* auth_rej;        // [n] k_local_prep's verdict of each event: 1 = an entry AuthoritySlot rejects
+    LSys* sys;                // SystemSlot, serial path only (the batch walks the system image): cx_entry checks and
+                              // cx_entry / cx_exit update ENTRY_NODE for the inbound resources; else null
     // the embedded token server (ClusterStateManager SERVER, emb = 1): the handle's cluster flow state
     int32_t emb;
     const Rule* c3_rules;
@@ -807,6 +827,26 @@ hipError_t launch_local_entry_rows(const LArgs& L, int64_t now, sg_metric_node* 
                                    int raw, hipStream_t stream, const int* gate = nullptr);
 hipError_t launch_local_metrics(const LArgs& L, int64_t now, sg_metric_node* out, unsigned long long* count, int emit,
                                 int raw, hipStream_t stream, const int* gate = nullptr);
+
+// SystemSlot (local.hip): the clear proof over the time-ordered batch before it is decided (k_sys_scan: verdict in
+// sys->unproven / first_unproven), and ENTRY_NODE's update from a decided batch that walked the normal image
+// (k_sys_apply_*: skipped when the batch failed validation, *err != 0). check: checkSystemStatus.
+struct SysArgs {
+    const sg_local_event* ev;
+    const sg_local_result* out;
+    uint64_t n;
+    uint32_t K;
+    const uint8_t* inbound;   // [K]
+    const uint8_t* auth_rej;  // [n] or null
+    LSys* sys;
+    int S;
+    int32_t wl;               // INTERVAL / SAMPLE_COUNT
+    double isec;
+    int64_t* pb;              // [3][kMaxPeriods] k_sys_scan: prefix sums at the batch's window boundaries
+    const int* err;
+};
+hipError_t launch_sys_scan(const SysArgs& s, hipStream_t stream);
+hipError_t launch_sys_apply(const SysArgs& s, hipStream_t stream);
 
 // Test aid (env SG_LDS_POISON=1): before every kernel that keeps counters or tables in LDS, a kernel fills the LDS of
 // every CU with 0xA5 bytes on the same stream, so a counter a kernel forgets to initialise reads garbage at once.

@@ -134,6 +134,8 @@ __device__ __forceinline__ void lstore(const LArgs& a, uint32_t idx, int32_t st,
 
 }  // namespace
 
+#include "system_dev.h"
+
 // ------------------------------------------------------------------------------------------ prep
 
 // One block per 4096-event tile (the radix sort's): with a.hist0 the block also counts its records' first sort
@@ -1535,9 +1537,15 @@ __device__ bool cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd,
     LNode& on = nn.on;
     LNode& cn = nn.cn;
     const bool rejected = a.auth_rej && a.auth_rej[e.idx];
-    const bool params = !rejected && R.ps && a.has_ps && x && !x->args_null;
-    int32_t status = rejected ? SG_LOCAL_BLOCK_AUTHORITY : SG_LOCAL_PASS;
-    int64_t wait = 0;
+    // SystemSlot (@Spi order -5000, between AuthoritySlot and ParamFlowSlot), serial path: checkSystem of an inbound
+    // entry against ENTRY_NODE as the events before it left it. A system-blocked entry goes the way of an
+    // authority-rejected one: BLOCK counts only, wait_ms = the limit type.
+    const bool sys_in = a.sys && a.inbound[nd.k];
+    const int sys_type =
+        sys_in && !rejected && a.sys->conf.check ? sys_check(*a.sys, a.S, a.wl2, a.isec, t, e.count) : -1;
+    const bool params = !rejected && sys_type < 0 && R.ps && a.has_ps && x && !x->args_null;
+    int32_t status = rejected ? SG_LOCAL_BLOCK_AUTHORITY : sys_type >= 0 ? SG_LOCAL_BLOCK_SYSTEM : SG_LOCAL_PASS;
+    int64_t wait = sys_type >= 0 ? sys_type : 0;
     if (params) {  // ParamFlowSlot (@Spi order -3000): before FlowSlot
         // the resource's one QPS rule, its (rule, value) slot looked up by k_local_prep (LArgs::pslot), else every rule
         const uint64_t psl = a.pslot ? a.pslot[e.idx] : kPsUnknown;
@@ -1670,14 +1678,15 @@ __device__ bool cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd,
             cn.sc[kLBlock] += e.count;
             cn.mc[kLBlock] += e.count;
         }
-        if (status != SG_LOCAL_BLOCK_PARAM) wait = 0;
+        if (status != SG_LOCAL_BLOCK_PARAM && status != SG_LOCAL_BLOCK_SYSTEM) wait = 0;
     }
+    if (sys_in) sys_entry(*a.sys, a.S, a.wl2, t, e.count, status);  // Constants.ENTRY_NODE
     if (params && (status == SG_LOCAL_PASS || status == SG_LOCAL_PASS_WAIT))
         ps_threads(a.ps, nd.k, x->arg_begin, x->arg_count, +1);  // ParamFlowStatisticEntryCallback.onPass
     lstore(a, e.idx, status, wait > INT32_MAX ? INT32_MAX : (int32_t)wait);
     if (have_on) on.finish();
     if (have_cn) cn.finish();
-    return !rejected;
+    return !rejected && sys_type < 0;
 }
 
 // One exit of a cx resource: StatisticSlot.exit (:124-165) on the ClusterNode (+ DegradeSlot.exit), the origin node
@@ -1687,6 +1696,7 @@ __device__ void cx_exit(const LArgs& a, const uint32_t* const* bndp, LNode& nd, 
                         int64_t create, int origin, int ctx, const sg_slot_ext* x, uint32_t qs, uint32_t qm, uint2 nodes,
                         unsigned char* slots) {
     nd.exit(e, t, create);
+    if (a.sys && a.inbound[nd.k]) sys_exit(*a.sys, a.S, a.wl2, t, create, e.count, e.kind == SG_LOCAL_EXIT_ERROR);
     const uint32_t on_idx = nodes.x, cn_idx = nodes.y;
     auto node_exit = [&](uint32_t idx, unsigned char* slot) {
         if constexpr (W) {
@@ -3130,6 +3140,21 @@ hipError_t launch_local_walk(const LArgs& a, const BatchArgs& sg, bool has_cx, h
     const hipError_t e = launch_local_exits(a, stream, false);
     if (e != hipSuccess) return e;
     return launch_local_back(a, sg, has_cx, aux, stream, fork, join);
+}
+
+hipError_t launch_sys_scan(const SysArgs& s, hipStream_t stream) {
+    lds_poison(stream);
+    hipLaunchKernelGGL(k_sys_scan, dim3(1), dim3(kSysScanThreads), 0, stream, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_sys_apply(const SysArgs& s, hipStream_t stream) {
+    const unsigned grid = (unsigned)((s.n + kSysApplyBlock - 1) / kSysApplyBlock);
+    lds_poison(stream);
+    hipLaunchKernelGGL(k_sys_apply_last, dim3(grid), dim3(256), 0, stream, s);
+    hipLaunchKernelGGL(k_sys_apply_acc, dim3(grid), dim3(256), 0, stream, s);
+    hipLaunchKernelGGL(k_sys_apply_fold, dim3(1), dim3(64), 0, stream, s);
+    return hipGetLastError();
 }
 
 }  // namespace sg

@@ -42,7 +42,9 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_node_local_load_rules", "sg_node_local_load_flow_rules", "sg_node_local_set_entry_types",
            "sg_node_local_owner_of", "sg_node_local_decide_batch", "sg_node_local_decide_batch_host",
            "sg_node_local_read_state", "sg_node_local_metrics", "sg_node_local_metrics_device",
-           "sg_node_local_merge_rows", "sg_local_load_authority_rules", "sg_node_local_load_authority_rules"]
+           "sg_node_local_merge_rows", "sg_local_load_authority_rules", "sg_node_local_load_authority_rules",
+           "sg_local_load_system_rules", "sg_local_set_system_status", "sg_local_read_entry_node",
+           "sg_local_system_last_path", "sg_local_system_first_unproven"]
 
 _lib = None
 
@@ -172,6 +174,11 @@ def load_library():
         "sg_node_local_load_flow_rules": (C.c_int, [vp, vp, u32, C.c_int32, C.c_int32]),
         "sg_local_load_authority_rules": (C.c_int, [vp, vp, u32, vp, u32, C.c_int32]),
         "sg_node_local_load_authority_rules": (C.c_int, [vp, vp, u32, vp, u32, C.c_int32]),
+        "sg_local_load_system_rules": (C.c_int, [vp, vp, u32]),
+        "sg_local_set_system_status": (C.c_int, [vp, C.c_double, C.c_double]),
+        "sg_local_read_entry_node": (C.c_int, [vp, vp, C.POINTER(C.c_int64)]),
+        "sg_local_system_last_path": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "sg_local_system_first_unproven": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "sg_node_local_set_entry_types": (C.c_int, [vp, vp, u32]),
         "sg_node_local_owner_of": (C.c_int, [vp, u32, C.POINTER(C.c_uint32)]),
         "sg_node_local_decide_batch": (C.c_int, [vp, vp, u64, vp, vp]),
@@ -986,6 +993,37 @@ class FlowEngine:
         """EntryType of each resource's entries (1 = IN: counted by Constants.ENTRY_NODE); default OUT."""
         v = np.ascontiguousarray(inbound, dtype=np.uint8)
         self._check(self._L.sg_local_set_entry_types(self.h, abi.ptr(v), len(v)))
+
+    def local_load_system_rules(self, rules) -> int:
+        """SystemRuleManager.loadRules (sg_local_load_system_rules): `rules` in SYSTEM_RULE_DTYPE, every field -1 = not
+        set. The first call starts ENTRY_NODE tracking (before the first batch). Returns checkSystemStatus (0 / 1)."""
+        rules = np.ascontiguousarray(rules, dtype=abi.SYSTEM_RULE_DTYPE).reshape(-1)
+        rc = self._L.sg_local_load_system_rules(self.h, abi.ptr(rules) if len(rules) else None, len(rules))
+        self._check(min(rc, 0))
+        return rc
+
+    def local_set_system_status(self, load=-1.0, cpu_usage=-1.0):
+        """SystemStatusListener's system load average and CPU usage, read by the load and CPU checks."""
+        self._check(self._L.sg_local_set_system_status(self.h, load, cpu_usage))
+
+    def local_entry_node(self):
+        """Constants.ENTRY_NODE: (second [S][8] as in local_state, curThreadNum)."""
+        sec = np.zeros((self.local_S, 8), np.int64)
+        thr = C.c_int64()
+        self._check(self._L.sg_local_read_entry_node(self.h, abi.ptr(sec), C.byref(thr)))
+        return sec, thr.value
+
+    def local_system_last_path(self) -> int:
+        """The last local batch: 0 ENTRY_NODE not tracked, 1 proven clear of system blocks (parallel), 2 serial."""
+        v = C.c_uint32()
+        self._check(self._L.sg_local_system_last_path(self.h, C.byref(v)))
+        return v.value
+
+    def local_system_first_unproven(self) -> int:
+        """Index of the first entry the last scan could not prove clear (0xFFFFFFFF: none, or no scan)."""
+        v = C.c_uint32()
+        self._check(self._L.sg_local_system_first_unproven(self.h, C.byref(v)))
+        return v.value
 
     def local_set_cluster_state(self, state):
         """ClusterStateManager state (CLUSTER_NOT_STARTED -1 is the one the device decides cluster rules in)."""
