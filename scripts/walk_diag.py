@@ -66,7 +66,7 @@ def main():
     ap.add_argument("--flows", type=int, default=1_000_000)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--splits", default="256")
-    ap.add_argument("--envs", default="", help="extra runs: 'K=V,K=V;K=V' (e.g. SG_DEBUG=4 for the register walker)")
+    ap.add_argument("--envs", default="", help="extra runs: 'K=V,K=V;K=V'")
     args = ap.parse_args()
     wl = ShardWorkload(args.flows, args.requests, 0, 1, torch.device("cuda", 0))
     for sm in args.splits.split(","):

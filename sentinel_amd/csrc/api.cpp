@@ -333,6 +333,11 @@ struct sg_handle {
     bool stats_on = false;
     uint32_t short_max = kShortMax;   // default walker split (env SG_SHORT_MAX overrides, for tuning)
     bool short_max_env = false;
+    // lane / wave walker splits of the other walkers, read once in sg_create (tuning)
+    uint32_t param_short_max = 64;    // hot-parameter walkers (env SG_PARAM_SHORT_MAX; r04: 64 < 32 by 2%)
+    uint32_t pace_short_max = 128;    // pace walkers (env SG_PACE_SHORT_MAX; 1M rules, 16M canPass: 32 → 1.31,
+                                      // 64 → 1.24, 96..256 → 1.21-1.22, 512 → 1.34 ms/step)
+    uint32_t cparam_short_max = 64;   // cluster param walkers (env SG_CPARAM_SHORT_MAX; r04: 64 < 32 by 5%)
     int dbg = 0;                      // env SG_DEBUG: see BatchArgs::dbg
     int l_cxw = 1;                    // env SG_CXW=0: long cx segments on the lane walker too (LArgs::cxw)
     uint32_t l_cxw_min = 0xFFFFFFFFu;          // env SG_CXW_MIN: shortest cx segment class the wave walker takes (LArgs::cxw_cls)
@@ -344,21 +349,14 @@ struct sg_handle {
     // Pipelined flow batches (sg_flow_enqueue, sg_flow_submit): the front half of a batch (validation, sort,
     // segments) runs on s_front while the previous batch's walkers run on s_back. The workspaces ws[0] / ws[1] alternate.
     Stream s_front, s_back, s_aux2;
-    Stream s_aux3;     // the length-class-0 walker beside the other two (SG_DEBUG & 128, tuning)
-    Event tjoin;
     Stream s_xcopy;    // the sharded limiter exchange's copy into a pipeline workspace
     Event xcopy_done;
     Event front_done[2], back_done[2], pfork, pjoin;
     Event lm_in, lm_done;  // sg_local_metrics_raw_enqueue: the caller's stream <-> s_back
     DevBuf<int> d_lm_gate;                           // its capacity gate (count <= cap)
     uint64_t pipe_seq = 0;            // batches put on the pipeline so far (workspace = seq % 2)
-    bool d2h_kernel = false;          // sg_flow_submit: results to pinned host buffers by k_copy_out (env SG_D2H=1; the
-                                      // copy engine measured faster: 2.64 vs 2.45 G decisions/s end to end)
-    int d2h_blocks = 64;              // its workgroups (env SG_D2H_BLOCKS)
     int front_sixteenths = 8;         // CU partition of the pipeline streams (pipe_setup; round 6: the binned front half
                                       // (k_bin_sort) takes 4/8, -2.5 % against 3/8; the two-pass sort measures the same at 3 or 4)
-    bool cu_blocked = false;          // env SG_CU_BLOCKED=1 (tuning): the front half gets CUs i with i * 16 / cus < k
-                                      // (contiguous sixteenths); both read once in sg_create
     bool rec4 = true;                 // env SG_REC4=0: 8-byte front records on the binned path too (BatchArgs::rec4)
     int walk_cus = 0;                 // CUs of the walkers' streams when partitioned (0 = all)
     struct DevTicket {                // sg_flow_enqueue batches in flight
@@ -369,11 +367,6 @@ struct sg_handle {
     };
     DevTicket dev[kDevSlots];
     bool front_only = false;          // a node handle's front (validation + namespace limiter): no flow state
-    // k_seg_mark over the sorted records (default), or the marks fused into the last scatter pass (env SG_SEG_MARK=0:
-    // its ~20M atomicMin/Max per 16M-record batch cost more than the separate read — 0.97 vs 0.91 ms/step, same box)
-    bool seg_mark_pass = true;
-    bool lim_pipe = true;             // limiter batches: the front half does not wait for the previous back half
-                                      // (env SG_LIM_PIPE=0: it waits); read once in sg_create
 };
 
 namespace {
@@ -604,14 +597,8 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
     if (hipMemcpy(h->d_plast_ts, &neg, sizeof(neg), hipMemcpyHostToDevice) != hipSuccess) return bail(SG_E_DEVICE);
     for (auto& e : h->ev)
         if (hipEventCreate(e.put()) != hipSuccess) return bail(SG_E_DEVICE);
-    // the auxiliary stream carries the wave walkers beside the lane walkers (pace, hot params, cluster params);
-    // env SG_AUX_PRIO=1 (tuning) creates it at the highest stream priority
-    int aux_prio = 0;
-    if (const char* e = std::getenv("SG_AUX_PRIO"); e && std::atoi(e) == 1) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) aux_prio = greatest;
-    }
-    if (hipStreamCreateWithPriority(h->aux.put(), hipStreamNonBlocking, aux_prio) != hipSuccess ||
+    // the auxiliary stream carries the wave walkers beside the lane walkers (pace, hot params, cluster params)
+    if (hipStreamCreateWithPriority(h->aux.put(), hipStreamNonBlocking, 0) != hipSuccess ||
         hipEventCreateWithFlags(h->fork.put(), hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(h->join.put(), hipEventDisableTiming) != hipSuccess)
         return bail(SG_E_DEVICE);
@@ -619,20 +606,17 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
     if (const char* d = std::getenv("SG_CXW")) h->l_cxw = std::atoi(d) != 0 ? 1 : 0;
     if (const char* d = std::getenv("SG_SYS_SERIAL")) h->l_sys_force = std::atoi(d) != 0 ? 1 : 0;
     if (const char* d = std::getenv("SG_CXW_MIN")) h->l_cxw_min = (uint32_t)std::strtoul(d, nullptr, 10);
-    if (const char* d = std::getenv("SG_D2H")) h->d2h_kernel = std::atoi(d) != 0;
-    if (const char* d = std::getenv("SG_SEG_MARK")) h->seg_mark_pass = std::atoi(d) != 0;
-    if (const char* d = std::getenv("SG_LIM_PIPE")) h->lim_pipe = std::atoi(d) != 0;
     if (const char* d = std::getenv("SG_BIN")) h->bin_mode = std::atoi(d);
-    if (const char* d = std::getenv("SG_FRONT_EIGHTHS")) h->front_sixteenths = 2 * std::atoi(d);
     if (const char* d = std::getenv("SG_FRONT_SIXTEENTHS")) h->front_sixteenths = std::atoi(d);
     if (const char* d = std::getenv("SG_REC4")) h->rec4 = std::atoi(d) != 0;
-    if (const char* d = std::getenv("SG_CU_BLOCKED")) h->cu_blocked = std::atoi(d) == 1;
     if (const char* d = std::getenv("SG_PREP_TILES")) h->prep_tiles = std::max(1, std::min(64, std::atoi(d)));
-    if (const char* d = std::getenv("SG_D2H_BLOCKS")) h->d2h_blocks = std::max(1, std::atoi(d));
     if (const char* sm = std::getenv("SG_SHORT_MAX")) {
         h->short_max = (uint32_t)std::strtoul(sm, nullptr, 10);
         h->short_max_env = true;
     }
+    if (const char* d = std::getenv("SG_PARAM_SHORT_MAX")) h->param_short_max = (uint32_t)std::strtoul(d, nullptr, 10);
+    if (const char* d = std::getenv("SG_PACE_SHORT_MAX")) h->pace_short_max = (uint32_t)std::strtoul(d, nullptr, 10);
+    if (const char* d = std::getenv("SG_CPARAM_SHORT_MAX")) h->cparam_short_max = (uint32_t)std::strtoul(d, nullptr, 10);
     if (const char* mr = std::getenv("SG_CP_MAX_ROUNDS")) h->cp_max_rounds = (uint32_t)std::strtoul(mr, nullptr, 10);
     // default namespace 0, no limiter, 1 connection
     sg_namespace d0{0, 1, 30000.0};
@@ -1333,16 +1317,15 @@ int pipe_setup(sg_handle* h) {
         if (!flow_ws_alloc(h, w)) return fail(h, SG_E_NOMEM, "pipeline workspace");
         // CU partition between the halves (env SG_FRONT_SIXTEENTHS = k: the front half gets the CUs whose sixteenth
         // 2 * (i % 8) + (i / 8) % 2 is below k, the walkers the rest; 0 = no masks, both halves on every CU). An even
-        // k is SG_FRONT_EIGHTHS = k / 2, the same CUs as i % 8 < k / 2; an odd k adds every other CU of the next eighth.
+        // k takes the CUs with i % 8 < k / 2; an odd k adds every other CU of the next eighth.
         int cus = 0;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
         const int k16 = h->front_sixteenths;
-        const bool blocked = h->cu_blocked;
         if (k16 > 0 && k16 < 16 && cus >= 8) {
             std::vector<uint32_t> fm((cus + 31) / 32, 0u), bm((cus + 31) / 32, 0u);
             int nb = 0;
             for (int i = 0; i < cus; ++i) {
-                if ((blocked ? i * 16 / cus : 2 * (i % 8) + (i / 8) % 2) < k16) fm[i / 32] |= 1u << (i % 32);
+                if (2 * (i % 8) + (i / 8) % 2 < k16) fm[i / 32] |= 1u << (i % 32);
                 else {
                     bm[i / 32] |= 1u << (i % 32);
                     ++nb;
@@ -1351,15 +1334,12 @@ int pipe_setup(sg_handle* h) {
             HIP_TRY(h, hipExtStreamCreateWithCUMask(h->s_front.put(), (uint32_t)fm.size(), fm.data()));
             HIP_TRY(h, hipExtStreamCreateWithCUMask(h->s_back.put(), (uint32_t)bm.size(), bm.data()));
             HIP_TRY(h, hipExtStreamCreateWithCUMask(h->s_aux2.put(), (uint32_t)bm.size(), bm.data()));
-            HIP_TRY(h, hipExtStreamCreateWithCUMask(h->s_aux3.put(), (uint32_t)bm.size(), bm.data()));
             h->walk_cus = nb;
         } else {
             HIP_TRY(h, hipStreamCreateWithFlags(h->s_front.put(), hipStreamNonBlocking));
             HIP_TRY(h, hipStreamCreateWithFlags(h->s_back.put(), hipStreamNonBlocking));
             HIP_TRY(h, hipStreamCreateWithFlags(h->s_aux2.put(), hipStreamNonBlocking));
-            HIP_TRY(h, hipStreamCreateWithFlags(h->s_aux3.put(), hipStreamNonBlocking));
         }
-        HIP_TRY(h, hipEventCreateWithFlags(h->tjoin.put(), hipEventDisableTiming));
         for (int x = 0; x < 2; ++x) {
             HIP_TRY(h, hipEventCreateWithFlags(h->front_done[x].put(), hipEventDisableTiming));
             HIP_TRY(h, hipEventCreateWithFlags(h->back_done[x].put(), hipEventDisableTiming));
@@ -1430,7 +1410,6 @@ BatchArgs flow_args(sg_handle* h, const sg_handle::FlowWs& w, const sg_req* req,
     a.skip_cap = (uint32_t)(2 * h->cfg.max_batch / kSkipMin + 1);
     a.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u
                   : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : h->short_max;
-    a.tiny = tiny_walker_enabled(a) ? 1 : 0;
     return a;
 }
 
@@ -1526,11 +1505,8 @@ int flow_front(sg_handle* h, BatchArgs& a, uint32_t* hist, hipStream_t stream, b
     }
     {
         uint64_t* sorted = nullptr;
-        // segment marks: k_seg_mark after the sort, or (SG_SEG_MARK=0) fused into the last scatter pass
-        const SegMark mk{a.seg_start, a.seg_end, a.K, a.kshift};
-        a.seg_marked = (a.seg_start && a.seg_end && a.long_end && !h->seg_mark_pass) ? 1 : 0;
         HIP_TRY(h, radix_sort_records(a.rec, a.rec_sorted, a.n, a.kshift, hist, &sorted, stream, 64, a.hist0 != nullptr,
-                                      a.seg_marked ? &mk : nullptr, a.csum0 != nullptr));
+                                      a.csum0 != nullptr));
         a.rec_sorted = sorted;
     }
     if (stats) HIP_TRY(h, hipEventRecord(h->ev[2], stream));
@@ -1547,24 +1523,13 @@ int flow_back(sg_handle* h, const BatchArgs& a, hipStream_t stream, hipStream_t 
     if (h->dbg & 2) {
         HIP_TRY(h, launch_walk_long(a, stream));
         HIP_TRY(h, launch_walk_short(a, stream));
-        HIP_TRY(h, launch_walk_tiny(a, stream));
     } else {
         HIP_TRY(h, hipEventRecord(fork, stream));
         HIP_TRY(h, hipStreamWaitEvent(aux, fork, 0));
         HIP_TRY(h, launch_walk_long(a, aux));
-        // the length-class-0 walker on a third stream beside the other two (pipelined flow path), else after the
-        // short walker
-        const bool third = a.tiny && aux == h->s_aux2 && h->s_aux3;
-        if (third) {
-            HIP_TRY(h, hipStreamWaitEvent(h->s_aux3, fork, 0));
-            HIP_TRY(h, launch_walk_tiny(a, h->s_aux3));
-            HIP_TRY(h, hipEventRecord(h->tjoin, h->s_aux3));
-        }
         HIP_TRY(h, launch_walk_short(a, stream));
-        if (!third) HIP_TRY(h, launch_walk_tiny(a, stream));
         HIP_TRY(h, hipEventRecord(join, aux));
         HIP_TRY(h, hipStreamWaitEvent(stream, join, 0));
-        if (third) HIP_TRY(h, hipStreamWaitEvent(stream, h->tjoin, 0));
     }
     HIP_TRY(h, launch_skip_apply(a, stream));
     if (stats) HIP_TRY(h, hipEventRecord(h->ev[3], stream));
@@ -1601,9 +1566,9 @@ int enqueue_flow(sg_handle* h, const sg_req* req, uint64_t n, sg_result* out, hi
 
 // Enqueue one batch on the pipeline: its front half waits for `after` (its input's arrival, may be null) and for
 // the walkers of the batch two back (same workspace); its back half follows its front half and the previous
-// batch's back half. With namespace limiters the front half also waits for the previous back half (the limiter
-// pre-pass must see only accepted batches, so the cross-batch time check stays in k_prep). Returns the event
-// that marks the batch's completion through *done (the back half's end, recorded on s_back).
+// batch's back half. With namespace limiters the cross-batch time check stays in k_prep, against front_ts (the
+// limiter pre-pass must see only accepted batches). Returns the event that marks the batch's completion through
+// *done (the back half's end, recorded on s_back).
 int enqueue_flow_pipelined(sg_handle* h, const sg_req* req, uint64_t n, sg_result* out, hipEvent_t after, int* err_dst,
                            hipEvent_t done) {
     int rc = ensure_layout(h);
@@ -1611,8 +1576,6 @@ int enqueue_flow_pipelined(sg_handle* h, const sg_req* req, uint64_t n, sg_resul
     rc = pipe_setup(h);
     if (rc) return rc;
     const int x = (int)(h->pipe_seq & 1);
-    const int xp = x ^ 1;
-    const bool first = h->pipe_seq == 0;
     sg_handle::FlowWs& w = h->ws[x];
     // sharded namespace limiter: the armed exchange is copied into workspace x's own buffer now (the caller's
     // buffer is free again when this returns); the batch two back, which read that buffer, has finished its
@@ -1644,14 +1607,10 @@ int enqueue_flow_pipelined(sg_handle* h, const sg_req* req, uint64_t n, sg_resul
     if (h->n_lim > 0) {
         // the limiter pre-pass must see only accepted batches: k_prep checks the time order against the previous
         // front half's last timestamp (front_ts, advanced once a batch passed validation) as well as last_ts, so
-        // this front half need not wait for the previous batch's walkers (env SG_LIM_PIPE=0: it waits, as before).
+        // this front half need not wait for the previous batch's walkers.
         // A batch the back half later refuses has still advanced front_ts: the next batch is checked against its
         // timestamps too (a batch must be time-ordered after every batch submitted before it, accepted or not).
-        if (!h->lim_pipe) {
-            if (!first) HIP_TRY(h, hipStreamWaitEvent(h->s_front, h->back_done[xp], 0));
-        } else {
-            a.front_ts = h->d_front_ts;
-        }
+        a.front_ts = h->d_front_ts;
     } else {
         a.check_last = 0;  // checked by the back half, after the previous batch has advanced last_ts
     }
@@ -1843,19 +1802,9 @@ int sg_flow_submit(sg_handle* h, const sg_req* req, uint64_t n, sg_result* out, 
     int rc = enqueue_flow_pipelined(h, sl.d_req, n, sl.d_out, sl.h2d, sl.h_err, sl.comp);
     if (rc) return rc;
     HIP_TRY(h, hipStreamWaitEvent(h->s_out, sl.comp, 0));
-    // results back on the copy engine (both directions of the link overlap: H2D of the next batch on s_in), or with
-    // SG_D2H=1 by a copy kernel when `out` is pinned host memory the device can address
-    void* out_dev = nullptr;
-    if (h->d2h_kernel) {
-        hipPointerAttribute_t pa{};
-        if (hipPointerGetAttributes(&pa, out) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
-            ((uintptr_t)pa.devicePointer & 15) == 0)
-            out_dev = pa.devicePointer;
-        else
-            (void)hipGetLastError();  // pageable memory: not an error, the copy engine takes it
-    }
-    if (out_dev) HIP_TRY(h, launch_copy_out(sl.d_out, out_dev, sizeof(sg_result) * n, h->d2h_blocks, h->s_out));
-    else HIP_TRY(h, hipMemcpyAsync(out, sl.d_out, sizeof(sg_result) * n, hipMemcpyDeviceToHost, h->s_out));
+    // results back on the copy engine (both directions of the link overlap: H2D of the next batch on s_in; a copy
+    // kernel measured slower end to end, 2.45 vs 2.64 G decisions/s)
+    HIP_TRY(h, hipMemcpyAsync(out, sl.d_out, sizeof(sg_result) * n, hipMemcpyDeviceToHost, h->s_out));
     HIP_TRY(h, hipEventRecord(sl.d2h, h->s_out));
     // (a slot is reused only after its batch completed: above, or when its ticket was collected)
     sl.ticket = h->next_ticket++;
@@ -2191,9 +2140,8 @@ int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int
     p.last_ts = h->d_plast_ts;
     p.long_list = h->ws[0].long_list;
     p.long_count = h->ws[0].counts;
-    uint32_t psplit = 64u;  // lane / wave walker split of the hot-parameter walkers (SG_PARAM_SHORT_MAX: tuning; r04: 64 < 32 by 2%)
-    if (const char* e = std::getenv("SG_PARAM_SHORT_MAX")) psplit = (uint32_t)std::strtoul(e, nullptr, 10);
-    p.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : psplit;
+    p.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u
+                  : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : h->param_short_max;
     const int gbits = bits_for(h->ptotal + 1);
     p.gshift = p.ibits + 8;  // {slot | acquire code : 8 | request index}
     if (p.gshift + gbits > 64) return fail(h, SG_E_UNSUPPORTED, "param tables x max_batch too large for 64-bit records");
@@ -2336,10 +2284,8 @@ int sg_pace_decide_batch(sg_handle* h, const sg_pace_req* req, uint64_t n, int32
     p.long_list = h->ws[0].long_list;
     p.long_count = h->ws[0].counts;
     p.short_list = h->ws[0].short_list;
-    uint32_t psplit = 128u;  // lane / wave walker split of the pace walkers (SG_PACE_SHORT_MAX: tuning; 1M rules,
-                             // 16M canPass: 32 → 1.31, 64 → 1.24, 96..256 → 1.21-1.22, 512 → 1.34 ms/step)
-    if (const char* e = std::getenv("SG_PACE_SHORT_MAX")) psplit = (uint32_t)std::strtoul(e, nullptr, 10);
-    p.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : psplit;
+    p.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u
+                  : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : h->pace_short_max;
     const int gbits = bits_for((uint64_t)p.n_rules + 1);
     p.gshift = p.ibits + 8;  // {rule | acquire code : 8 | request index}
     if (p.gshift + gbits > 64) return fail(h, SG_E_UNSUPPORTED, "pace rules x max_batch too large for 64-bit records");
@@ -2716,9 +2662,8 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     sgm.short_list = h->d_cp_short;
     sgm.short_count = h->ws[0].counts + 1;
     for (int cl = 0; cl < kClasses; ++cl) sgm.class_off[cl] = h->cp_class_off[cl];
-    uint32_t csplit = 64u;  // lane / wave walker split of the cluster param walkers (SG_CPARAM_SHORT_MAX: tuning; r04: 64 < 32 by 5%)
-    if (const char* e = std::getenv("SG_CPARAM_SHORT_MAX")) csplit = (uint32_t)std::strtoul(e, nullptr, 10);
-    sgm.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : csplit;
+    sgm.short_max = (h->cfg.flags & SG_FLAG_WAVE_ONLY) ? 0u
+                    : (h->cfg.flags & SG_FLAG_SERIAL_ONLY) ? 0xFFFFFFFFu : h->cparam_short_max;
     HIP_TRY(h, hipMemsetAsync(h->ws[0].counts, 0, (1 + kClasses) * sizeof(uint32_t), stream));
     HIP_TRY(h, launch_seg(sgm, stream));
     // are there multi-value requests? (then the first walk saves the touched rings for the re-walks)
@@ -2746,8 +2691,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         uint32_t ck_np = 0;
         for (int w = 0; w < b.n_wl; ++w) ck_np = std::max(ck_np, np[w]);
         const uint64_t ck = (uint64_t)counts[0] * ck_np * h->cpstride;
-        if (counts[0] > 0 && ck_np <= kCkMaxPeriods && ck * sizeof(CPBucket) <= kCkMaxBytes &&
-            !std::getenv("SG_CP_NO_CKPT")) {
+        if (counts[0] > 0 && ck_np <= kCkMaxPeriods && ck * sizeof(CPBucket) <= kCkMaxBytes) {
             if (!h->d_cp_ckpt.reserve(ck)) return fail(h, SG_E_NOMEM, "cparam ring checkpoints");
             b.ckpt = h->d_cp_ckpt;
             b.ck_np = ck_np;
@@ -3494,7 +3438,7 @@ int local_front(sg_handle* h, LArgs& L, BatchArgs& sgm, hipStream_t stream) {
 // count_exits: k_seg also counts the exit records per exit tile (k_lexit_count's pass, pipelined path)
 int local_sort(sg_handle* h, LArgs& L, BatchArgs& sgm, uint64_t* spare, hipStream_t stream, bool count_exits = false) {
     uint64_t* sorted = nullptr;
-    HIP_TRY(h, radix_sort_records(L.rec, spare, L.n, L.kshift, L.hist0, &sorted, stream, 64, true, nullptr,
+    HIP_TRY(h, radix_sort_records(L.rec, spare, L.n, L.kshift, L.hist0, &sorted, stream, 64, true,
                                   L.csum0 != nullptr));
     L.rec_sorted = sorted;
     sgm.rec_sorted = sorted;
@@ -5070,10 +5014,8 @@ int node_shard_rec(sg_handle* h, BatchArgs b, uint64_t cnt, uint32_t* hist, hipS
     HIP_TRY(h, hipMemsetAsync(b.long_count, 0, (1 + kClasses) * sizeof(uint32_t), front));
     HIP_TRY(h, hipMemsetAsync(b.skip_count, 0, sizeof(uint32_t), front));
     uint64_t* sorted = nullptr;
-    const SegMark mk{b.seg_start, b.seg_end, b.K, b.kshift};
-    b.seg_marked = (b.seg_start && b.seg_end && b.long_end && !h->seg_mark_pass) ? 1 : 0;
     HIP_TRY(h, radix_sort_records(b.rec, b.rec_sorted, cnt, b.kshift, hist, &sorted, front, 64, b.hist0 != nullptr,
-                                  b.seg_marked ? &mk : nullptr, b.csum0 != nullptr));
+                                  b.csum0 != nullptr));
     b.rec_sorted = sorted;
     HIP_TRY(h, launch_seg_flow(b, front));
     if (front_done) {
@@ -5084,7 +5026,6 @@ int node_shard_rec(sg_handle* h, BatchArgs b, uint64_t cnt, uint32_t* hist, hipS
     HIP_TRY(h, hipStreamWaitEvent(aux, fork, 0));
     HIP_TRY(h, launch_walk_long(b, aux));
     HIP_TRY(h, launch_walk_short(b, back));
-    HIP_TRY(h, launch_walk_tiny(b, back));
     HIP_TRY(h, hipEventRecord(join, aux));
     HIP_TRY(h, hipStreamWaitEvent(back, join, 0));
     HIP_TRY(h, launch_skip_apply(b, back));

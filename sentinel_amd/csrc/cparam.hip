@@ -1294,9 +1294,6 @@ hipError_t launch_cp_order(const CPArgs& c, const CPBatch& b, const uint64_t* so
 hipError_t launch_cp_walk2(const CPArgs& c, const CPBatch& b, const BatchArgs& sg, hipStream_t stream, hipStream_t aux,
                            hipEvent_t fork, hipEvent_t join) {
     const uint64_t waves = sg.n / ((uint64_t)sg.short_max + 1) + 1;  // bound on the long list's length
-#ifdef SG_CP_ONE_STREAM
-    aux = stream;
-#endif
     hipError_t e = hipEventRecord(fork, stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(aux, fork, 0);
     if (e != hipSuccess) return e;

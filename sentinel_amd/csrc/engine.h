@@ -128,20 +128,17 @@ struct BatchArgs {
     uint32_t* seg_start;   // [K] start of each present key's segment (k_seg_mark), 0xFFFFFFFF between batches
     uint32_t* short_end;   // end of each short_list entry's segment (k_seg_classify)
     uint32_t* long_end;    // end of each long_list entry's segment (k_seg_classify; nullptr: seg_end[long_key])
-    int seg_marked;        // the sort's last pass marked seg_start / seg_end (launch_seg_flow skips k_seg_mark)
     uint32_t* long_pend;   // [kLongTab][kLongPeriods]: position in rec_sorted where period q + 1 of long segment
                            // i begins (k_long_bounds; nullptr: the wave walker searches for it)
     uint64_t class_off[kClasses]; // first entry of each class slice in short_list
     uint32_t short_max;  // segments longer than this go to the wave walker
     uint32_t* exit_cnt;  // local chain: k_seg also counts the exit records per kLTile-record tile into exit_cnt[1 + t]
     uint64_t exit_amask; // (zeroed before; an exit is a record of a resource whose kind bits (amask >> 1 & 3) are set)
-    int dbg;             // debugging switches (env SG_DEBUG): 1 = period table from HBM, 2 = one stream
-                         // (serialised walkers, for per-kernel profiles), 64 = short-walker counters into dbg_ctr,
-                         // 128 = length class 0 through k_walk_tiny; timing experiments only (wrong results):
-                         // 4096 = no k_walk_long, 8192 = no k_walk_short, 16384 = k_prep writes no default results
+    int dbg;             // debugging switches (env SG_DEBUG): 2 = one stream (serialised walkers, for per-kernel
+                         // profiles), 64 = walker counters into dbg_ctr, 65536 = k_bin_sort's per-phase clocks into
+                         // dbg_ctr[40..51] (scripts/bin_diag.py); other bits are ignored
     int narrow;          // PASS / WAITING of every bucket provably < 2^30 (short walker's 12 B LDS snapshot)
     int generic_walker;  // SG_FLAG_RING_REREAD: short walker re-reads the ring (no register snapshot)
-    int tiny;            // 1: length class 0 (<= kClassMax[0] records) is walked by k_walk_tiny, not k_walk_short
     unsigned long long* dbg_ctr;  // [32]
     // ranges of records the wave walker skipped as certainly BLOCKED: {flow key, period q, begin, end}
     uint4* skips;
@@ -1008,16 +1005,9 @@ constexpr uint32_t kChunkTiles = SG_CHUNK_TILES;  // sort tiles per column-sum c
 bool radix_csum_atomic();
 uint32_t* radix_csum(uint32_t* hist_ws, uint64_t n, int D);   // the chunk column sums' place in hist_ws
 size_t radix_csum_bytes(uint64_t n, int D);
-// Segment marks of a flowId-keyed sort's last pass (seg_start atomicMin / seg_end atomicMax per key, see sort.hip)
-struct SegMark {
-    uint32_t* seg_start;
-    uint32_t* seg_end;
-    uint32_t K;
-    int kshift;
-};
 hipError_t radix_sort_records(uint64_t* a, uint64_t* b, uint64_t n, int lo_bit, uint32_t* hist_ws,
                               uint64_t** result, hipStream_t stream, int hi_bit = 64, bool first_hist_ready = false,
-                              const SegMark* mark = nullptr, bool first_csum_ready = false);
+                              bool first_csum_ready = false);
 const uint32_t* radix_tot(const uint32_t* hist_ws, uint64_t n, int D);
 hipError_t radix_bin_pass(uint64_t* src, uint64_t* out, uint64_t* reg, uint32_t R, uint64_t n, int shift,
                           uint32_t* hist_ws, bool hist_ready, bool csum_ready, hipStream_t stream);
@@ -1041,14 +1031,10 @@ hipError_t launch_hot_reset(uint2* hot_tab, hipStream_t stream);
 // Testing aid: a compact-layout batch's sorted records (BatchArgs::rec4) as n 8-byte records in `out`.
 hipError_t launch_rec4_expand(const BatchArgs& a, uint64_t* out, hipStream_t stream);
 hipError_t launch_walk_long(const BatchArgs& a, hipStream_t stream);   // on an aux stream, concurrent with
-bool tiny_walker_enabled(const BatchArgs& a);
-hipError_t launch_walk_tiny(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_walk_short(const BatchArgs& a, hipStream_t stream);  // the short walker
 hipError_t launch_check_last(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_finish(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_front_ts(const BatchArgs& a, hipStream_t stream);
-// bytes (a multiple of 4) from device memory to a device-accessible host buffer by the shader
-hipError_t launch_copy_out(const void* src, void* dst_dev, uint64_t bytes, int blocks, hipStream_t stream);
 hipError_t launch_skip_apply(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_hot_sync(const Bucket* ring, BucketHot* hot, uint64_t buckets, hipStream_t stream);
 hipError_t launch_init_state(Bucket* ring, Occ* occ, uint32_t K, int stride, const int32_t* src_map,

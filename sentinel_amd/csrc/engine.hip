@@ -205,23 +205,19 @@ __global__ void __launch_bounds__(256) k_prep(BatchArgs a) {
             if constexpr (BIN) {  // the flowId's hot slot, else its key range
                 d = key >> a.bin_bsh;
                 r4 = ((key - (d << a.bin_bsh)) << kRec4KeyShift) | (uint32_t)ac;
-                if (!(a.dbg & 131072)) {  // (timing experiment: no hot lookup, every flowId regular)
-                    const uint4* hb = reinterpret_cast<const uint4*>(htab + hot_hash(key) * kHotWays);
-                    const uint4 e0 = hb[0], e1 = hb[1];
-                    d = e0.x == key ? a.bin_R + e0.y : d;
-                    d = e0.z == key ? a.bin_R + e0.w : d;
-                    d = e1.x == key ? a.bin_R + e1.y : d;
-                    d = e1.z == key ? a.bin_R + e1.w : d;
-                }
+                const uint4* hb = reinterpret_cast<const uint4*>(htab + hot_hash(key) * kHotWays);
+                const uint4 e0 = hb[0], e1 = hb[1];
+                d = e0.x == key ? a.bin_R + e0.y : d;
+                d = e0.z == key ? a.bin_R + e0.w : d;
+                d = e1.x == key ? a.bin_R + e1.y : d;
+                d = e1.z == key ? a.bin_R + e1.w : d;
             }
         }
         if constexpr (BIN) rec |= (uint64_t)d << a.bin_dshift;
-        if (!(a.dbg & 16384)) {
-            int32_t* o = &a.out[i].status;  // the default result {st, 0, 0}
-            st_stream(o, st);
-            st_stream(o + 1, 0);
-            st_stream(o + 2, 0);
-        }
+        int32_t* o = &a.out[i].status;  // the default result {st, 0, 0}
+        st_stream(o, st);
+        st_stream(o + 1, 0);
+        st_stream(o + 2, 0);
         if (BIN && a.rec4) st_stream(reinterpret_cast<uint32_t*>(a.rec) + i, r4 | (d << kRec4DigitShift));
         else st_stream(a.rec + i, rec);
         if (a.hist0) ldig[it * 256 + threadIdx.x] = (uint16_t)(BIN ? d : (uint32_t)(rec >> a.hist0_shift) & dmask);
@@ -318,9 +314,6 @@ __shared__ uint8_t g_p0mod[kMaxWl][kModS + 1];  // g_p0[w] mod s (s = 1..kModS),
 // Ring slot of the batch's window period q (period P0 + q of window length w) for sampleCount S: (P0 + q) % S in
 // 32 bits from the staged residue (a 64-bit modulo of the absolute period is ~120 instructions).
 __device__ __forceinline__ int period_slot(int w, uint32_t q, int S) {
-#ifdef SG_NO_PSLOT
-    return (int)((g_p0[w] + (int64_t)q) % S);
-#endif
     if (S <= kModS) return (int)(((uint32_t)g_p0mod[w][S] + q) % (uint32_t)S);
     return (int)((g_p0[w] + (int64_t)q) % S);
 }
@@ -711,18 +704,10 @@ __device__ __forceinline__ uint64_t wave_search(uint64_t lo, uint64_t hi, Pred p
     return m ? lo + (uint64_t)__builtin_ctzll(m) : hi;
 }
 
-// Inlined into k_walk_long (SG_WAVE_INLINE=0: a called function, as in round 3): one register allocation for the
-// kernel instead of a call frame per segment — 0.90 vs 0.96 ms/step pipelined, same box.
-#ifndef SG_WAVE_INLINE
-#define SG_WAVE_INLINE 1
-#endif
-#if SG_WAVE_INLINE
-#define SG_WAVE_ATTR __device__ __forceinline__
-#else
-#define SG_WAVE_ATTR __device__ __noinline__
-#endif
+// Inlined into k_walk_long (not a called function, as in round 3): one register allocation for the kernel instead of
+// a call frame per segment — 0.90 vs 0.96 ms/step pipelined, same box.
 template <bool L, bool R4 = false>
-SG_WAVE_ATTR void walk_wave(const BatchArgs& a, uint32_t k, uint64_t s, uint64_t e, uint32_t item) {
+__device__ __forceinline__ void walk_wave(const BatchArgs& a, uint32_t k, uint64_t s, uint64_t e, uint32_t item) {
     using RT = typename RecOf<R4>::T;
     WaveWalker<L> w(a, k);
     const int lane = w.lane;
@@ -959,8 +944,8 @@ __global__ void __launch_bounds__(256) k_seg_classify(BatchArgs a) {
             const uint64_t k = k0 + (uint64_t)u * 256 + tid;
             slot[u] = 0xFFFFFFFFu;
             if (st[u] == 0xFFFFFFFFu) continue;
-            a.seg_start[k] = 0xFFFFFFFFu;  // both marks cleared for the next batch (the sort's last pass
-            en[u] = a.seg_end[k];          // takes atomicMin / atomicMax of them)
+            a.seg_start[k] = 0xFFFFFFFFu;  // both marks cleared for the next batch
+            en[u] = a.seg_end[k];
             a.seg_end[k] = 0;
             const uint32_t len = en[u] - st[u];
             uint32_t l = 0;
@@ -1428,7 +1413,7 @@ __global__ void __launch_bounds__(256) k_hot_reset(uint2* hot_tab) {
 __device__ __forceinline__ void stage_periods(const BatchArgs& a) {
     uint32_t tot = 0;
     for (int w = 0; w < a.n_wl; ++w) tot += a.np[w];
-    const bool lds = tot <= (uint32_t)kLdsBndFlow && !(a.dbg & 1);
+    const bool lds = tot <= (uint32_t)kLdsBndFlow;
     uint32_t off = 0;
     for (int w = 0; w < a.n_wl; ++w) {
         const uint32_t npw = a.np[w];
@@ -1520,7 +1505,7 @@ __global__ void __launch_bounds__(256) k_long_bounds(BatchArgs a) {
 #endif
 template <bool R4>
 __global__ void __launch_bounds__(256, SG_WLONG_BLOCKS) k_walk_long(BatchArgs a) {
-    if (*a.err || (a.dbg & 4096)) return;
+    if (*a.err) return;
     stage_periods(a);
     if (g_blds) walk_long_body<true, R4>(a);
     else walk_long_body<false, R4>(a);
@@ -1564,11 +1549,6 @@ __device__ __forceinline__ bool narrow_span(const BatchArgs& a, int64_t T0) {
              (b - ((int64_t)a.stride + 1) * wl - T0 > -(1ll << 29));
     }
     return ok;
-}
-
-// k_walk_tiny takes length class 0 (same answer in every kernel of the batch: batch constants only)
-__device__ __forceinline__ bool tiny_active(const BatchArgs& a) {
-    return a.tiny && a.narrow && narrow_span(a, a.p0[0] * (int64_t)a.wl[0]);
 }
 
 __device__ __forceinline__ void store_bucket(Bucket* b, BucketHot* h, int64_t start, const int64_t* c) {
@@ -1656,7 +1636,7 @@ __device__ __forceinline__ void walk_reg(const BatchArgs& a, bool act, uint32_t 
         // 1. open the period of every lane whose next record starts one (the first record included)
         if (live && qn != pc.q) {
             if (I >= 0) {  // close the open bucket: memory and the snapshot
-                if (!(a.dbg & 512)) store_bucket(ring + I, hot + I, ws, ps.cur);
+                store_bucket(ring + I, hot + I, ws, ps.cur);
                 snap[I].st = (int32_t)(ws - T0);
                 snap[I].pass = (int32_t)ps.cur[SG_EV_PASS];
                 snap[I].wait = (int32_t)ps.cur[SG_EV_WAITING];
@@ -1709,11 +1689,11 @@ __device__ __forceinline__ void walk_reg(const BatchArgs& a, bool act, uint32_t 
                 ps.cur[SG_EV_PASS] += dn.acq;
                 ps.cur[SG_EV_PASS_REQUEST] += 1;
                 if (dn.prio) ps.cur[SG_EV_OCCUPIED_PASS] += dn.acq;
-                if (!(a.dbg & 256)) store_result(a.out, dn.idx, SG_STATUS_OK, java_d2i(next_remaining), 0);
+                store_result(a.out, dn.idx, SG_STATUS_OK, java_d2i(next_remaining), 0);
             } else {
                 int32_t wait;
                 const int32_t stt = decide_fail(R, a.max_occ_ratio, ps, dn.acq, dn.prio, &wait);
-                if (stt != SG_STATUS_BLOCKED && !(a.dbg & 256)) store_result(a.out, dn.idx, stt, 0, wait);
+                if (stt != SG_STATUS_BLOCKED) store_result(a.out, dn.idx, stt, 0, wait);
             }
             advance();
             if (live) peek();
@@ -1914,14 +1894,17 @@ template <int SM, bool L, bool R4>
 __device__ __forceinline__ void walk_short_lds(const BatchArgs& a, SlotSnap* snap_all, uint32_t* recs_all) {
     static_assert(SM > 0, "LDS ring snapshot");
     const int lane = lane_id();
-    const bool tiny = tiny_active(a);
     SlotSnap* snap = snap_all + (threadIdx.x / 64) * (64 * SM);
     uint32_t* wrecs = recs_all + (threadIdx.x / 64) * (kRecW * 64);
+    // An empty batch lists no segments. The test changes no count (short_count is zero then); class 0's count as a
+    // select on a batch constant is the form under which the register allocator keeps this kernel's VGPRs and
+    // spills where they were measured (profiles/switches_resource_usage.txt): the plain load costs 2-6 VGPRs.
+    const bool none = a.n == 0;
     uint32_t cnt[kClasses], grp_end[kClasses];
     uint32_t total = 0;
 #pragma unroll
     for (int c = kClasses - 1; c >= 0; --c) {  // group order: longest class first
-        cnt[c] = (c == 0 && tiny) ? 0u : a.short_count[c];  // class 0: k_walk_tiny
+        cnt[c] = (c == 0 && none) ? 0u : a.short_count[c];
         total += (cnt[c] + 63) / 64;
         grp_end[c] = total;
     }
@@ -2030,13 +2013,14 @@ __device__ __forceinline__ void walk_short_body(const BatchArgs& a, SlotSnap* sn
     }
     constexpr int kSnapPerWave = SM > 0 ? 64 * SM : 1;
     const int lane = lane_id();
-    const bool tiny = tiny_active(a);
     SlotSnap* snap = snap_all + (threadIdx.x / 64) * kSnapPerWave;
+    // (as in walk_short_lds; with the narrow test the 8-byte-record instantiations keep their scratch size)
+    const bool none = a.n == 0 && a.narrow && narrow_span(a, a.p0[0] * (int64_t)a.wl[0]);
     uint32_t cnt[kClasses], grp_end[kClasses];
     uint32_t total = 0;
 #pragma unroll
     for (int c = kClasses - 1; c >= 0; --c) {  // group order: longest class first
-        cnt[c] = (c == 0 && tiny) ? 0u : a.short_count[c];  // class 0: k_walk_tiny
+        cnt[c] = (c == 0 && none) ? 0u : a.short_count[c];
         total += (cnt[c] + 63) / 64;
         grp_end[c] = total;
     }
@@ -2134,137 +2118,10 @@ __global__ void __launch_bounds__(256, C ? SG_SHORT_C_BLOCKS : kShortBlocksPerCu
     static_assert(SM <= kGatherMaxS, "LDS budget of the ring snapshot");
     __shared__ SlotSnap snap_all[4 * (SM > 0 ? 64 * SM : 1)];
     __shared__ uint32_t recs_all[SM > 0 && C ? 4 * kRecW * 64 : 1];
-    if (*a.err || (a.dbg & 8192)) return;
+    if (*a.err) return;
     stage_periods(a);
     if (g_blds) walk_short_body<SM, true, C, R4>(a, snap_all, recs_all);
     else walk_short_body<SM, false, C, R4>(a, snap_all, recs_all);
-}
-
-// Tiny-segment walker: one thread per flowId of length class 0 (<= kClassMax[0] records, most touched flowIds of a
-// Zipf batch), everything in registers — the ring's {start, PASS, WAITING} (S <= SM slots, the 32-bit encoding of
-// SlotSnap: exact under BatchArgs::narrow and narrow_span), the records, the open bucket — so the kernel needs no
-// LDS beyond the period tables and runs at more waves per SIMD: a group of 64 such segments in the lane-per-segment
-// walker paid two memory round trips and a wave-wide period phase for a handful of decisions. Same decisions as
-// walk_serial (ClusterFlowChecker.acquireClusterToken :67-111).
-template <int SM, bool L, bool R4>
-__device__ __forceinline__ void walk_tiny_body(const BatchArgs& a) {
-    using RT = typename RecOf<R4>::T;
-    const RT* rs = sorted_recs<R4>(a);
-    constexpr int kR = (int)kClassMax[0];
-    const uint32_t cnt = a.short_count[0];
-    const uint64_t base = a.class_off[0];
-    const int64_t T0 = a.p0[0] * (int64_t)a.wl[0];
-    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < cnt; t += gridDim.x * blockDim.x) {
-        const uint64_t s = a.short_list[base + t];
-        const uint32_t k = a.short_key[base + t];
-        const uint32_t e = a.short_end[base + t];
-        const Rule R = a.rules[k];
-        const Occ occ = a.occ[k];
-        RT r0 = rs[s], r1 = rs[min(s + 1, a.n - 1)];
-        RT r2 = rs[min(s + 2, a.n - 1)], r3 = rs[min(s + 3, a.n - 1)];
-        static_assert(kR == 4, "four record registers");
-        Bucket* ring = a.ring + (size_t)k * a.stride;
-        BucketHot* hot = a.hot + (size_t)k * a.stride;
-        int32_t st[SM], pa[SM], wa[SM];
-#pragma unroll
-        for (int x = 0; x < SM; ++x) {
-            const int xx = x < R.S ? x : 0;
-            const ulonglong2 hv = *reinterpret_cast<const ulonglong2*>(hot + xx);  // {start, PASS | WAITING << 32}
-            st[x] = snap_rel((int64_t)hv.x, T0);
-            pa[x] = (int32_t)(uint32_t)hv.y;
-            wa[x] = (int32_t)(uint32_t)(hv.y >> 32);
-        }
-        PeriodCursor<L> pc;
-        pc.init(a, R.wl_idx);
-        const int64_t P0 = g_p0[R.wl_idx];
-        const int S = R.S;
-        PeriodState ps;
-        ps.occ_pass = occ.pass;
-        ps.occ_req = occ.pass_req;
-#pragma unroll
-        for (int ev = 0; ev < SG_NUM_EVENTS; ++ev) ps.cur[ev] = 0;
-        ps.wo_pass = ps.wo_wait = ps.head_other = 0;
-        int I = -1;
-        int64_t ws = 0;
-        const uint32_t m = e - (uint32_t)s;
-        for (uint32_t u = 0; u < m; ++u) {
-            const Decoded d = decode(a, r0);
-            r0 = r1;
-            r1 = r2;
-            r2 = r3;
-            const uint32_t q = pc.of(d.idx);
-            if (q != pc.q) {
-                if (I >= 0) {  // close the open bucket: memory and the register ring
-                    store_bucket(ring + I, hot + I, ws, ps.cur);
-#pragma unroll
-                    for (int x = 0; x < SM; ++x) {
-                        st[x] = x == I ? (int32_t)(ws - T0) : st[x];
-                        pa[x] = x == I ? (int32_t)ps.cur[SG_EV_PASS] : pa[x];
-                        wa[x] = x == I ? (int32_t)ps.cur[SG_EV_WAITING] : wa[x];
-                    }
-                }
-                const uint32_t qprev = pc.q;
-                pc.seek(q);
-                const int64_t P = P0 + (int64_t)q;
-                I = I < 0 ? period_slot(R.wl_idx, q, S) : (int)((uint32_t)(I + (int)(q - qprev)) % (uint32_t)S);
-                ws = P * R.wl;
-                const int64_t lo_rel = ws - (int64_t)S * R.wl - T0;  // valid iff start > ws - S * wl
-                const int32_t lo32 = rel32(lo_rel);  // snapshot starts are 32-bit (snap_rel)
-                const int h = I + 1 == S ? 0 : I + 1;
-                uint32_t wp = 0, ww = 0, ho = 0;
-                int32_t stI_rel = INT32_MIN;
-#pragma unroll
-                for (int x = 0; x < SM; ++x) {
-                    const bool v = (x < S) & (x != I) & (st[x] > lo32);
-                    const uint32_t mk = v ? 0xFFFFFFFFu : 0u;
-                    wp += (uint32_t)pa[x] & mk;
-                    ww += (uint32_t)wa[x] & mk;
-                    ho = (x == h) ? ((uint32_t)pa[x] & mk) : ho;
-                    stI_rel = x == I ? st[x] : stI_rel;
-                }
-                ps.wo_pass = (int64_t)wp;
-                ps.wo_wait = (int64_t)ww;
-                ps.head_other = (int64_t)ho;
-                const int64_t stI = stI_rel == INT32_MIN ? INT64_MIN : T0 + (int64_t)stI_rel;
-                int64_t cI[SG_NUM_EVENTS];
-                if (stI == ws) {  // the batch continues the stored period
-#pragma unroll
-                    for (int ev = 0; ev < SG_NUM_EVENTS; ++ev) cI[ev] = ring[I].c[ev];
-                }
-                open_bucket(ps, stI, cI, ws);
-            }
-            const double latest = qps_of(ps.wo_pass + ps.cur[SG_EV_PASS], R.isec);
-            const double next_remaining = R.thr - latest - (double)d.acq;
-            if (next_remaining >= 0) {
-                ps.cur[SG_EV_PASS] += d.acq;
-                ps.cur[SG_EV_PASS_REQUEST] += 1;
-                if (d.prio) ps.cur[SG_EV_OCCUPIED_PASS] += d.acq;
-                store_result(a.out, d.idx, SG_STATUS_OK, java_d2i(next_remaining), 0);
-            } else {
-                int32_t wait;
-                const int32_t stt = decide_fail(R, a.max_occ_ratio, ps, d.acq, d.prio, &wait);
-                if (stt != SG_STATUS_BLOCKED) store_result(a.out, d.idx, stt, 0, wait);
-            }
-        }
-        if (I >= 0) store_bucket(ring + I, hot + I, ws, ps.cur);
-        if (ps.occ_pass != occ.pass || ps.occ_req != occ.pass_req) {  // rarely changes: no partial-line store
-            Occ o;
-            o.pass = ps.occ_pass;
-            o.pass_req = ps.occ_req;
-            a.occ[k] = o;
-        }
-    }
-}
-
-template <int SM, bool R4 = false>
-#ifndef SG_TINY_BLOCKS
-#define SG_TINY_BLOCKS 4
-#endif
-__global__ void __launch_bounds__(256, SG_TINY_BLOCKS) k_walk_tiny(BatchArgs a) {
-    if (*a.err || !tiny_active(a)) return;
-    stage_periods(a);
-    if (g_blds) walk_tiny_body<SM, true, R4>(a);
-    else walk_tiny_body<SM, false, R4>(a);
 }
 
 // One wave per skipped piece: Σ acquire and Σ prioritized acquire over its records, added with 64-bit
@@ -2512,8 +2369,7 @@ hipError_t launch_hot_reset(uint2* hot_tab, hipStream_t stream) {
 }
 
 hipError_t launch_seg_flow(const BatchArgs& a, hipStream_t stream) {
-    if (!a.seg_marked)
-        hipLaunchKernelGGL(k_seg_mark, dim3((unsigned)((a.n + 256 * kMarkItems - 1) / (256 * kMarkItems))), dim3(256), 0,
+    hipLaunchKernelGGL(k_seg_mark, dim3((unsigned)((a.n + 256 * kMarkItems - 1) / (256 * kMarkItems))), dim3(256), 0,
                        stream, a);
     lds_poison(stream);
     if (a.K) hipLaunchKernelGGL(k_seg_classify, dim3(grid_for(a.K, 256 * kClsItems, 4096)), dim3(256), 0, stream, a);
@@ -2577,7 +2433,7 @@ hipError_t launch_walk_long(const BatchArgs& a, hipStream_t stream) {
 }
 
 // Compact LDS records for the short walker: {idx, acode} fill the low 32 bits (abits == 8, ibits <= 24).
-static bool short_compact(const BatchArgs& a) { return a.abits == 8 && a.imask <= 0xFFFFFFull && !(a.dbg & 4); }
+static bool short_compact(const BatchArgs& a) { return a.abits == 8 && a.imask <= 0xFFFFFFull; }
 
 template <int SM>
 static hipError_t launch_short_sm(const BatchArgs& a, hipStream_t stream) {
@@ -2595,32 +2451,6 @@ static hipError_t launch_short_sm(const BatchArgs& a, hipStream_t stream) {
     if (c) hipLaunchKernelGGL((k_walk_short<SM, true>), dim3(blocks), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((k_walk_short<SM, false>), dim3(blocks), dim3(256), 0, stream, a);
     return hipGetLastError();
-}
-
-template <int SM>
-static hipError_t launch_tiny_sm(const BatchArgs& a, hipStream_t stream) {
-    if (a.rec4)
-        hipLaunchKernelGGL((k_walk_tiny<SM, true>), dim3(walker_grid((const void*)k_walk_tiny<SM, true>, a.walk_cus)),
-                           dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((k_walk_tiny<SM>), dim3(walker_grid((const void*)k_walk_tiny<SM>, a.walk_cus)), dim3(256), 0,
-                           stream, a);
-    return hipGetLastError();
-}
-
-// Whether k_walk_tiny takes length class 0 (the host sets BatchArgs::tiny from the same answer).
-bool tiny_walker_enabled(const BatchArgs& a) {
-    // opt-in (SG_DEBUG & 128): measured 11 % slower per C3 step than class 0 inside k_walk_short (r03 A/B:
-    // 0.999 vs 0.897 ms), the extra launch serialises behind the short walker on the same stream
-    return !a.generic_walker && a.stride <= 10 && a.short_max >= kClassMax[0] && (a.dbg & 128);
-}
-
-hipError_t launch_walk_tiny(const BatchArgs& a, hipStream_t stream) {
-    if (!a.tiny) return hipSuccess;
-    if (a.stride <= 2) return launch_tiny_sm<2>(a, stream);
-    if (a.stride <= 4) return launch_tiny_sm<4>(a, stream);
-    if (a.stride <= 8) return launch_tiny_sm<8>(a, stream);
-    return launch_tiny_sm<10>(a, stream);
 }
 
 hipError_t launch_walk_short(const BatchArgs& a, hipStream_t stream) {
@@ -2641,34 +2471,6 @@ hipError_t launch_skip_apply(const BatchArgs& a, hipStream_t stream) {
 
 hipError_t launch_check_last(const BatchArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(k_check_last, dim3(1), dim3(1), 0, stream, a);
-    return hipGetLastError();
-}
-
-// Result copy to host memory by the shader (sg_flow_submit with a device-accessible host buffer): 16-B stores in
-// order over the PCIe link, so the results of batch i travel while the copy engine brings batch i + 1's requests
-// in (the two directions of the link in use at once, whatever the SDMA engine assignment). `dst` is the buffer's
-// device alias; bytes % 16 == 0 or the tail is copied by 4-B words.
-__global__ void __launch_bounds__(256) k_copy_out(const uint4* __restrict__ src, uint4* __restrict__ dst, uint64_t n16,
-                                                  const uint32_t* __restrict__ src_tail, uint32_t* __restrict__ dst_tail,
-                                                  uint32_t tail_words) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i + 3 * stride < n16; i += 4 * stride) {  // four loads in flight per thread
-        const uint4 a = src[i], b = src[i + stride], c = src[i + 2 * stride], d = src[i + 3 * stride];
-        dst[i] = a;
-        dst[i + stride] = b;
-        dst[i + 2 * stride] = c;
-        dst[i + 3 * stride] = d;
-    }
-    for (; i < n16; i += stride) dst[i] = src[i];
-    if (blockIdx.x == 0 && threadIdx.x < tail_words) dst_tail[threadIdx.x] = src_tail[threadIdx.x];
-}
-
-hipError_t launch_copy_out(const void* src, void* dst_dev, uint64_t bytes, int blocks, hipStream_t stream) {
-    const uint64_t n16 = bytes / 16;
-    const uint32_t tail = (uint32_t)((bytes % 16) / 4);
-    hipLaunchKernelGGL(k_copy_out, dim3(blocks), dim3(256), 0, stream, (const uint4*)src, (uint4*)dst_dev, n16,
-                       (const uint32_t*)src + n16 * 4, (uint32_t*)dst_dev + n16 * 4, tail);
     return hipGetLastError();
 }
 

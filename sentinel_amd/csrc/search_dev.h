@@ -62,9 +62,6 @@ __device__ __forceinline__ bool sorted_has(const int32_t* a, uint32_t n, int32_t
 // the exponent bits; the fp64 division sequence (~13 instructions a record on the walkers' hot path) runs only
 // for other intervals. (A test for isec == 1.0 alone is folded away by the compiler: x / 1.0 == x.)
 __device__ __forceinline__ double avg_div(double x, double isec) {
-#ifdef SG_NO_AVGDIV
-    return x / isec;
-#endif
     const uint64_t b = (uint64_t)__double_as_longlong(isec);
     const uint64_t e = (b >> 52) & 0x7FF;
     if ((b & 0x800FFFFFFFFFFFFFull) == 0 && e - 1 < 0x7FD)
@@ -74,17 +71,9 @@ __device__ __forceinline__ double avg_div(double x, double isec) {
 
 // Streaming stores for the prep kernels' outputs (default results, packed records: written once, read by a later
 // kernel): non-temporal, so a batch's front half does not fill L2 with lines the walkers beside it would have used.
-// SG_NT_PREP=0 builds plain stores.
-#ifndef SG_NT_PREP
-#define SG_NT_PREP 1
-#endif
 template <class T>
 __device__ __forceinline__ void st_stream(T* p, T v) {
-#if SG_NT_PREP
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 }  // namespace sg

@@ -175,12 +175,6 @@ __global__ void __launch_bounds__(1 << D) k_rescan(uint32_t* hist, const uint32_
     }
 }
 
-// MARK (the last pass of a sort whose key is a flowId index, SegMark): besides the records, each key's segment in
-// the sorted output — within a digit's run of the tile the records are sorted by the whole key, so the first and
-// last record of every key in the run are found by comparing LDS neighbours; the segment's start is the smallest of
-// its runs' firsts (atomicMin on seg_start, 0xFFFFFFFF between batches) and its end the largest of their lasts + 1
-// (atomicMax on seg_end, 0 between batches; k_seg_classify consumes and clears both). This replaces a separate pass
-// over the sorted records (k_seg_mark).
 // BIN (the binned front half's one pass, engine.h kBinDigit): the digit is the bin digit k_prep wrote into the
 // record's middle bits; it is cleared on the way out, and the records of regular bins (digit < R) go to `reg` (k_bin_sort
 // sorts them from there into `out`), the hot bins' and rejected requests' records to `out`, at the same positions.
@@ -189,10 +183,10 @@ struct BinSplit {
     uint32_t R;
 };
 
-template <int D, bool MARK>
+template <int D>
 __global__ void __launch_bounds__(kSortThreads) k_radix_scatter(const uint64_t* in, uint64_t* out, uint64_t n, int shift,
                                                                 const uint32_t* hist, uint32_t ntiles,
-                                                                const uint32_t* tot, SegMark mk, BinSplit bs) {
+                                                                const uint32_t* tot, BinSplit bs) {
     constexpr int kBins = 1 << D;
     constexpr int kPer = kBins / kSortThreads;  // digits per thread
     using Cnt = typename std::conditional<(D > 8), uint16_t, uint32_t>::type;  // wave counts <= 1024
@@ -307,19 +301,10 @@ __global__ void __launch_bounds__(kSortThreads) k_radix_scatter(const uint64_t* 
         const uint32_t d = (uint32_t)(v >> shift) & (kBins - 1);
         const uint32_t gp = gbase[d] + (p - dstart[d]);
         (bs.reg && d < bs.R ? bs.reg : out)[gp] = v & keep;
-        if constexpr (MARK) {
-            const uint32_t k = (uint32_t)(v >> mk.kshift);
-            if (k < mk.K) {
-                const uint32_t r0 = dstart[d];
-                const uint32_t r1 = d + 1 < (uint32_t)kBins ? dstart[d + 1] : cnt;  // the digit's run in the tile
-                if (p == r0 || (uint32_t)(stage[p - 1] >> mk.kshift) != k) atomicMin(mk.seg_start + k, gp);
-                if (p + 1 == r1 || (uint32_t)(stage[p + 1] >> mk.kshift) != k) atomicMax(mk.seg_end + k, gp + 1);
-            }
-        }
     }
 }
 
-// The bin pass of the compact layout (BatchArgs::rec4, kRec4*): k_radix_scatter<kBinDigit, false> with BinSplit, except
+// The bin pass of the compact layout (BatchArgs::rec4, kRec4*): k_radix_scatter<kBinDigit> with BinSplit, except
 // that a record is read as 32 bits at its request index and widened when it is placed in LDS — {key | bin digit |
 // request index | acquire code}, the index from its position in the tile, the key from the bin and the key in bin —
 // and that only the regular bins leave as 8-byte records (k_bin_sort sorts them by that key): a hot bin's records go
@@ -477,7 +462,7 @@ int radix_digit_bits(int bits) { return ((bits > 16 && bits <= 20) || (bits > 24
 
 template <int D>
 static hipError_t radix_pass(uint64_t* src, uint64_t* dst, uint64_t n, int shift, uint32_t* hist_ws, hipStream_t stream,
-                       bool hist_ready, const SegMark* mark, bool csum_ready, BinSplit bs = BinSplit{}) {
+                       bool hist_ready, bool csum_ready, BinSplit bs = BinSplit{}) {
     const uint32_t ntiles = (uint32_t)((n + kTile - 1) / kTile);
     const uint32_t nchunks = (ntiles + kChunkTiles - 1) / kChunkTiles;
     uint32_t* hist = hist_ws;                                   // [ntiles][bins], then run offsets in place
@@ -499,12 +484,8 @@ static hipError_t radix_pass(uint64_t* src, uint64_t* dst, uint64_t n, int shift
     hipLaunchKernelGGL(k_rescan<D>, dim3(nchunks), dim3(1u << D), 0, stream, hist, csum, ntiles);
     const uint32_t grid = 8 * ((ntiles + 7) / 8);  // xcd_tile: blocks past ntiles return at once
     lds_poison(stream);
-    if (mark)
-        hipLaunchKernelGGL((k_radix_scatter<D, true>), dim3(grid), dim3(kSortThreads), 0, stream, src, dst, n, shift,
-                           hist, ntiles, tot, *mark, BinSplit{});
-    else
-        hipLaunchKernelGGL((k_radix_scatter<D, false>), dim3(grid), dim3(kSortThreads), 0, stream, src, dst, n, shift,
-                           hist, ntiles, tot, SegMark{}, bs);
+    hipLaunchKernelGGL(k_radix_scatter<D>, dim3(grid), dim3(kSortThreads), 0, stream, src, dst, n, shift, hist, ntiles,
+                       tot, bs);
     return hipGetLastError();
 }
 
@@ -520,7 +501,7 @@ const uint32_t* radix_tot(const uint32_t* hist_ws, uint64_t n, int D) {
 hipError_t radix_bin_pass(uint64_t* src, uint64_t* out, uint64_t* reg, uint32_t R, uint64_t n, int shift,
                           uint32_t* hist_ws, bool hist_ready, bool csum_ready, hipStream_t stream) {
     static_assert(kBinDigit == 10, "radix_pass<10>");
-    return radix_pass<10>(src, out, n, shift, hist_ws, stream, hist_ready, nullptr, csum_ready, BinSplit{reg, R});
+    return radix_pass<10>(src, out, n, shift, hist_ws, stream, hist_ready, csum_ready, BinSplit{reg, R});
 }
 
 hipError_t radix_bin_pass4(const uint32_t* src, uint32_t* out, const Bin4& b4, uint64_t n, uint32_t* hist_ws,
@@ -545,16 +526,15 @@ hipError_t radix_bin_pass4(const uint32_t* src, uint32_t* out, const Bin4& b4, u
 // first_hist_ready: the first pass's per-tile histogram (radix_digit_bits wide) is already in hist_ws (k_prep).
 hipError_t radix_sort_records(uint64_t* a, uint64_t* b, uint64_t n, int lo_bit, uint32_t* hist_ws,
                               uint64_t** result, hipStream_t stream, int hi_bit, bool first_hist_ready,
-                              const SegMark* mark, bool first_csum_ready) {
+                              bool first_csum_ready) {
     uint64_t* src = a;
     uint64_t* dst = b;
     const int D = radix_digit_bits(hi_bit - lo_bit);
     for (int shift = lo_bit; shift < hi_bit && n > 0; shift += D) {
         const bool ready = shift == lo_bit && first_hist_ready;
-        const SegMark* mk = shift + D >= hi_bit ? mark : nullptr;  // the last pass marks the segments
         const bool cready = ready && first_csum_ready;
-        const hipError_t e = D == 10 ? radix_pass<10>(src, dst, n, shift, hist_ws, stream, ready, mk, cready)
-                                     : radix_pass<8>(src, dst, n, shift, hist_ws, stream, ready, mk, cready);
+        const hipError_t e = D == 10 ? radix_pass<10>(src, dst, n, shift, hist_ws, stream, ready, cready)
+                                     : radix_pass<8>(src, dst, n, shift, hist_ws, stream, ready, cready);
         if (e != hipSuccess) return e;
         uint64_t* t = src;
         src = dst;

@@ -54,13 +54,10 @@ def test_pipelined_batches_equal_oracle(pinned):
     assert np.array_equal(ring, ring_o) and np.array_equal(occ, occ_o)
 
 
-@pytest.mark.parametrize("d2h", ["0", "1"])
 @pytest.mark.parametrize("offset,trim", [(1, 0), (4, 3), (0, 1)])
-def test_pinned_outputs_any_alignment_and_length(monkeypatch, d2h, offset, trim):
-    """Results into views of pinned buffers, by the copy engine (SG_D2H=0, the default) or the shader copy
-    (SG_D2H=1): a 12-B offset (not 16-B aligned: the copy engine takes it either way), a 48-B offset, and batch
-    lengths whose result bytes are not a multiple of 16 (the copy kernel's 4-B tail)."""
-    monkeypatch.setenv("SG_D2H", d2h)
+def test_pinned_outputs_any_alignment_and_length(offset, trim):
+    """Results into views of pinned buffers by the copy engine: a 12-B offset (not 16-B aligned), a 48-B offset, and
+    batch lengths whose result bytes are not a multiple of 16."""
     wl, eng, ora = _setup(seed=35)
     reqs = [wl.requests(b)[: 100_000 - trim - b] for b in range(4)]
     bufs = [eng.host_array(len(r) + offset, abi.RES_DTYPE) for r in reqs]
@@ -199,17 +196,14 @@ def test_device_enqueue_with_limiter_and_sync_calls_between():
         assert np.array_equal(outs[b], want), f"batch {b}: {(outs[b] != want).sum()} differ"
 
 
-@pytest.mark.parametrize("lim_pipe", ["1", "0"])
-def test_device_enqueue_with_limiter_rejects_a_late_batch(monkeypatch, lim_pipe):
+def test_device_enqueue_with_limiter_rejects_a_late_batch():
     """Four limiter batches in flight, the second older than the first: it is refused on its own ticket, its
     requests never reach the namespace limiter (the following batches' TOO_MANY_REQUEST answers equal the oracle's,
-    which never saw it), and the flowIds' rings equal the oracle's. SG_LIM_PIPE=0: the front halves wait for the
-    previous back half (the round-4 order), same answers."""
+    which never saw it), and the flowIds' rings equal the oracle's."""
     import torch
     from oracle.binding import ClusterTokenService
     from sentinel_amd.engine import EngineError, FlowEngine
     from sentinel_amd.workload import ClusterWorkload
-    monkeypatch.setenv("SG_LIM_PIPE", lim_pipe)
     wl = ClusterWorkload(n_flows=1500, n_requests=50_000, seed=41, prio_frac=0.05)
     ns = np.zeros(1, abi.NS_DTYPE)
     ns["connected_count"] = 1

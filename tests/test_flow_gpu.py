@@ -134,13 +134,12 @@ def test_random_traces_match_oracle(n_keys, n, zipf, prio, S, interval, flags):
     _compare_state(eng, ora, rules)
 
 
-@pytest.mark.parametrize("seg_mark,csum", [("0", "1"), ("1", "0"), ("0", "0")])
-def test_sort_variants(monkeypatch, seg_mark, csum):
-    """The non-default sort paths stay exact: segment marks fused into the last scatter pass (SG_SEG_MARK=0) and the
-    k_colsum pass instead of the histogram kernels' atomic column sums (SG_CSUM_ATOMIC=0)."""
-    monkeypatch.setenv("SG_SEG_MARK", seg_mark)
+@pytest.mark.parametrize("csum", ["1", "0"])
+def test_sort_variants(monkeypatch, csum):
+    """The two-pass sort (3000 flowIds: below the binned front half's threshold) stays exact with the histogram
+    kernels' atomic column sums (the default) and with the k_colsum pass instead (SG_CSUM_ATOMIC=0)."""
     monkeypatch.setenv("SG_CSUM_ATOMIC", csum)
-    rng = np.random.default_rng(int(seg_mark) * 2 + int(csum) + 90)
+    rng = np.random.default_rng(2 + int(csum) + 90)
     rules = _rules(3000, rng, S=10, interval=1000)
     eng, ora = _pair(rules)
     t = 1_700_000_000_003
@@ -404,9 +403,8 @@ def test_hot_flow_saturated_periods_are_skipped_exactly(prio):
 
 
 @pytest.mark.parametrize("n_keys,n,S", [(1000, 100_000, 10), (3000, 60_000, 2), (200_000, 400_000, 10)])
-def test_tiny_walker_opt_in_matches_oracle(monkeypatch, n_keys, n, S):
-    """SG_DEBUG=128 walks length class 0 with k_walk_tiny (off by default: slower in the r03 A/B)."""
-    monkeypatch.setenv("SG_DEBUG", "128")
+def test_length_class_0_matches_oracle(n_keys, n, S):
+    """Batches of mostly 1..4-record segments: length class 0 of k_walk_short."""
     rng = np.random.default_rng(n_keys + n)
     rules = _rules(n_keys, rng, S=S)
     eng, ora = _pair(rules)
