@@ -200,7 +200,8 @@ typedef struct sg_pslot_arg {    /* one argument: null, a value, or a collection
     uint32_t value_begin;
     uint32_t value_count;
     int32_t  kind;               /* SG_ARG_*                                                              */
-    int32_t  reserved;
+    int32_t  reserved;           /* SG_ARG_COLLECTION: the caller's label id of the collection's String.valueOf, read
+                                    only by the block log (sg_local_block_log, SG_BLOCK_APP_LABEL); 0 = unlabelled */
 } sg_pslot_arg;
 typedef struct sg_pslot_event {  /* an entry (SphU.entry) or the exit of a passed entry (its own arguments) */
     int64_t  ts_ms;
@@ -840,6 +841,59 @@ int sg_local_set_entry_types(sg_handle* h, const uint8_t* inbound, uint32_t n);
 int sg_local_read_origin_state(sg_handle* h, uint32_t res, int32_t origin, int64_t* second, int64_t* borrow,
                                int64_t* minute, int64_t* head);
 int sg_local_read_controller(sg_handle* h, uint32_t rule, int64_t* state3);
+
+/* ---- LogSlot: sentinel-block.log (core/slots/logger/LogSlot.java:35-47, EagleEyeLogUtil.java:31-45) ----
+ * LogSlot.entry catches every BlockException of the slots behind it and calls statLogger.stat(resource,
+ * exception class, e.getRuleLimitApp(), context origin).count(count): a per-second rollup (StatLogger /
+ * StatRollingData, time slot t - t % 1000) with one COUNT_SUM entry per key, written as one line per entry
+ * `time|1|resource,ExceptionName,ruleLimitApp,origin|count,0` (StatLogWriteTask.run). PriorityWaitException and exits
+ * never reach it. The device keeps that rollup across batches in an exact table in device memory and hands out rows.
+ *   sg_local_block_log_enable ← the StatLogger's creation: a table of 2^capacity_log2 rows (4..24), and every local
+ *     batch decided from then on (sg_local_decide_batch, sg_slot_decide_batch, their _host forms, sg_local_enqueue) adds
+ *     its blocked entries behind its walkers. Allowed at any time, before or after the rules and the first batches
+ *     (rows record only what was decided after it); a second call with the same capacity does nothing, with another
+ *     SG_E_INVAL. The table outlives every rule reload (pending rows keep the caller's ids). A handle that never calls
+ *     it runs exactly the kernels it ran before.
+ *   sg_local_block_log ← the rolling task (StatLogWriteTask) at now_ms: every row whose second is complete
+ *     (timestamp + 1000 <= now_ms - now_ms % 1000) into HOST memory, sorted by (timestamp, resource, status, app_kind,
+ *     app, origin), and removed from the table. cap too small: SG_E_CAPACITY, *n_rows = the rows needed, nothing
+ *     changes (the lost totals included). now_ms may lie behind the latest decided event: only complete seconds leave.
+ *     SG_E_INVAL before sg_local_block_log_enable. A blocked entry whose key found no free row is not logged and never
+ *     changes a decision: it is counted in *lost_events and its count in *lost_count, reported by the next successful
+ *     call and cleared by it. One row per key and second (the reference's maxEntryCount = 6000 rolls the map early,
+ *     so a key can have several lines in a second: summed per key and second they equal the row).
+ * ruleLimitApp by class (app_kind says how to read app):
+ *   FlowException     SG_BLOCK_APP_LIMIT_APP  limit_app of the rule that failed (int32 in the low word:
+ *                                             SG_LIMIT_APP_DEFAULT, SG_LIMIT_APP_OTHER or an origin id)
+ *   DegradeException  SG_BLOCK_APP_LIMIT_APP  always SG_LIMIT_APP_DEFAULT: sg_degrade_rule carries no limitApp
+ *   AuthorityException SG_BLOCK_APP_ORIGIN    the entry's origin id (0 = "")
+ *   SystemBlockException SG_BLOCK_APP_SYSTEM  SG_SYSTEM_* (the two-argument constructor passes the limit type on as
+ *                                             ruleLimitApp, SystemBlockException.java)
+ *   ParamFlowException (ParamFlowSlot.java:81-91: String.valueOf(args[rule.getParamIdx()]) after applyRealParamIdx)
+ *                     SG_BLOCK_APP_VALUE      a scalar argument's value id
+ *                     SG_BLOCK_APP_NULL_ARG   a null argument: "null"
+ *                     SG_BLOCK_APP_NO_ARG     args.length <= paramIdx: ""
+ *                     SG_BLOCK_APP_LABEL      a collection / array argument: sg_pslot_arg.reserved, the caller's id of
+ *                                             the collection's String.valueOf (0 = unlabelled) */
+#define SG_BLOCK_APP_LIMIT_APP 0
+#define SG_BLOCK_APP_ORIGIN    1
+#define SG_BLOCK_APP_SYSTEM    2
+#define SG_BLOCK_APP_VALUE     3
+#define SG_BLOCK_APP_NULL_ARG  4
+#define SG_BLOCK_APP_NO_ARG    5
+#define SG_BLOCK_APP_LABEL     6
+typedef struct sg_block_row {
+    int64_t  timestamp;           /* the second: t - t % 1000                                   */
+    int64_t  count;               /* sum of the blocked entries' acquireCount                   */
+    uint64_t app;                 /* ruleLimitApp, read by app_kind                             */
+    uint32_t resource;
+    int32_t  origin;              /* Context origin id, 0 = ""                                  */
+    int32_t  status;              /* SG_LOCAL_BLOCK_*: the exception class                      */
+    int32_t  app_kind;            /* SG_BLOCK_APP_*                                             */
+} sg_block_row;
+int sg_local_block_log_enable(sg_handle* h, int32_t capacity_log2);
+int sg_local_block_log(sg_handle* h, int64_t now_ms, sg_block_row* rows, uint64_t cap, uint64_t* n_rows,
+                       uint64_t* lost_events, uint64_t* lost_count);
 
 /* ---- the node handle: one token server over G shard handles (SURVEY §8(b) "multi-GPU fan-out is internal to the
  * handle", §8(e) flowIds hashed over the GPUs) ----

@@ -173,6 +173,12 @@ SYSTEM_RULE_DTYPE = np.dtype([("highest_system_load", "<f8"), ("highest_cpu_usag
                               ("avg_rt", "<i8"), ("max_thread", "<i8")], align=True)
 assert SYSTEM_RULE_DTYPE.itemsize == 40
 ENTRY_NODE_RESOURCE = 0xFFFFFFFF  # sg_local_metrics rows of Constants.ENTRY_NODE
+# LogSlot's rollup (sg_local_block_log): one sentinel-block.log row; app is read by app_kind
+BLOCK_ROW_DTYPE = np.dtype([("timestamp", "<i8"), ("count", "<i8"), ("app", "<u8"), ("resource", "<u4"),
+                            ("origin", "<i4"), ("status", "<i4"), ("app_kind", "<i4")], align=True)
+assert BLOCK_ROW_DTYPE.itemsize == 40
+(BLOCK_APP_LIMIT_APP, BLOCK_APP_ORIGIN, BLOCK_APP_SYSTEM, BLOCK_APP_VALUE, BLOCK_APP_NULL_ARG, BLOCK_APP_NO_ARG,
+ BLOCK_APP_LABEL) = range(7)
 CONTROL_DEFAULT, CONTROL_WARM_UP, CONTROL_RATE_LIMITER, CONTROL_WARM_UP_RATE_LIMITER = 0, 1, 2, 3
 LIMIT_APP_DEFAULT, LIMIT_APP_OTHER = 0, -1
 STRATEGY_DIRECT, STRATEGY_RELATE, STRATEGY_CHAIN = 0, 1, 2

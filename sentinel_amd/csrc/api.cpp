@@ -12,6 +12,7 @@
 #include <string>
 #include <unordered_map>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "devmem.h"
@@ -273,6 +274,14 @@ struct sg_handle {
     DevBuf<LBucket> d_lentry_acc;     // [60] the ENTRY_NODE's buckets, summed per metric call
     DevBuf<unsigned long long> d_lm_cnt;     // the metric passes' row counter
     DevBuf<int64_t> d_lentry_fetch;   // the ENTRY_NODE's lastFetchTime
+    // LogSlot's rollup (sg_local_block_log_enable; null d_blog: off)
+    DevBuf<BlogSlot> d_blog;          // the table, 2^blog_log2 slots; outlives every rule reload
+    int32_t blog_log2 = 0;
+    DevBuf<unsigned long long> d_blog_ctr;  // {lost entries, lost count, rows taken, rows kept}
+    DevBuf<sg_block_row> d_blog_rows, d_blog_keep;  // [slots] the fetch's complete rows / survivors
+    DevBuf<int32_t> d_blog_app;       // [max_batch] LArgs::blog_app
+    DevBuf<int32_t> d_lres_app;       // [K] LArgs::res_app
+    std::vector<int32_t> l_res_app;   // its host copy (blocklog_rules.h), kept whether or not the log is on
 
     int kbits = 0, ibits = 0, abits = 0;
     int32_t shard_rank = 0, shard_world = 1;  // sg_set_shard: this handle's share of a node's flowIds
@@ -2867,6 +2876,21 @@ int sg_cparam_top_values(sg_handle* h, int64_t now_ms, uint32_t number, uint64_t
 
 // ------------------------------------------------------------------------------ local slot chain
 
+namespace {
+// LArgs::res_app on the device from h->l_res_app (nothing while the block log is off). The caller has drained the
+// pipeline: no batch in flight reads the old table.
+int blog_sync_apps(sg_handle* h) {
+    if (!h->d_blog) return SG_OK;
+    const size_t K = h->l_res_app.size();
+    DevBuf<int32_t> d;
+    if (!d.alloc(K ? K : 1)) return fail(h, SG_E_NOMEM, "block log limitApp table");
+    if (K) HIP_TRY(h, hipMemcpy(d, h->l_res_app.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->d_lres_app = std::move(d);
+    return SG_OK;
+}
+}  // namespace
+
 int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local_rule* rules, uint32_t n) {
     if (!h || !cfg || (!rules && n)) return SG_E_INVAL;
     if (n >= SG_KEY_BAD) return fail(h, SG_E_INVAL, "too many resources");
@@ -2954,6 +2978,11 @@ int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local
     HIP_TRY(h, hipMemcpy(h->d_llast_ts, &neg, sizeof(neg), hipMemcpyHostToDevice));
     h->lcfg = *cfg;
     h->ltab = tab;
+    h->l_res_app.assign(n, SG_LIMIT_APP_DEFAULT);  // no flow rule list yet: every FlowException is the one rule's
+    {
+        const int rc = blog_sync_apps(h);
+        if (rc) return rc;
+    }
     if (n) {
         if (!h->d_lrules.alloc_bytes(sizeof(LRule) * n) || !h->d_lhead.alloc_bytes(sizeof(LHead) * n) ||
             !h->d_lsec.alloc_bytes(sizeof(LBucket) * (size_t)n * cfg->sample_count) ||
@@ -3283,6 +3312,14 @@ int local_bufs(sg_handle* h, int x, LocalBufs& b) {
     return SG_OK;
 }
 
+BlogArgs blog_args(sg_handle* h) {
+    BlogArgs b{};
+    b.tab = h->d_blog;
+    b.mask = h->d_blog.size() - 1;
+    b.lost = h->d_blog_ctr;
+    return b;
+}
+
 // The kernels' arguments of a local batch on workspace buffers b (node tracking set up by the caller).
 int local_args(sg_handle* h, const LocalBufs& b, const sg_local_event* ev, const sg_slot_ext* ext, uint64_t n,
                const sg_pslot_arg* args, uint64_t n_args, const uint64_t* values, uint64_t n_values, sg_local_result* out,
@@ -3374,6 +3411,10 @@ int local_args(sg_handle* h, const LocalBufs& b, const sg_local_event* ev, const
         L.auth = h->d_lauth;
         L.auth_ids = h->d_lauth_ids;
         L.auth_rej = b.lw->auth_rej;
+    }
+    if (h->d_blog) {  // the block log: cx_entry's side word and the per-resource limitApps
+        L.blog_app = h->d_blog_app;
+        L.res_app = h->d_lres_app;
     }
     L.flags = b.lw->flags;
     L.cxw_next = b.lw->cxw_next;
@@ -3581,6 +3622,7 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
         HIP_TRY(h, launch_sys_apply(SA, stream));
     }
     if (h->stats_on) HIP_TRY(h, hipEventRecord(h->ev[3], stream));
+    if (h->d_blog) HIP_TRY(h, launch_blog_add(L, blog_args(h), stream));  // LogSlot, behind the decisions
     HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     if (h->stats_on) {
         HIP_TRY(h, hipMemcpyAsync(h->h_long, h->ws[0].counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -3640,6 +3682,9 @@ int enqueue_local_pipelined(sg_handle* h, const sg_local_event* ev, uint64_t n, 
     HIP_TRY(h, hipEventRecord(h->front_done[x], h->s_front));
     HIP_TRY(h, hipStreamWaitEvent(h->s_back, h->front_done[x], 0));
     HIP_TRY(h, launch_local_back(L, sgm, h->l_has_cx || h->l_has_cx_ps, h->s_aux2, h->s_back, h->pfork, h->pjoin));
+    // LogSlot on s_back, behind this batch's walkers and before back_done: the next batch's walkers (s_back) and the
+    // batch after that (this workspace's records) both wait for it
+    if (h->d_blog) HIP_TRY(h, launch_blog_add(L, blog_args(h), h->s_back));
     HIP_TRY(h, hipMemcpyAsync(err_dst, L.err, sizeof(int), hipMemcpyDeviceToHost, h->s_back));
     HIP_TRY(h, hipEventRecord(h->back_done[x], h->s_back));
     if (done) HIP_TRY(h, hipEventRecord(done, h->s_back));
@@ -3690,6 +3735,73 @@ int sg_local_enqueue(sg_handle* h, const sg_local_event* ev, uint64_t n, sg_loca
     d.local = true;
     d.ticket = h->next_ticket++;
     *ticket = d.ticket;
+    return SG_OK;
+}
+
+int sg_local_block_log_enable(sg_handle* h, int32_t capacity_log2) {
+    if (!h) return SG_E_INVAL;
+    if (capacity_log2 < 4 || capacity_log2 > 24) return fail(h, SG_E_INVAL, "capacity_log2 outside 4..24");
+    if (h->d_blog)
+        return capacity_log2 == h->blog_log2 ? SG_OK : fail(h, SG_E_INVAL, "the block log has another capacity");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);  // batches already enqueued stay unlogged: rows record what is decided from here on
+    const size_t slots = (size_t)1 << capacity_log2;
+    DevBuf<BlogSlot> tab;
+    DevBuf<unsigned long long> ctr;
+    DevBuf<sg_block_row> rows, keep;
+    DevBuf<int32_t> app;
+    if (!tab.alloc(slots) || !ctr.alloc(4) || !rows.alloc(slots) || !keep.alloc(slots) || !app.alloc(h->cfg.max_batch))
+        return fail(h, SG_E_NOMEM, "block log table");
+    HIP_TRY(h, hipMemset(tab, 0, sizeof(BlogSlot) * slots));
+    HIP_TRY(h, hipMemset(ctr, 0, sizeof(unsigned long long) * 4));
+    HIP_TRY(h, hipMemset(app, 0, sizeof(int32_t) * h->cfg.max_batch));
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->d_blog = std::move(tab);
+    h->d_blog_ctr = std::move(ctr);
+    h->d_blog_rows = std::move(rows);
+    h->d_blog_keep = std::move(keep);
+    h->d_blog_app = std::move(app);
+    h->blog_log2 = capacity_log2;
+    const int rc = blog_sync_apps(h);
+    if (rc) {  // off again: a handle is never left with half of the log's state
+        h->d_blog.reset();
+        h->blog_log2 = 0;
+    }
+    return rc;
+}
+
+int sg_local_block_log(sg_handle* h, int64_t now_ms, sg_block_row* rows, uint64_t cap, uint64_t* n_rows,
+                       uint64_t* lost_events, uint64_t* lost_count) {
+    if (!h || !n_rows || !lost_events || !lost_count || (!rows && cap)) return SG_E_INVAL;
+    *n_rows = *lost_events = *lost_count = 0;
+    if (!h->d_blog) return fail(h, SG_E_INVAL, "sg_local_block_log_enable first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    const BlogArgs b = blog_args(h);
+    unsigned long long* ctr = h->d_blog_ctr;
+    const int64_t limit = now_ms - now_ms % 1000;
+    unsigned long long c[4] = {0, 0, 0, 0};
+    // the count pass changes nothing: a capacity that is too small leaves the table and the lost totals as they were
+    HIP_TRY(h, hipMemsetAsync(ctr + 2, 0, 2 * sizeof(unsigned long long), 0));
+    HIP_TRY(h, launch_blog_take(b, limit, 0, nullptr, nullptr, ctr + 2, ctr + 3, 0));
+    HIP_TRY(h, hipMemcpy(c, ctr, sizeof(c), hipMemcpyDeviceToHost));
+    *n_rows = c[2];
+    if (c[2] > cap) return fail(h, SG_E_CAPACITY, "block log rows exceed cap");
+    if (c[2]) {  // move the complete rows out, clear the table, put the open seconds' rows back
+        HIP_TRY(h, hipMemsetAsync(ctr + 2, 0, 2 * sizeof(unsigned long long), 0));
+        HIP_TRY(h, launch_blog_take(b, limit, 1, h->d_blog_rows, h->d_blog_keep, ctr + 2, ctr + 3, 0));
+        HIP_TRY(h, hipMemsetAsync(h->d_blog, 0, sizeof(BlogSlot) * h->d_blog.size(), 0));
+        HIP_TRY(h, launch_blog_put(b, h->d_blog_keep, ctr + 3, 0));
+        HIP_TRY(h, hipMemcpy(rows, h->d_blog_rows, sizeof(sg_block_row) * c[2], hipMemcpyDeviceToHost));
+        std::sort(rows, rows + c[2], [](const sg_block_row& x, const sg_block_row& y) {
+            return std::tie(x.timestamp, x.resource, x.status, x.app_kind, x.app, x.origin) <
+                   std::tie(y.timestamp, y.resource, y.status, y.app_kind, y.app, y.origin);
+        });
+    }
+    HIP_TRY(h, hipMemset(ctr, 0, 2 * sizeof(unsigned long long)));
+    HIP_TRY(h, hipDeviceSynchronize());
+    *lost_events = c[0];
+    *lost_count = c[1];
     return SG_OK;
 }
 
@@ -4159,6 +4271,11 @@ int sg_local_load_flow_rules(sg_handle* h, const sg_local_flow_rule* rules, uint
     h->l_n_contexts = n_contexts;
     h->l_cluster_rules = cluster_rules;
     h->l_rule_slot = slot;
+    blocklog_limit_apps(rules, by_res, h->l_res_app);  // LogSlot: which resources need the failing rule reported
+    {
+        const int rc = blog_sync_apps(h);
+        if (rc) return rc;
+    }
     const int rc = local_apply_groups(h);
     if (rc) return rc;
     int kept = 0;

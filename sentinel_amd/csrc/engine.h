@@ -8,6 +8,7 @@
 
 #include "../../include/sentinel_gpu.h"
 #include "authority_rules.h"
+#include "blocklog_rules.h"
 #include "system_rules.h"
 #include "search_dev.h"
 
@@ -782,6 +783,10 @@ struct LArgs {
     const uint8_t* inbound;   // [K] 1: the resource's entries are EntryType.IN (Constants.ENTRY_NODE), or null
     LBucket* entry_acc;       // [60] the ENTRY_NODE's minute buckets summed from the inbound resources' (metric rows)
     int64_t* entry_fetch;     // the ENTRY_NODE's lastFetchTime
+    // LogSlot's rollup (sg_local_block_log_enable; null blog_app: off — no store, dead periods as without it)
+    int32_t* blog_app;        // [n] cx_entry: the limitApp of the flow rule that blocked the entry (FLOW blocks of the
+                              // kBlogMixed resources; the other entries' words are stale)
+    const int32_t* res_app;   // [K] each resource's one limitApp or kBlogMixed (blocklog_rules.h); set with blog_app
 };
 
 constexpr uint64_t kPsUnknown = ~0ull;     // LArgs::pslot codes: not looked up (the walker's own step decides)
@@ -824,6 +829,34 @@ hipError_t launch_local_entry_rows(const LArgs& L, int64_t now, sg_metric_node* 
                                    int raw, hipStream_t stream, const int* gate = nullptr);
 hipError_t launch_local_metrics(const LArgs& L, int64_t now, sg_metric_node* out, unsigned long long* count, int emit,
                                 int raw, hipStream_t stream, const int* gate = nullptr);
+
+// ---- LogSlot (blocklog.hip): sentinel-block.log's per-second rollup of a decided local batch ----
+// One row of the table: exact open addressing with linear probing over a four-word key. tag: 0 empty, kBlogBusy
+// claimed (its key words are being written), else the key's hash with bit 63 set — published with release order after
+// the key words, so a prober that reads a published tag reads the whole key.
+constexpr uint64_t kBlogBusy = 1;
+struct alignas(16) BlogSlot {
+    uint64_t tag;
+    int64_t ts;               // the second: t - t % 1000
+    uint64_t app;             // sg_block_row.app
+    uint64_t ro;              // resource << 32 | origin
+    uint32_t status, kind;    // SG_LOCAL_BLOCK_*, SG_BLOCK_APP_*
+    int64_t count;            // Σ acquireCount (64-bit integer adds: the order of arrival does not show)
+};
+static_assert(sizeof(BlogSlot) == 48, "BlogSlot layout");
+struct BlogArgs {
+    BlogSlot* tab;
+    uint64_t mask;            // slots - 1
+    unsigned long long* lost; // [2] entries and Σ count that found no slot
+};
+// The blocked entries of the decided batch L (after its walkers; nothing when *L.err != 0) added to the table.
+hipError_t launch_blog_add(const LArgs& L, const BlogArgs& b, hipStream_t stream);
+// The rows of the complete seconds (ts + 1000 <= limit): counted into *count (emit 0), or moved to rows[] with the
+// other slots' rows to keep[] (*count, *n_keep) — the caller clears the table and puts keep[] back (launch_blog_put).
+hipError_t launch_blog_take(const BlogArgs& b, int64_t limit, int emit, sg_block_row* rows, sg_block_row* keep,
+                            unsigned long long* count, unsigned long long* n_keep, hipStream_t stream);
+hipError_t launch_blog_put(const BlogArgs& b, const sg_block_row* keep, const unsigned long long* n_keep,
+                           hipStream_t stream);
 
 // SystemSlot (local.hip): the clear proof over the time-ordered batch before it is decided (k_sys_scan: verdict in
 // sys->unproven / first_unproven), and ENTRY_NODE's update from a decided batch that walked the normal image

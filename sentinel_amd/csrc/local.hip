@@ -1578,6 +1578,7 @@ __device__ bool cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd,
     // walked here because of its param rules) gets that rule back as a plain DIRECT / "default" rule
     const uint32_t n_rules = R.fr_n ? R.fr_n : (R.flow_grade >= 0 ? 1u : 0u);
     LCtl stateless{0, 0, -1, 0};
+    int32_t blocked_app = SG_LIMIT_APP_DEFAULT;  // FlowException.getRuleLimitApp(): the failing rule's (LogSlot)
     for (uint32_t i = 0; status == SG_LOCAL_PASS && i < n_rules; ++i) {
         LFlowRule r;
         if (R.fr_n) {
@@ -1603,6 +1604,7 @@ __device__ bool cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd,
             }
             if (ts == SG_STATUS_BLOCKED) {
                 status = SG_LOCAL_BLOCK_FLOW;
+                blocked_app = r.limit_app;
                 break;
             }
             // NO_RULE_EXISTS / BAD_REQUEST / FAIL / TOO_MANY_REQUEST: fallbackToLocalOrPass
@@ -1633,6 +1635,7 @@ __device__ bool cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd,
         }
         if (v == 0) {
             status = SG_LOCAL_BLOCK_FLOW;
+            blocked_app = r.limit_app;
             break;
         }
         if (v == 2) {
@@ -1679,6 +1682,7 @@ __device__ bool cx_entry(const LArgs& a, const uint32_t* const* bndp, LNode& nd,
             cn.mc[kLBlock] += e.count;
         }
         if (status != SG_LOCAL_BLOCK_PARAM && status != SG_LOCAL_BLOCK_SYSTEM) wait = 0;
+        if (a.blog_app && status == SG_LOCAL_BLOCK_FLOW) a.blog_app[e.idx] = blocked_app;  // the block log is on
     }
     if (sys_in) sys_entry(*a.sys, a.S, a.wl2, t, e.count, status);  // Constants.ENTRY_NODE
     if (params && (status == SG_LOCAL_PASS || status == SG_LOCAL_PASS_WAIT))
@@ -1979,6 +1983,9 @@ __device__ __noinline__ int cxw_step(const LArgs& a, const uint32_t* const* bndp
 __device__ bool cxw_dead_able(const LArgs& a, const LRule& R, uint32_t k, int32_t* prule) {
     *prule = -1;
     if (a.track_ctx) return false;
+    // the block log names the flow rule that failed: a dead period decides its entries without walking the rules, so a
+    // resource whose rules carry several limitApps walks entry by entry while the log is on
+    if (a.blog_app && a.res_app[k] == kBlogMixed) return false;
     if (R.fr_n == 0) {
         if (R.flow_grade != 1) return false;
     } else {

@@ -44,7 +44,8 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_node_local_read_state", "sg_node_local_metrics", "sg_node_local_metrics_device",
            "sg_node_local_merge_rows", "sg_local_load_authority_rules", "sg_node_local_load_authority_rules",
            "sg_local_load_system_rules", "sg_local_set_system_status", "sg_local_read_entry_node",
-           "sg_local_system_last_path", "sg_local_system_first_unproven"]
+           "sg_local_system_last_path", "sg_local_system_first_unproven",
+           "sg_local_block_log_enable", "sg_local_block_log"]
 
 _lib = None
 
@@ -176,6 +177,8 @@ def load_library():
         "sg_node_local_load_authority_rules": (C.c_int, [vp, vp, u32, vp, u32, C.c_int32]),
         "sg_local_load_system_rules": (C.c_int, [vp, vp, u32]),
         "sg_local_set_system_status": (C.c_int, [vp, C.c_double, C.c_double]),
+        "sg_local_block_log_enable": (C.c_int, [vp, C.c_int32]),
+        "sg_local_block_log": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "sg_local_read_entry_node": (C.c_int, [vp, vp, C.POINTER(C.c_int64)]),
         "sg_local_system_last_path": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "sg_local_system_first_unproven": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
@@ -940,6 +943,26 @@ class FlowEngine:
         out = np.zeros(max(1, n.value), abi.METRIC_NODE_DTYPE)
         self._check(self._L.sg_local_metrics(self.h, now_ms, abi.ptr(out), len(out), C.byref(n)))
         return out[:n.value]
+
+    def block_log_enable(self, capacity_log2=16):
+        """sg_local_block_log_enable: LogSlot's per-second rollup of blocked entries, kept on the device from now on
+        in a table of 2^capacity_log2 rows."""
+        self._check(self._L.sg_local_block_log_enable(self.h, capacity_log2))
+
+    def block_log(self, now_ms):
+        """sg_local_block_log: (rows, lost_events, lost_count) — the sentinel-block.log rows (abi.BLOCK_ROW_DTYPE,
+        sorted) of every second complete at now_ms, removed from the device table, and the blocked entries / their
+        summed count that found no free row since the last call."""
+        n, le, lc = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self._L.sg_local_block_log(self.h, now_ms, None, 0, C.byref(n), C.byref(le), C.byref(lc))
+        if rc == 0:  # no complete row: this call was the fetch, and it reported and cleared the lost totals
+            return np.zeros(0, abi.BLOCK_ROW_DTYPE), le.value, lc.value
+        if rc != abi.SG_E_CAPACITY:
+            self._check(rc)
+        out = np.zeros(max(1, n.value), abi.BLOCK_ROW_DTYPE)
+        self._check(self._L.sg_local_block_log(self.h, now_ms, abi.ptr(out), len(out), C.byref(n), C.byref(le),
+                                               C.byref(lc)))
+        return out[:n.value], le.value, lc.value
 
     def local_metrics_raw(self, now_ms) -> np.ndarray:
         """sg_local_metrics_raw: this GPU's share of the node's rows, rt as the raw sum (LocalMetricRollup merges)."""

@@ -281,3 +281,51 @@ def cluster_node_map(now_ms, flow_rules, flow_names, flow_snapshot, param_rules=
                 "passQps": 0.0, "blockQps": 0.0, "topParams": dict(param_top[k])}
         out.setdefault(param_names[k], []).append(node)
     return out
+
+
+# ---- sentinel-block.log (LogSlot → EagleEyeLogUtil → StatLogger "sentinel-block-log") ----
+BLOCK_LOG_FILE = "sentinel-block.log"  # EagleEyeLogUtil.FILE_NAME
+# BlockException.getClass().getSimpleName() by sg_local_result status
+BLOCK_EXCEPTION_NAMES = {abi.LOCAL_BLOCK_FLOW: "FlowException", abi.LOCAL_BLOCK_DEGRADE: "DegradeException",
+                         abi.LOCAL_BLOCK_PARAM: "ParamFlowException", abi.LOCAL_BLOCK_AUTHORITY: "AuthorityException",
+                         abi.LOCAL_BLOCK_SYSTEM: "SystemBlockException"}
+SYSTEM_LIMIT_TYPES = {abi.SYSTEM_QPS: "qps", abi.SYSTEM_THREAD: "thread", abi.SYSTEM_RT: "rt", abi.SYSTEM_LOAD: "load",
+                      abi.SYSTEM_CPU: "cpu"}
+
+
+def block_rule_limit_app(row, origin_names, value_str=str, label_str=str):
+    """BlockException.getRuleLimitApp() of one sg_block_row as the string LogSlot logs (read by app_kind)."""
+    kind, app = int(row["app_kind"]), int(row["app"])
+    if kind == abi.BLOCK_APP_LIMIT_APP:
+        la = app - (1 << 32) if app >= (1 << 31) else app  # the rule's int32 limit_app
+        if la == abi.LIMIT_APP_DEFAULT:
+            return "default"
+        return "other" if la == abi.LIMIT_APP_OTHER else origin_names[la]
+    if kind == abi.BLOCK_APP_ORIGIN:
+        return origin_names[app] if app else ""
+    if kind == abi.BLOCK_APP_SYSTEM:
+        return SYSTEM_LIMIT_TYPES[app]
+    if kind == abi.BLOCK_APP_VALUE:
+        return value_str(app)
+    if kind == abi.BLOCK_APP_NULL_ARG:
+        return "null"  # String.valueOf((Object) null)
+    if kind == abi.BLOCK_APP_NO_ARG:
+        return ""
+    if kind == abi.BLOCK_APP_LABEL:
+        return label_str(app)
+    raise ValueError(f"app_kind {kind}")
+
+
+def block_log_lines(rows, resource_names, origin_names, value_str=str, label_str=str, tz=datetime.timezone.utc):
+    """The sentinel-block.log lines of sg_local_block_log rows, one per row in row order (StatLogWriteTask.run,
+    StatLogController.java:130-152: `time|statType|keys joined by ','|count,value` with the COUNT_SUM entry's stat
+    type 1 and a value sum LogSlot never adds to): `yyyy-MM-dd HH:mm:ss|1|resource,ExceptionName,ruleLimitApp,origin|
+    count,0`. origin_names[id] is the origin string of id >= 1 (id 0 is ""); value_str / label_str turn a value id / a
+    collection label id into String.valueOf of the argument."""
+    out = []
+    for r in rows:
+        origin = origin_names[int(r["origin"])] if int(r["origin"]) else ""
+        out.append(f"{_date(int(r['timestamp']), tz)}|1|{resource_names[int(r['resource'])]},"
+                   f"{BLOCK_EXCEPTION_NAMES[int(r['status'])]},"
+                   f"{block_rule_limit_app(r, origin_names, value_str, label_str)},{origin}|{int(r['count'])},0\n")
+    return out
