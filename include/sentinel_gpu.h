@@ -219,7 +219,11 @@ typedef struct sg_pslot_result {
 /* Loads the rules (state of sg_param_* starts empty, as for sg_param_load_rules). */
 int sg_pslot_load_rules(sg_handle* h, const sg_pslot_rule* rules, uint32_t n, const sg_param_hot_item* hot,
                         uint32_t n_hot, uint32_t n_resources);
-/* A time-ordered batch; events, args, values and results are DEVICE pointers (asynchronous on stream). */
+/* A time-ordered batch; events, args, values and results are DEVICE pointers (asynchronous on stream). A batch
+ * rejected from its events alone (SG_E_TIME, SG_E_INVAL) changes no state, the value tables' free slots included. A
+ * table found full while the batch is walked — a param rule's values, the thread counts, or the embedded token
+ * server's cluster param values — is SG_E_CAPACITY and can leave the batch partly applied: the state then holds
+ * the events decided up to there, and the last timestamp does not advance. */
 int sg_pslot_decide_batch(sg_handle* h, const sg_pslot_event* ev, uint64_t n, const sg_pslot_arg* args,
                           uint64_t n_args, const uint64_t* values, uint64_t n_values, sg_pslot_result* out, void* stream);
 int sg_pslot_decide_batch_host(sg_handle* h, const sg_pslot_event* ev, uint64_t n, const sg_pslot_arg* args,
@@ -550,7 +554,9 @@ int sg_snapshot_metrics_enqueue(sg_handle* h, int64_t now_ms, double* out_dev, u
 int sg_param_load_rules(sg_handle* h, const sg_param_rule* rules, uint32_t n,
                         const sg_param_hot_item* hot, uint32_t n_hot);
 /* passSingleValueCheck for a time-ordered batch: pass[i] = 1 admitted / 0 blocked. req/pass are DEVICE
- * pointers. Requests naming a rule index >= n pass (no rule). */
+ * pointers. Requests naming a rule index >= n pass (no rule). A rejected batch (SG_E_TIME; SG_E_CAPACITY: a rule
+ * met more distinct values than its 2^capacity_log2 table holds) changes no state, the value tables' free slots
+ * included: a value the batch was the first to name is absent afterwards and counts against no rule's capacity. */
 int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int32_t* pass, void* stream);
 int sg_param_decide_batch_host(sg_handle* h, const sg_param_req* req, uint64_t n, int32_t* pass);
 /* State of (rule, value): returns flags (bit0 time counter, bit1 token counter; 0 = absent) or < 0. */
@@ -581,7 +587,16 @@ int sg_pace_read_state(sg_handle* h, uint32_t rule, int64_t* latest_passed_time)
  *                             i, as a packer appending each request's values produces) — else SG_E_INVAL.
  *                             allowProceed goes through the namespace's QPS limiter, the same state the flow-token
  *                             path uses (GlobalRequestLimiter is per namespace): keep flow and param batches that
- *                             share a limiter in time order. A rejected batch changes no state.
+ *                             share a limiter in time order. A rejected batch changes no state, the value tables'
+ *                             free slots included: a value the batch was the first to name is absent afterwards
+ *                             and counts against no rule's capacity (SG_E_CAPACITY: a rule met more distinct
+ *                             values than its table holds). A batch wrong in several ways reports what is wrong
+ *                             with the batch itself before what the tables could not take of it: SG_E_TIME, then
+ *                             SG_E_INVAL (value ranges), then SG_E_UNSUPPORTED (more than 65536 window periods),
+ *                             then SG_E_CAPACITY (it comes last for sg_param_* and sg_slot_* batches too). The slots
+ *                             go back by rebuilding the tables from a scratch copy; with no device memory for the
+ *                             copy the call still returns the batch's own code and only the free slots stay
+ *                             taken (until a later refusal rebuilds, or a reload).
  *   sg_cparam_last_rounds   fixed-point rounds the last batch needed (1 = single pass; requests with several values
  *                           may need more; max_rounds + 1 = it was decided serially). Tuning / tests.
  *   sg_cparam_read_sum      ← ClusterParamMetric.getSum(value) at now_ms (without currentWindow's side effect). */
@@ -768,7 +783,13 @@ int sg_local_system_first_unproven(const sg_handle* h, uint32_t* index);
  *     (StatisticSlot.exit :124-165, passed entries only): RT / success / exception and curThreadNum on the nodes,
  *     ParamFlowStatisticExitCallback (decreaseThreadCount of the exit's args), DegradeSlot.exit.
  *     ext[i] (nullable: every event in context 0 with null args) carries the event's context and arguments; args,
- *     values and ext are DEVICE pointers like ev and out. sg_local_decide_batch = this call with ext = NULL. */
+ *     values and ext are DEVICE pointers like ev and out. sg_local_decide_batch = this call with ext = NULL.
+ *     A batch rejected from its events alone (SG_E_TIME, SG_E_INVAL, SG_E_UNSUPPORTED) changes no state, the param
+ *     value tables' free slots included: a value only its entries named is absent afterwards and counts against no
+ *     rule's capacity. A table found full while the batch is walked (an entry with a collection argument or of a
+ *     resource with several param rules, the thread counts, the embedded token server's cluster param values) is
+ *     SG_E_CAPACITY and can leave the batch partly applied: the statistics then hold the events decided up to
+ *     there, and the last timestamp does not advance. */
 typedef struct sg_slot_ext {
     uint32_t context;             /* Context name id (0 .. n_contexts - 1); CHAIN rules select by it              */
     uint32_t arg_begin;           /* the event's args: args[arg_begin .. + arg_count)                           */

@@ -2072,6 +2072,21 @@ int sg_snapshot_metrics_enqueue(sg_handle* h, int64_t now_ms, double* out_dev, u
     return SG_OK;
 }
 
+// A refused batch changes no state, table capacity included: the value slots its prep kernel claimed before the
+// verdict (k_pprep, k_local_prep) hold no counter and are given back by rebuilding the sub-tables from a copy. On
+// the refusal path only; the copy lives for this call. The refusal's code stands unless the device fails here: when
+// there is no memory for the copy the claims stay (they cost free slots, never an answer) and the caller reports
+// what it refused the batch for.
+static int param_release_claims(sg_handle* h, hipStream_t stream) {
+    if (!h->ptotal || h->ptab.empty()) return SG_OK;
+    DevBuf<PSlot> old;
+    if (!old.alloc(h->ptotal)) return SG_OK;
+    HIP_TRY(h, hipMemcpyAsync(old, h->d_ptable, sizeof(PSlot) * h->ptotal, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(h, launch_param_rebuild(h->d_prules, (uint32_t)h->ptab.size(), h->d_ptable, old, h->ptotal, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    return SG_OK;
+}
+
 // ParamFlowRuleManager.loadRules (…/param/ParamFlowRuleManager.java) → fresh ParameterMetric maps.
 int sg_param_load_rules(sg_handle* h, const sg_param_rule* rules, uint32_t n, const sg_param_hot_item* hot,
                         uint32_t n_hot) {
@@ -2181,6 +2196,10 @@ int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int
     HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     const int err = *h->h_err & ~kErrNonPositive;
+    if (err) {  // no walker ran: what k_pprep claimed goes back
+        const int rc = param_release_claims(h, stream);
+        if (rc) return rc;  // SG_E_DEVICE only
+    }
     if (err & kErrTime)
         return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
     if (err & kErrTableFull) return fail(h, SG_E_CAPACITY, "a param rule's value table is full");
@@ -2534,6 +2553,33 @@ int sg_cparam_decide_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, c
 
 namespace {
 
+// A cparam batch's error flags → return code, one order for every exit: what is wrong with the batch itself (time
+// order, value ranges, window periods) comes before what the tables could not take of it.
+int cparam_status(sg_handle* h, int err) {
+    if (err & kErrTime) return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
+    if (err & kErrBounds)
+        return fail(h, SG_E_INVAL, "a request's values lie outside the value array, overlap another's or go backwards");
+    if (err & kErrPeriods) return fail(h, SG_E_UNSUPPORTED, "batch spans more than 65536 window or limiter periods");
+    if (err & kErrTableFull) return fail(h, SG_E_CAPACITY, "a param rule's value table is full");
+    return SG_OK;
+}
+
+// A batch that ends without its walk changes no state, table capacity included: the value slots k_cp_prep2 claimed
+// before the verdict go back (the sub-tables rebuilt from a copy that lives for this call). When there is no memory
+// for the copy the claims stay — they cost free slots, never an answer — and the caller's code stands.
+int cparam_release_claims(sg_handle* h, const CPArgs& c, hipStream_t stream) {
+    if (!h->cptotal) return SG_OK;
+    DevBuf<uint64_t> okeys;
+    DevBuf<CPBucket> oring;
+    const size_t cells = (size_t)h->cptotal * h->cpstride;
+    if (!okeys.alloc(h->cptotal) || !oring.alloc(cells)) return SG_OK;
+    HIP_TRY(h, hipMemcpyAsync(okeys, h->d_cpkeys, sizeof(uint64_t) * h->cptotal, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(h, hipMemcpyAsync(oring, h->d_cpring, sizeof(CPBucket) * cells, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(h, launch_cp_rebuild(c, okeys, oring, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    return SG_OK;
+}
+
 int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint64_t* values, uint64_t n_values,
                  sg_result* out, hipStream_t stream) {
     CPArgs c = cp_args(h, req, n, values, n_values, out);
@@ -2612,10 +2658,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         HIP_TRY(h, hipMemcpyAsync(&err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
         HIP_TRY(h, hipStreamSynchronize(stream));
         h->cp_rounds = 0;
-        if (err & kErrTime) return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
-        if (err & kErrBounds) return fail(h, SG_E_INVAL, "a request's values lie outside the value array");
-        if (err & kErrPeriods) return fail(h, SG_E_UNSUPPORTED, "batch spans more than 65536 window or limiter periods");
-        return SG_OK;
+        return cparam_status(h, err);  // no value: nothing was claimed
     }
     uint64_t* sorted = nullptr;
     HIP_TRY(h, radix_sort_records(h->d_cp_rec, h->d_cp_rec2, nv, pbits, h->d_cp_hist, &sorted, stream, 64));
@@ -2691,7 +2734,10 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         // re-walk flags clear, the multi-value requests' list
         HIP_TRY(h, hipMemsetAsync(b.dflag, 0, sizeof(uint32_t) * touched, stream));
         HIP_TRY(h, launch_cp_mlist(c, b, stream));
-        if (!h->d_cp_save.reserve((size_t)touched * h->cpstride)) return fail(h, SG_E_NOMEM, "cparam ring save area");
+        if (!h->d_cp_save.reserve((size_t)touched * h->cpstride)) {
+            (void)cparam_release_claims(h, c, stream);  // the batch ends here: its claims go back
+            return fail(h, SG_E_NOMEM, "cparam ring save area");
+        }
         b.save = h->d_cp_save;  // the first walk saves the touched rings, re-walks restore the dirty ones
         // hot slots' ring at the opening of every window period, so a re-walk resumes at the first period a changed
         // outcome touches (batches of <= kCkMaxPeriods periods, within a memory cap)
@@ -2701,7 +2747,10 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         for (int w = 0; w < b.n_wl; ++w) ck_np = std::max(ck_np, np[w]);
         const uint64_t ck = (uint64_t)counts[0] * ck_np * h->cpstride;
         if (counts[0] > 0 && ck_np <= kCkMaxPeriods && ck * sizeof(CPBucket) <= kCkMaxBytes) {
-            if (!h->d_cp_ckpt.reserve(ck)) return fail(h, SG_E_NOMEM, "cparam ring checkpoints");
+            if (!h->d_cp_ckpt.reserve(ck)) {
+                (void)cparam_release_claims(h, c, stream);  // the batch ends here: its claims go back
+                return fail(h, SG_E_NOMEM, "cparam ring checkpoints");
+            }
             b.ckpt = h->d_cp_ckpt;
             b.ck_np = ck_np;
             HIP_TRY(h, hipMemsetAsync(b.dq, 0xFF, sizeof(uint32_t) * touched, stream));
@@ -2710,7 +2759,10 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     // saturated ranges of hot slots (pieces of <= 4096 records, each >= 256: at most 2 nv / 256 + 1)
     {
         const uint64_t cap = 2 * nv / 256 + 1;
-        if (!h->d_cp_skips.reserve(cap) || !h->d_cp_skip_count.reserve(1)) return fail(h, SG_E_NOMEM, "cparam skip list");
+        if (!h->d_cp_skips.reserve(cap) || !h->d_cp_skip_count.reserve(1)) {
+            (void)cparam_release_claims(h, c, stream);  // the batch ends here: its claims go back
+            return fail(h, SG_E_NOMEM, "cparam skip list");
+        }
         b.skips = h->d_cp_skips;
         b.skip_count = h->d_cp_skip_count;
         b.skip_cap = (uint32_t)cap;
@@ -2795,12 +2847,11 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     HIP_TRY(h, launch_cp_finish_batch(c, stream));
     HIP_TRY(h, hipMemcpyAsync(&err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
-    if (err & kErrTime) return fail(h, SG_E_TIME, "timestamps must be >= 0, non-decreasing, and not older than earlier batches");
-    if (err & kErrBounds)
-        return fail(h, SG_E_INVAL, "a request's values lie outside the value array, overlap another's or go backwards");
-    if (err & kErrTableFull) return fail(h, SG_E_CAPACITY, "a param rule's value table is full");
-    if (err & kErrPeriods) return fail(h, SG_E_UNSUPPORTED, "batch spans more than 65536 window or limiter periods");
-    return SG_OK;
+    if (err) {  // refused: no walker ran, and what k_cp_prep2 claimed goes back
+        const int rc2 = cparam_release_claims(h, c, stream);
+        if (rc2) return rc2;
+    }
+    return cparam_status(h, err);
 }
 
 }  // namespace
@@ -3602,7 +3653,10 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
         // ClusterBuilderSlot create them at entry, before any rule is checked).
         const int rc = lnode_grow(h, used);
         h->l_pool_used = (uint32_t)used;
-        if (rc) return rc;
+        if (rc) {
+            if (L.pslot) (void)param_release_claims(h, stream);  // refused before any walker: the claims go back
+            return rc;
+        }
         L.N = h->l_nodes;
         L.head = h->d_lhead;
         L.sec = h->d_lsec;
@@ -3642,7 +3696,10 @@ int local_decide(sg_handle* h, const sg_local_event* ev, const sg_slot_ext* ext,
         h->stats.skipped_ranges = h->h_long[1];
     }
     rc = local_status(h, *h->h_err);
-    if (rc) return rc;
+    if (rc) {  // the value slots k_local_prep claimed for the refused batch's entries go back
+        if (L.pslot) (void)param_release_claims(h, stream);  // (the refusal's code and message stand)
+        return rc;
+    }
     ++h->l_batches;
     return SG_OK;
 }

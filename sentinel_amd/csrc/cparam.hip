@@ -63,6 +63,29 @@ __global__ void __launch_bounds__(256) k_cp_copy(const uint64_t* okeys, const CP
     }
 }
 
+// The cleared tables filled again from copies of what they held, live values only: a value whose slot k_cp_prep2
+// claimed and whose ring never got a bucket (no add: the batch was refused, or every request of the value was) is
+// not in the reference's metric and gives the slot back. Linear probing has no tombstones, so a value leaves by
+// rebuilding its rule's sub-table; the side slots stay where they are.
+__global__ void __launch_bounds__(256) k_cp_rebuild(CPArgs c, const uint64_t* okeys, const CPBucket* oring) {
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < c.total_slots; g += (uint64_t)gridDim.x * blockDim.x) {
+        const CPRule r = c.rules[cp_rule_of_slot(c, g)];
+        const CPBucket* src = oring + g * (uint64_t)c.stride;
+        uint64_t ng = g;
+        if (g != r.table_base + r.table_mask + 1) {
+            const uint64_t v = okeys[g];
+            if (v == kCpEmpty) continue;
+            bool live = false;
+            for (int j = 0; j < r.S && !live; ++j) live = src[j].start != INT64_MIN;
+            if (!live) continue;
+            ng = cp_slot(c, r, v);
+            if (ng == ~0ull) continue;  // cannot happen: the sub-table held these values
+        }
+        CPBucket* dst = c.ring + ng * (uint64_t)c.stride;
+        for (int j = 0; j < c.stride; ++j) dst[j] = src[j];
+    }
+}
+
 // ClusterParamMetric.getSum(value) of a rule at `now`, without the currentWindow side effect.
 __global__ void k_cp_read(CPArgs c, uint32_t rule, uint64_t value, int64_t now, int64_t* out) {
     const CPRule r = c.rules[rule];
@@ -121,6 +144,14 @@ hipError_t launch_cp_copy(const uint64_t* okeys, const CPBucket* oring, uint64_t
                           CPBucket* nring, uint64_t nbase, int nstride, uint64_t slots, int S, hipStream_t stream) {
     hipLaunchKernelGGL(k_cp_copy, dim3(cgrid(slots * S, 8192)), dim3(256), 0, stream, okeys, oring, obase, ostride, nkeys,
                        nring, nbase, nstride, slots, S);
+    return hipGetLastError();
+}
+
+hipError_t launch_cp_rebuild(const CPArgs& c, const uint64_t* okeys, const CPBucket* oring, hipStream_t stream) {
+    if (c.total_slots == 0) return hipSuccess;
+    hipError_t e = launch_cp_clear(c.keys, c.ring, c.total_slots, c.stride, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cp_rebuild, dim3(cgrid(c.total_slots, 8192)), dim3(256), 0, stream, c, okeys, oring);
     return hipGetLastError();
 }
 

@@ -311,6 +311,9 @@ struct alignas(32) PSThread {  // ParameterMetric.threadCountMap entry: (resourc
 };
 
 hipError_t launch_param_clear(PSlot* table, uint64_t n, hipStream_t stream);
+// table cleared and filled again from its copy `old` [n], entries no walker ever stepped (flags 0) left out
+hipError_t launch_param_rebuild(const PRule* rules, uint32_t n_rules, PSlot* table, const PSlot* old, uint64_t n,
+                                hipStream_t stream);
 // The long-segment walker runs on `aux` beside the short one (fork / join events).
 // sg: the length-class lists (short_list / short_count / class_off) and a zero error word for k_seg.
 hipError_t launch_param_batch(const PArgs& p, const BatchArgs& sg, uint64_t* a_buf, uint64_t* b_buf, uint32_t* hist,
@@ -478,6 +481,8 @@ hipError_t launch_cp_limprep(const CPArgs& c, BatchArgs& a, hipStream_t stream);
 hipError_t launch_cp_clear(uint64_t* keys, CPBucket* ring, uint64_t slots, int stride, hipStream_t stream);
 hipError_t launch_cp_copy(const uint64_t* okeys, const CPBucket* oring, uint64_t obase, int ostride, uint64_t* nkeys,
                           CPBucket* nring, uint64_t nbase, int nstride, uint64_t slots, int S, hipStream_t stream);
+// c.keys / c.ring cleared and filled again from their copies, values whose ring has no bucket left out
+hipError_t launch_cp_rebuild(const CPArgs& c, const uint64_t* okeys, const CPBucket* oring, hipStream_t stream);
 hipError_t launch_cp_read(const CPArgs& c, uint32_t rule, uint64_t value, int64_t now, int64_t* out_dev, hipStream_t stream);
 struct CPTop {                // a (rule, value) window sum for ClusterParamMetric.getTopValues
     uint64_t value;

@@ -345,6 +345,28 @@ __global__ void __launch_bounds__(256) k_ptable_clear(PSlot* table, uint64_t n) 
     }
 }
 
+// The cleared tables filled again from a copy `old` of what they held, live entries only: a value whose slot was
+// claimed by a prep kernel (k_pprep, k_local_prep) and never stepped by a walker — flags 0, the reference's maps do
+// not hold it — gives the slot back. Linear probing has no tombstones, so an entry leaves by rebuilding its
+// sub-table; the side slots stay where they are.
+__global__ void __launch_bounds__(256) k_ptable_rebuild(PArgs p, const PSlot* old) {
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < p.total_slots; g += (uint64_t)gridDim.x * blockDim.x) {
+        const PSlot s = old[g];
+        const PRule r = p.rules[rule_of_slot(p, g)];
+        if (g == r.table_base + r.table_mask + 1) {
+            p.table[g] = s;
+            continue;
+        }
+        if (s.value == kEmptyValue || !s.flags) continue;
+        const uint64_t ng = param_slot(p, r, s.value);
+        if (ng == ~0ull) continue;  // cannot happen: the sub-table held these entries
+        PSlot& d = p.table[ng];
+        d.flags = s.flags;
+        d.time = s.time;
+        d.tokens = s.tokens;
+    }
+}
+
 static unsigned pgrid(uint64_t n, unsigned cap) {
     uint64_t g = (n + 255) / 256;
     if (g < 1) g = 1;
@@ -355,6 +377,20 @@ static unsigned pgrid(uint64_t n, unsigned cap) {
 hipError_t launch_param_clear(PSlot* table, uint64_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_ptable_clear, dim3(pgrid(n, 8192)), dim3(256), 0, stream, table, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_param_rebuild(const PRule* rules, uint32_t n_rules, PSlot* table, const PSlot* old, uint64_t n,
+                                hipStream_t stream) {
+    if (n == 0 || n_rules == 0) return hipSuccess;
+    hipError_t e = launch_param_clear(table, n, stream);
+    if (e != hipSuccess) return e;
+    PArgs p{};
+    p.rules = rules;
+    p.n_rules = n_rules;
+    p.table = table;
+    p.total_slots = n;
+    hipLaunchKernelGGL(k_ptable_rebuild, dim3(pgrid(n, 8192)), dim3(256), 0, stream, p, old);
     return hipGetLastError();
 }
 
