@@ -561,6 +561,29 @@ int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int
 int sg_param_decide_batch_host(sg_handle* h, const sg_param_req* req, uint64_t n, int32_t* pass);
 /* State of (rule, value): returns flags (bit0 time counter, bit1 token counter; 0 = absent) or < 0. */
 int sg_param_read_state(sg_handle* h, uint32_t rule, uint64_t value, int64_t* last_time, int64_t* tokens);
+/* Growing the value tables in place (the reference's CacheMaps simply grow). Every sg_*_resize / sg_vdict_grow call:
+ *   bit-exact       afterwards the handle decides every batch and answers every state read exactly as a handle that
+ *                   had the larger capacity from the start and saw the same history: no time, token, window bucket
+ *                   or id moves;
+ *   all or nothing  the new tables are allocated and filled beside the old ones and swapped in at the end: when the
+ *                   allocation fails the call returns SG_E_NOMEM and the handle is as it was, and so after any other
+ *                   refusal;
+ *   ordered         enqueued work drains first, as in the rule loads.
+ * sg_param_resize: capacity_log2[n], one entry per loaded rule (n = the loaded rule count; the tables of sg_param_*,
+ * sg_pslot_* and the slot chain): 0 keeps the rule's size, any other value is the new capacity_log2, at least the
+ * current one and at most 30. Every rule is re-inserted, also one whose size is kept, so a call that changes no size
+ * compacts: a value whose slot was claimed and never counted (a batch found another table full inside a walker)
+ * gives its slot back. SG_E_INVAL: no rules loaded, n differs from the rule count, a size out of range, a shrink.
+ * SG_E_UNSUPPORTED: 2^32 slots or more in all, or a total at which a batch's record layout would overflow (slot bits
+ * + 8 + the bits of max_batch - 1 above 64 for sg_param_decide_batch; slots above 0xFFFFFFFC with sg_pslot_load_rules
+ * in force, the slot chain's 32-bit lookups) — a resize that succeeds never leaves a handle whose next batch is
+ * refused for width. The thread-count table is not part of this.
+ * sg_param_table_used: counted on the device over rule's sub-table. used = slots whose value word is taken — what a
+ * capacity refusal goes by; live = those some walker has counted (flags != 0); capacity = 2^capacity_log2. The side
+ * slot of the value 0xFFFF…FFFF is in none of them. Null outputs are skipped. A caller grows when used nears
+ * capacity, ahead of the refusal. */
+int sg_param_resize(sg_handle* h, const int32_t* capacity_log2, uint32_t n);
+int sg_param_table_used(sg_handle* h, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity);
 
 /* ---- pace controller ----
  *   sg_pace_load_rules    ← FlowRuleUtil.generateRater for CONTROL_BEHAVIOR_RATE_LIMITER rules
@@ -617,6 +640,18 @@ int sg_cparam_last_rounds(const sg_handle* h, uint32_t* rounds);
  *                          after the latest decided request (the metricList task's current time): the device keeps a
  *                          ring per (rule, value), which equals the reference's bucket maps from that time on. */
 int sg_cparam_top_values(sg_handle* h, int64_t now_ms, uint32_t number, uint64_t* values, double* qps, uint32_t* counts);
+/*   sg_cparam_resize     the (rule, value) tables grown in place, under the contract of sg_param_resize (bit-exact, all
+ *                          or nothing, ordered): one capacity_log2 for all rules, at least the current one and at most
+ *                          28 (SG_E_INVAL otherwise, or with no rules loaded). Keys and rings of every value with a
+ *                          written bucket move to their slot under the new mask; a value with none is dropped, as by a
+ *                          refused batch's rebuild. SG_E_UNSUPPORTED, nothing changed: 2^32 slots or more, or a
+ *                          total whose value records no longer fit max_batch ids. The embedded token server of the slot
+ *                          chain sees the new tables. A later sg_cparam_load_rules keeps surviving flowIds when it
+ *                          names the new capacity; any other capacity stays SG_E_UNSUPPORTED.
+ *   sg_cparam_table_used used = slots of rule's sub-table that hold a value, live = those with at least one written
+ *                          bucket, capacity = 2^capacity_log2; the side slot is in none. */
+int sg_cparam_resize(sg_handle* h, int32_t capacity_log2);
+int sg_cparam_table_used(sg_handle* h, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity);
 
 /* ---- local slot chain (the ProcessorSlot chain's statistic / flow / degrade slots, batched) ----
  *   sg_local_load_rules    ← FlowRuleManager.loadRules + DegradeRuleManager.loadRules for one resource each
@@ -984,6 +1019,12 @@ int sg_node_cparam_decide_batch_host(sg_node* nd, const sg_cparam_req* req, uint
 int sg_node_cparam_read_sum(sg_node* nd, uint32_t rule, uint64_t value, int64_t now_ms, int64_t* sum);
 int sg_node_cparam_top_values(sg_node* nd, int64_t now_ms, uint32_t number, uint64_t* values, double* qps,
                               uint32_t* counts);
+/* sg_cparam_resize on every shard that owns a flowId, in shard order. Each shard's growth is all or nothing; the
+ * node's is not: the first refusal is returned with the shards before it grown (which changes no answer; call again
+ * to complete — a shard already at the size is rehashed at that size). sg_node_cparam_table_used: the node's rule
+ * index, answered by the rule's owner. */
+int sg_node_cparam_resize(sg_node* nd, int32_t capacity_log2);
+int sg_node_cparam_table_used(sg_node* nd, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity);
 int sg_node_conc_set_rule_timeouts(sg_node* nd, const int64_t* client_offline_ms, const int64_t* resource_timeout_ms,
                                    uint32_t n);
 int sg_node_conc_decide_batch(sg_node* nd, const sg_conc_req* req, uint64_t n, sg_conc_result* out, void* stream);
@@ -1118,6 +1159,13 @@ int sg_node_local_read_controller(sg_node* nd, uint32_t rule, int64_t* state3);
 int sg_node_pslot_thread_count(sg_node* nd, uint32_t resource, int32_t param_idx, uint64_t value, int64_t* count);
 int sg_node_pslot_param_idx(sg_node* nd, uint32_t rule, int32_t* param_idx);
 int sg_node_param_read_state(sg_node* nd, uint32_t rule, uint64_t value, int64_t* last_time, int64_t* tokens);
+/* sg_param_resize over the node (sg_node_pslot_load_rules' rule indices): the front and every shard hold the whole
+ * rule set, so the front grows first — it refuses what any shard would, before one has changed — then the shards in
+ * order. Not node-wide all or nothing: a shard that fails (SG_E_NOMEM) leaves the front and the shards before it grown,
+ * which changes no answer; call again to complete. sg_node_param_table_used is answered by the owner of the rule's
+ * resource, where the rule's state lives. */
+int sg_node_param_resize(sg_node* nd, const int32_t* capacity_log2, uint32_t n);
+int sg_node_param_table_used(sg_node* nd, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity);
 
 /* ---------- token-server wire codec ----------
  * The default token server frames every message with a 2-byte big-endian length
@@ -1185,6 +1233,12 @@ int sg_codec_encode_flow(sg_handle* h, const int32_t* xid, const uint8_t* kind, 
  *                    sg_cparam_top_values reporting. An id of 0 or above the value count is SG_E_INVAL; bytes_cap too
  *                    small is SG_E_CAPACITY with offsets_out filled.
  *   sg_vdict_size    values and arena bytes in use.
+ *   sg_vdict_grow    a larger dictionary in place: capacity_log2 (at most 28) and arena_bytes both at least what they
+ *                    are (SG_E_INVAL otherwise, or before sg_vdict_init). Entries and the used arena bytes are copied
+ *                    and the lookup table is rebuilt on the device from the entries; every id, sg_vdict_size,
+ *                    sg_vdict_lookup and the ids handed out next (count + 1, …) are as in a dictionary that was this
+ *                    large from the start. max_batch_values is unchanged. All or nothing: SG_E_NOMEM leaves the
+ *                    dictionary as it was.
  * All or nothing: a batch whose new values would exceed the capacity, or whose new long payloads the arena, returns
  * SG_E_CAPACITY and leaves the dictionary as it was — size, ids and arena.
  *
@@ -1204,7 +1258,7 @@ int sg_codec_encode_flow(sg_handle* h, const int32_t* xid, const uint8_t* kind, 
  * sg_codec_encode_param: as sg_codec_encode_flow for SG_FRAME_PARAM kinds, waitInMs 0 whatever res.wait_ms holds.
  *
  * Not covered: the node handle (sg_node_*), the concurrent-token message types 3 / 4 (the default server registers
- * no decoder for them), growing a dictionary after sg_vdict_init. */
+ * no decoder for them). */
 #define SG_FRAME_PARAM     4   /* a param-flow token request, decoded                                    */
 #define SG_FRAME_MALFORMED 5   /* MSG_TYPE_PARAM_FLOW whose decoder would throw: no request is made       */
 #define SG_PARAM_TYPE_INTEGER 0
@@ -1227,6 +1281,7 @@ int sg_vdict_intern(sg_handle* h, const uint8_t* types, const uint32_t* offsets,
 int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* types_out, uint32_t* offsets_out,
                     uint8_t* bytes_out, uint64_t bytes_cap);
 int sg_vdict_size(sg_handle* h, uint64_t* n_values, uint64_t* arena_used);
+int sg_vdict_grow(sg_handle* h, int32_t capacity_log2, uint64_t arena_bytes);
 int sg_codec_decode_param(sg_handle* h, const uint8_t* payload, const uint32_t* offsets, const int64_t* ts_ms,
                           uint64_t n, sg_cparam_req* req_out, uint64_t* values_out, uint64_t values_cap,
                           uint64_t* n_values, int32_t* xid_out, uint8_t* kind_out, void* stream);

@@ -17,6 +17,7 @@
 
 #include "devmem.h"
 #include "engine.h"
+#include "table_grow.h"
 
 using namespace sg;
 
@@ -1211,6 +1212,44 @@ int sg_vdict_size(sg_handle* h, uint64_t* n_values, uint64_t* arena_used) {
     return SG_OK;
 }
 
+// The reference interns nothing: its maps hold the values themselves and grow. Entries [1, count] and the used arena
+// bytes are copied into the larger arrays — ids are array positions, so none moves — and the main table is filled
+// again from the entries (pcodec.hip k_vd_rehash). The per-batch scratch (max_batch_values) is not touched.
+int sg_vdict_grow(sg_handle* h, int32_t capacity_log2, uint64_t arena_bytes) {
+    if (!h) return SG_E_INVAL;
+    auto& v = h->vd;
+    const GrowPlan plan = grow_plan_vdict(v.on, v.capacity, v.arena_bytes, capacity_log2, arena_bytes);
+    if (plan.code) return fail(h, plan.code, plan.why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    const uint64_t capacity = plan.total, slots = 2 * capacity;  // at most half full: a probe always ends
+    DevBuf<uint64_t> tab;
+    DevBuf<VEntry> entries;
+    DevBuf<uint8_t> arena;
+    if (!tab.alloc_bytes(8 * slots) || !entries.alloc_bytes(sizeof(VEntry) * (capacity + 1)) ||
+        !arena.alloc_bytes(arena_bytes ? arena_bytes : 1))
+        return fail(h, SG_E_NOMEM, "grown value dictionary");
+    HIP_TRY(h, hipMemsetAsync(tab, 0, 8 * slots, nullptr));
+    HIP_TRY(h, hipMemcpyAsync(entries, v.entries, sizeof(VEntry) * (v.count + 1), hipMemcpyDeviceToDevice, nullptr));
+    if (v.arena_used)
+        HIP_TRY(h, hipMemcpyAsync(arena, v.arena, v.arena_used, hipMemcpyDeviceToDevice, nullptr));
+    VDictArgs a{};
+    a.tab = tab;
+    a.tab_mask = slots - 1;
+    a.entries = entries;
+    a.arena = arena;
+    a.count = v.count;
+    HIP_TRY(h, launch_vd_rehash(a, nullptr));
+    HIP_TRY(h, hipDeviceSynchronize());
+    v.tab = std::move(tab);
+    v.entries = std::move(entries);
+    v.arena = std::move(arena);
+    v.tab_mask = slots - 1;
+    v.capacity = capacity;
+    v.arena_bytes = arena_bytes;
+    return SG_OK;
+}
+
 int sg_codec_decode_param(sg_handle* h, const uint8_t* payload, const uint32_t* offsets, const int64_t* ts_ms,
                           uint64_t n, sg_cparam_req* req_out, uint64_t* values_out, uint64_t values_cap,
                           uint64_t* n_values, int32_t* xid_out, uint8_t* kind_out, void* stream) {
@@ -2254,6 +2293,55 @@ int sg_param_read_state(sg_handle* h, uint32_t rule, uint64_t value, int64_t* la
     return (int)found.flags;
 }
 
+// The reference's CacheMaps simply grow. Here the grown tables are allocated and filled beside the ones in force
+// (grow.hip k_pgrow: every counted entry re-inserted under its rule's new mask, the side slots carried over) and
+// swapped in at the end, so any refusal leaves the handle as it was. Every batch builds its arguments from
+// d_prules / d_ptable / ptab / ptotal when it is called (sg_param_decide_batch, pslot_args for sg_pslot_* and the slot
+// chain): once the enqueued work has drained nothing else holds the old tables.
+int sg_param_resize(sg_handle* h, const int32_t* capacity_log2, uint32_t n) {
+    if (!h) return SG_E_INVAL;
+    std::vector<uint64_t> cur(h->ptab.size());
+    for (size_t i = 0; i < cur.size(); ++i) cur[i] = h->ptab[i].table_mask;
+    const GrowPlan plan = grow_plan_param(cur, capacity_log2, n, h->cfg.max_batch, h->ps_loaded);
+    if (plan.code) return fail(h, plan.code, plan.why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    std::vector<PRule> tab = h->ptab;
+    for (uint32_t i = 0; i < n; ++i) {
+        tab[i].table_base = plan.base[i];
+        tab[i].table_mask = plan.mask[i];
+    }
+    DevBuf<PRule> d_rules;
+    DevBuf<PSlot> d_table;
+    if (!d_rules.alloc(n) || !d_table.alloc(plan.total)) return fail(h, SG_E_NOMEM, "grown param tables");
+    HIP_TRY(h, hipMemcpy(d_rules, tab.data(), sizeof(PRule) * n, hipMemcpyHostToDevice));
+    HIP_TRY(h, launch_param_grow(h->d_prules, h->d_ptable, h->ptotal, d_rules, n, d_table, plan.total, 0));
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->d_prules = std::move(d_rules);
+    h->d_ptable = std::move(d_table);
+    h->ptab = tab;
+    h->ptotal = plan.total;
+    for (uint32_t i = 0; i < n; ++i)
+        if (capacity_log2[i]) h->prules[i].capacity_log2 = capacity_log2[i];
+    return SG_OK;
+}
+
+int sg_param_table_used(sg_handle* h, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity) {
+    if (!h || rule >= h->ptab.size()) return SG_E_INVAL;
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    const PRule& R = h->ptab[rule];
+    DevBuf<unsigned long long> d;
+    if (!d.alloc(2)) return fail(h, SG_E_NOMEM, "table count buffer");
+    unsigned long long got[2] = {0, 0};
+    HIP_TRY(h, launch_param_used(h->d_ptable, R.table_base, R.table_mask + 1, d, 0));
+    HIP_TRY(h, hipMemcpy(got, d, sizeof(got), hipMemcpyDeviceToHost));
+    if (used) *used = got[0];
+    if (live) *live = got[1];
+    if (capacity) *capacity = R.table_mask + 1;
+    return SG_OK;
+}
+
 // --------------------------------------------------------------------- pace controller
 // FlowRuleUtil.generateRater (core/.../flow/FlowRuleUtil.java:132-145) builds one RateLimiterController per
 // CONTROL_BEHAVIOR_RATE_LIMITER rule; a rebuild starts every latestPassedTime at -1
@@ -2922,6 +3010,62 @@ int sg_cparam_top_values(sg_handle* h, int64_t now_ms, uint32_t number, uint64_t
         qps[(size_t)t.rule * number + k] = (double)t.sum / h->cptab[t.rule].isec;  // count / getIntervalInSecond
         ++k;
     }
+    return SG_OK;
+}
+
+// ClusterParamMetric's value → count maps simply grow. The grown keys and rings are allocated and filled beside the
+// ones in force (grow.hip: a claim pass, then a coalesced move of the buckets) and swapped in at the end; cp_args
+// builds every batch's arguments — the embedded token server's too (pslot_embed) — from the members written here, and
+// the scratch sized by cptotal follows at the next batch (d_cp_slot_item.reserve).
+int sg_cparam_resize(sg_handle* h, int32_t capacity_log2) {
+    if (!h) return SG_E_INVAL;
+    const uint32_t R = (uint32_t)h->cptab.size();
+    const GrowPlan plan = grow_plan_cparam(R, R ? h->cptab[0].table_mask : 0, capacity_log2, h->cfg.max_batch);
+    if (plan.code) return fail(h, plan.code, plan.why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    std::vector<CPRule> tab = h->cptab;
+    for (uint32_t i = 0; i < R; ++i) {
+        tab[i].table_base = plan.base[i];
+        tab[i].table_mask = plan.mask[i];
+    }
+    DevBuf<CPRule> d_rules;
+    DevBuf<uint64_t> d_keys;
+    DevBuf<CPBucket> d_ring;
+    DevBuf<uint32_t> d_map;
+    if (!d_rules.alloc(R) || !d_keys.alloc(plan.total) || !d_ring.alloc((size_t)plan.total * h->cpstride) ||
+        !d_map.alloc(h->cptotal))
+        return fail(h, SG_E_NOMEM, "grown cluster param tables");
+    HIP_TRY(h, hipMemcpy(d_rules, tab.data(), sizeof(CPRule) * R, hipMemcpyHostToDevice));
+    CPArgs nc = cp_args(h, nullptr, 0, nullptr, 0, nullptr);
+    nc.rules = d_rules;
+    nc.keys = d_keys;
+    nc.ring = d_ring;
+    nc.total_slots = plan.total;
+    nc.per = plan.mask[0] + 2;
+    HIP_TRY(h, launch_cp_grow(nc, h->d_cprules, h->cptab[0].table_mask + 2, h->d_cpkeys, h->d_cpring, h->cptotal, d_map, 0));
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->d_cprules = std::move(d_rules);
+    h->d_cpkeys = std::move(d_keys);
+    h->d_cpring = std::move(d_ring);
+    h->cptab = tab;
+    h->cptotal = plan.total;
+    return SG_OK;
+}
+
+int sg_cparam_table_used(sg_handle* h, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity) {
+    if (!h || rule >= h->cptab.size()) return SG_E_INVAL;
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    const CPRule& R = h->cptab[rule];
+    DevBuf<unsigned long long> d;
+    if (!d.alloc(2)) return fail(h, SG_E_NOMEM, "table count buffer");
+    unsigned long long got[2] = {0, 0};
+    HIP_TRY(h, launch_cp_used(h->d_cpkeys, h->d_cpring, h->cpstride, R.S, R.table_base, R.table_mask + 1, d, 0));
+    HIP_TRY(h, hipMemcpy(got, d, sizeof(got), hipMemcpyDeviceToHost));
+    if (used) *used = got[0];
+    if (live) *live = got[1];
+    if (capacity) *capacity = R.table_mask + 1;
     return SG_OK;
 }
 
@@ -6897,6 +7041,59 @@ int sg_node_local_merge_rows(sg_node* nd, const sg_metric_node* d_rows, uint64_t
     node_drain(nd);
     NHIP(nd, hipSetDevice(nd->devices[0]));
     return node_merge_rows(nd, d_rows, n, d_out, cap, n_out, (hipStream_t)stream);
+}
+
+// The front and every shard hold the whole param rule set under the node's rule indices (sg_node_pslot_load_rules),
+// so all of them grow: the front first (it refuses what any shard would, before one has changed), then the shards in
+// order. Each handle's growth is all or nothing; the node's is not — a shard that fails (SG_E_NOMEM) leaves the front
+// and the shards before it grown, which decides nothing differently (a table's size is invisible) and is completed by
+// calling again: sizes already reached are kept.
+int sg_node_param_resize(sg_node* nd, const int32_t* capacity_log2, uint32_t n) {
+    if (!nd) return SG_E_INVAL;
+    if (!nd->l_ps_loaded) return nfail(nd, SG_E_INVAL, "sg_node_pslot_load_rules first");
+    node_drain(nd);
+    int rc = node_child(nd, nd->front, sg_param_resize(nd->front, capacity_log2, n));
+    for (size_t g = 0; !rc && g < nd->shards.size(); ++g)
+        rc = node_child(nd, nd->shards[g], sg_param_resize(nd->shards[g], capacity_log2, n));
+    for (uint32_t i = 0; !rc && i < n; ++i)  // what a front rollback loads again (node_local_front_rollback)
+        if (capacity_log2[i]) nd->l_prules[i].rule.capacity_log2 = capacity_log2[i];
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_param_table_used(sg_node* nd, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity) {
+    if (!nd) return SG_E_INVAL;
+    sg_handle* h = node_prule_owner(nd, rule);
+    if (!h) return nfail(nd, SG_E_INVAL, "no such param rule");
+    node_drain(nd);
+    const int rc = node_child(nd, h, sg_param_table_used(h, rule, used, live, capacity));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+// Every shard that owns cluster param rules grows its tables, in shard order; the first refusal is returned with the
+// shards before it grown (as sg_node_cparam_load_rules: not node-wide all or nothing; call again to complete).
+int sg_node_cparam_resize(sg_node* nd, int32_t capacity_log2) {
+    if (!nd) return SG_E_INVAL;
+    if (nd->cp_rules.empty()) return nfail(nd, SG_E_INVAL, "no cluster param rules loaded");
+    node_drain(nd);
+    int rc = SG_OK;
+    for (size_t g = 0; !rc && g < nd->shards.size(); ++g) {
+        sg_handle* h = nd->shards[g];
+        if (h->cptab.empty()) continue;  // owns no flowId
+        rc = node_child(nd, h, sg_cparam_resize(h, capacity_log2));
+    }
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
+}
+
+int sg_node_cparam_table_used(sg_node* nd, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity) {
+    if (!nd || rule >= nd->cp_rules.size()) return SG_E_INVAL;
+    node_drain(nd);
+    sg_handle* h = nd->shards[nd->cp_shard_of[rule]];
+    const int rc = node_child(nd, h, sg_cparam_table_used(h, nd->cp_local_of[rule], used, live, capacity));
+    (void)hipSetDevice(nd->devices[0]);
+    return rc;
 }
 
 }  // extern "C"

@@ -314,6 +314,12 @@ hipError_t launch_param_clear(PSlot* table, uint64_t n, hipStream_t stream);
 // table cleared and filled again from its copy `old` [n], entries no walker ever stepped (flags 0) left out
 hipError_t launch_param_rebuild(const PRule* rules, uint32_t n_rules, PSlot* table, const PSlot* old, uint64_t n,
                                 hipStream_t stream);
+// grow.hip: `table` [new_total] cleared and filled from the tables in force (old [old_total] under orules), rule i
+// at nrules[i]'s base and mask; entries no walker ever stepped are left out, the side slots carry over
+hipError_t launch_param_grow(const PRule* orules, const PSlot* old, uint64_t old_total, const PRule* nrules,
+                             uint32_t n_rules, PSlot* table, uint64_t new_total, hipStream_t stream);
+// out2[0] = slots of table[base .. base + n) whose value word is taken, out2[1] = those with flags != 0
+hipError_t launch_param_used(const PSlot* table, uint64_t base, uint64_t n, unsigned long long* out2, hipStream_t stream);
 // The long-segment walker runs on `aux` beside the short one (fork / join events).
 // sg: the length-class lists (short_list / short_count / class_off) and a zero error word for k_seg.
 hipError_t launch_param_batch(const PArgs& p, const BatchArgs& sg, uint64_t* a_buf, uint64_t* b_buf, uint32_t* hist,
@@ -483,6 +489,14 @@ hipError_t launch_cp_copy(const uint64_t* okeys, const CPBucket* oring, uint64_t
                           CPBucket* nring, uint64_t nbase, int nstride, uint64_t slots, int S, hipStream_t stream);
 // c.keys / c.ring cleared and filled again from their copies, values whose ring has no bucket left out
 hipError_t launch_cp_rebuild(const CPArgs& c, const uint64_t* okeys, const CPBucket* oring, hipStream_t stream);
+// grow.hip: nc.keys / nc.ring (nc.rules, nc.total_slots, the old stride) cleared and filled from the tables in force
+// (orules, oper slots per rule, okeys, oring [old_total]); map: [old_total] words of scratch. Values whose ring has no
+// bucket are left out.
+hipError_t launch_cp_grow(const CPArgs& nc, const CPRule* orules, uint64_t oper, const uint64_t* okeys,
+                          const CPBucket* oring, uint64_t old_total, uint32_t* map, hipStream_t stream);
+// out2[0] = slots of keys[base .. base + n) that hold a value, out2[1] = those with a written bucket among the first S
+hipError_t launch_cp_used(const uint64_t* keys, const CPBucket* ring, int stride, int S, uint64_t base, uint64_t n,
+                          unsigned long long* out2, hipStream_t stream);
 hipError_t launch_cp_read(const CPArgs& c, uint32_t rule, uint64_t value, int64_t now, int64_t* out_dev, hipStream_t stream);
 struct CPTop {                // a (rule, value) window sum for ClusterParamMetric.getTopValues
     uint64_t value;
@@ -1175,6 +1189,8 @@ hipError_t launch_pcodec_encode(const PCodecArgs& c, hipStream_t stream);
 hipError_t launch_vd_host_lookup(const VDictArgs& v, hipStream_t stream);
 hipError_t launch_vd_dedupe(const VDictArgs& v, hipStream_t stream);   // misses → dedupe table, representative flags
 hipError_t launch_vd_commit(const VDictArgs& v, hipStream_t stream);   // append + insert the new values, ids of all misses
+// the main table (zeroed, v.tab_mask) filled again from entries [1, v.count]: each entry's hash recomputed from its payload
+hipError_t launch_vd_rehash(const VDictArgs& v, hipStream_t stream);
 hipError_t launch_vd_gather(const VEntry* entries, const uint64_t* ids, uint64_t n, VEntry* out, hipStream_t stream);
 hipError_t launch_vd_bytes(const VEntry* e, const uint32_t* offsets, uint64_t n, const uint8_t* arena, uint8_t* out,
                            hipStream_t stream);

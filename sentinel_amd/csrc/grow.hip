@@ -1,0 +1,185 @@
+// grow.hip — the exact value tables grown in place: the hot-parameter sub-tables (PSlot, pslot_dev.h) and the cluster
+// param tables (keys + CPBucket rings, cparam_dev.h) rehashed into fresh, larger tables beside the old ones, and the
+// occupancy counts a caller watches to grow ahead of a capacity refusal. The reference's maps (CacheMap,
+// ClusterParamMetric's value → count buckets) simply grow; here the host allocates the new tables, these kernels
+// fill them, and the host swaps them in (api.cpp sg_param_resize / sg_cparam_resize).
+//
+// Both rehashes keep what the rebuild kernels keep (k_ptable_rebuild, k_cp_rebuild): a value whose slot was claimed
+// and never counted is not in the reference's maps and is dropped; the side slots carry over.
+//   PSlot    one lane per old slot: find-or-claim the destination by param_slot's CAS, then the whole 32-byte struct.
+//   cparam   a claim pass (one lane per old slot → destination index or "dropped" in a u32 map), then a move pass
+//            over the old ring in memory order: consecutive lanes take consecutive 16-byte buckets of a slot, read
+//            and written as one vector each, so both sides of the bulk copy are coalesced.
+#include "pslot_dev.h"
+
+namespace sg {
+
+namespace {
+
+constexpr uint32_t kGrowDropped = 0xFFFFFFFFu;  // the claim pass's map: this old slot moves nowhere
+
+__device__ __forceinline__ uint32_t grow_rule_of_slot(const PRule* rules, uint32_t n_rules, uint64_t g) {
+    uint32_t lo = 0, hi = n_rules;  // rules sorted by table_base; slot g belongs to the last base <= g
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (rules[mid].table_base <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o, 64);
+    return v;
+}
+
+}  // namespace
+
+// np: the new rules (table_base / table_mask of the grown sub-tables) and the cleared new table; orules / old: the
+// tables in force. Rule i of both lists is the same rule.
+__global__ void __launch_bounds__(256) k_pgrow(PArgs np, const PRule* orules, const PSlot* old, uint64_t old_total) {
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < old_total; g += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t ri = grow_rule_of_slot(orules, np.n_rules, g);
+        const PRule o = orules[ri];
+        const PRule r = np.rules[ri];
+        const PSlot s = old[g];
+        if (g == o.table_base + o.table_mask + 1) {  // the side slot (its value word stays ~0)
+            np.table[r.table_base + r.table_mask + 1] = s;
+            continue;
+        }
+        if (s.value == kEmptyValue || !s.flags) continue;
+        const uint64_t ng = param_slot(np, r, s.value);
+        if (ng == ~0ull) continue;  // cannot happen: the new sub-table is at least as large
+        np.table[ng] = s;           // the value word again, beside its counters: one 32-byte store
+    }
+}
+
+// out[0] += slots of table[base .. base + n) whose value word is taken, out[1] += those a walker has counted.
+__global__ void __launch_bounds__(256) k_ptable_used(const PSlot* table, uint64_t base, uint64_t n,
+                                                     unsigned long long* out) {
+    uint64_t used = 0, live = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const PSlot s = table[base + i];
+        if (s.value == kEmptyValue) continue;
+        ++used;
+        live += s.flags != 0;
+    }
+    used = wave_sum_u64(used);
+    live = wave_sum_u64(live);
+    if (__lane_id() == 0 && used) {
+        atomicAdd(out, (unsigned long long)used);
+        if (live) atomicAdd(out + 1, (unsigned long long)live);
+    }
+}
+
+// nc: the new rules and the cleared new keys / rings; orules, oper (slots per old rule), okeys, oring: the tables in
+// force. map[g] = the new slot of old slot g, or kGrowDropped.
+__global__ void __launch_bounds__(256) k_cpgrow_claim(CPArgs nc, const CPRule* orules, uint64_t oper, const uint64_t* okeys,
+                                                      const CPBucket* oring, uint64_t old_total, uint32_t* map) {
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < old_total; g += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t ri = (uint32_t)(g / oper);
+        const CPRule o = orules[ri];
+        const CPRule r = nc.rules[ri];
+        uint64_t ng = ~0ull;
+        if (g == o.table_base + o.table_mask + 1) {
+            ng = r.table_base + r.table_mask + 1;
+        } else {
+            const uint64_t v = okeys[g];
+            if (v != kCpEmpty) {
+                const CPBucket* src = oring + g * (uint64_t)nc.stride;
+                bool live = false;
+                for (int j = 0; j < o.S && !live; ++j) live = src[j].start != INT64_MIN;
+                if (live) ng = cp_slot(nc, r, v);
+            }
+        }
+        map[g] = ng == ~0ull ? kGrowDropped : (uint32_t)ng;
+    }
+}
+
+// Bucket i of the old ring → its slot's new ring, 16 bytes per lane. Buckets past the rule's sampleCount are never
+// written by any walker and stay as the clear left them.
+__global__ void __launch_bounds__(256) k_cpgrow_move(const CPRule* orules, uint64_t oper, const uint4* oring, uint4* nring,
+                                                     int stride, const uint32_t* map, uint64_t old_total) {
+    const uint64_t cells = old_total * (uint64_t)stride;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t g = i / (uint64_t)stride;
+        const int j = (int)(i - g * (uint64_t)stride);
+        const uint32_t ng = map[g];
+        if (ng == kGrowDropped || j >= orules[g / oper].S) continue;
+        nring[(uint64_t)ng * (uint64_t)stride + j] = oring[i];
+    }
+}
+
+// out[0] += slots of keys[base .. base + n) that hold a value, out[1] += those with at least one written bucket.
+__global__ void __launch_bounds__(256) k_cptable_used(const uint64_t* keys, const CPBucket* ring, int stride, int S,
+                                                      uint64_t base, uint64_t n, unsigned long long* out) {
+    uint64_t used = 0, live = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (keys[base + i] == kCpEmpty) continue;
+        ++used;
+        const CPBucket* src = ring + (base + i) * (uint64_t)stride;
+        bool l = false;
+        for (int j = 0; j < S && !l; ++j) l = src[j].start != INT64_MIN;
+        live += l;
+    }
+    used = wave_sum_u64(used);
+    live = wave_sum_u64(live);
+    if (__lane_id() == 0 && used) {
+        atomicAdd(out, (unsigned long long)used);
+        if (live) atomicAdd(out + 1, (unsigned long long)live);
+    }
+}
+
+static_assert(sizeof(CPBucket) == sizeof(uint4), "the move pass copies a bucket as one 16-byte vector");
+
+static unsigned ggrid(uint64_t n, unsigned cap) {
+    uint64_t g = (n + 255) / 256;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (unsigned)g;
+}
+
+hipError_t launch_param_grow(const PRule* orules, const PSlot* old, uint64_t old_total, const PRule* nrules,
+                             uint32_t n_rules, PSlot* table, uint64_t new_total, hipStream_t stream) {
+    if (n_rules == 0 || new_total == 0) return hipSuccess;
+    hipError_t e = launch_param_clear(table, new_total, stream);
+    if (e != hipSuccess) return e;
+    PArgs p{};
+    p.rules = nrules;
+    p.n_rules = n_rules;
+    p.table = table;
+    p.total_slots = new_total;
+    hipLaunchKernelGGL(k_pgrow, dim3(ggrid(old_total, 8192)), dim3(256), 0, stream, p, orules, old, old_total);
+    return hipGetLastError();
+}
+
+hipError_t launch_param_used(const PSlot* table, uint64_t base, uint64_t n, unsigned long long* out2, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(out2, 0, 2 * sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ptable_used, dim3(ggrid(n, 2048)), dim3(256), 0, stream, table, base, n, out2);
+    return hipGetLastError();
+}
+
+hipError_t launch_cp_grow(const CPArgs& nc, const CPRule* orules, uint64_t oper, const uint64_t* okeys,
+                          const CPBucket* oring, uint64_t old_total, uint32_t* map, hipStream_t stream) {
+    if (nc.n_rules == 0 || nc.total_slots == 0) return hipSuccess;
+    hipError_t e = launch_cp_clear(nc.keys, nc.ring, nc.total_slots, nc.stride, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cpgrow_claim, dim3(ggrid(old_total, 8192)), dim3(256), 0, stream, nc, orules, oper, okeys, oring,
+                       old_total, map);
+    hipLaunchKernelGGL(k_cpgrow_move, dim3(ggrid(old_total * (uint64_t)nc.stride, 16384)), dim3(256), 0, stream, orules,
+                       oper, reinterpret_cast<const uint4*>(oring), reinterpret_cast<uint4*>(nc.ring), nc.stride,
+                       (const uint32_t*)map, old_total);
+    return hipGetLastError();
+}
+
+hipError_t launch_cp_used(const uint64_t* keys, const CPBucket* ring, int stride, int S, uint64_t base, uint64_t n,
+                          unsigned long long* out2, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(out2, 0, 2 * sizeof(unsigned long long), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cptable_used, dim3(ggrid(n, 2048)), dim3(256), 0, stream, keys, ring, stride, S, base, n, out2);
+    return hipGetLastError();
+}
+
+}  // namespace sg

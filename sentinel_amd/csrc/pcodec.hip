@@ -420,6 +420,20 @@ __global__ void __launch_bounds__(256) k_vd_bytes(const VEntry* e, const uint32_
     for (uint32_t k = 0; k < x.len; ++k) o[k] = x.len <= 8 ? (uint8_t)(x.data >> (8 * k)) : arena[x.data + k];
 }
 
+// sg_vdict_grow: the zeroed main table of the grown dictionary filled from its entries, one lane per id. The hash
+// is computed again from the entry's payload with the lookup's function (vd_lookup_store), so the slot an id lands
+// on is the one every later lookup of its value probes from.
+__global__ void __launch_bounds__(256) k_vd_rehash(VDictArgs v) {
+    const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
+    if (id > v.count) return;
+    const VEntry e = v.entries[id];
+    const bool inl = e.len <= 8;
+    const uint64_t h = value_hash((e.len << 8) | e.type, inl ? e.data : 0, inl ? v.arena : v.arena + e.data);
+    const uint64_t val = (h & 0xFFFFFFFF00000000ull) | id;
+    for (uint64_t s = h & v.tab_mask;; s = (s + 1) & v.tab_mask)  // the entries are pairwise distinct: no compare
+        if (v.tab[s] == 0 && atomicCAS((unsigned long long*)&v.tab[s], 0ull, (unsigned long long)val) == 0ull) return;
+}
+
 unsigned grid_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 unsigned frame_grid(uint64_t n) {
@@ -469,6 +483,12 @@ hipError_t launch_vd_dedupe(const VDictArgs& v, hipStream_t stream) {
 
 hipError_t launch_vd_commit(const VDictArgs& v, hipStream_t stream) {
     hipLaunchKernelGGL(k_vd_commit, dim3(grid_for(v.m, 256)), dim3(256), 0, stream, v);
+    return hipGetLastError();
+}
+
+hipError_t launch_vd_rehash(const VDictArgs& v, hipStream_t stream) {
+    if (v.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_vd_rehash, dim3(grid_for(v.count, 256)), dim3(256), 0, stream, v);
     return hipGetLastError();
 }
 

@@ -200,6 +200,15 @@ def load_library():
         "sg_node_pslot_thread_count": (C.c_int, [vp, u32, C.c_int32, u64, C.POINTER(i64)]),
         "sg_node_pslot_param_idx": (C.c_int, [vp, u32, C.POINTER(C.c_int32)]),
         "sg_node_param_read_state": (C.c_int, [vp, u32, u64, vp, vp]),
+        "sg_param_resize": (C.c_int, [vp, vp, u32]),
+        "sg_param_table_used": (C.c_int, [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "sg_cparam_resize": (C.c_int, [vp, C.c_int32]),
+        "sg_cparam_table_used": (C.c_int, [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "sg_vdict_grow": (C.c_int, [vp, C.c_int32, u64]),
+        "sg_node_param_resize": (C.c_int, [vp, vp, u32]),
+        "sg_node_param_table_used": (C.c_int, [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "sg_node_cparam_resize": (C.c_int, [vp, C.c_int32]),
+        "sg_node_cparam_table_used": (C.c_int, [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("SG_LIB_PATH") and not hasattr(L, name):
@@ -519,6 +528,29 @@ class NodeEngine:
             self._check(flags)
         return flags, lt.value, tk.value
 
+    # ---- the value tables grown in place (sg_node_*_resize, sg_node_*_table_used)
+    def param_resize(self, capacity_log2):
+        """One capacity_log2 per param rule (0 keeps the size), on the front and every shard."""
+        lg = np.ascontiguousarray(capacity_log2, dtype=np.int32)
+        self._check(self._L.sg_node_param_resize(self.h, abi.ptr(lg), len(lg)))
+
+    def param_table_used(self, rule):
+        """(used, live, capacity) of the rule's value table on the owner of its resource."""
+        return _table_used(self, self._L.sg_node_param_table_used, rule)
+
+    def cparam_resize(self, capacity_log2: int):
+        self._check(self._L.sg_node_cparam_resize(self.h, capacity_log2))
+
+    def cparam_table_used(self, rule):
+        """(used, live, capacity) of the rule's value table on its owner."""
+        return _table_used(self, self._L.sg_node_cparam_table_used, rule)
+
+
+def _table_used(eng, fn, rule):
+    used, live, cap = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    eng._check(fn(eng.h, rule, C.byref(used), C.byref(live), C.byref(cap)))
+    return int(used.value), int(live.value), int(cap.value)
+
 
 class FlowEngine:
     """One sg_handle: the cluster flow rules of a token server on one GPU."""
@@ -653,6 +685,10 @@ class FlowEngine:
         nv, na = C.c_uint64(), C.c_uint64()
         self._check(self._L.sg_vdict_size(self.h, C.byref(nv), C.byref(na)))
         return int(nv.value), int(na.value)
+
+    def vdict_grow(self, capacity_log2: int, arena_bytes: int):
+        """A larger dictionary in place (both sizes at least the current ones): every id stays what it is."""
+        self._check(self._L.sg_vdict_grow(self.h, capacity_log2, arena_bytes))
 
     def codec_decode_param(self, payload_ptr: int, offsets_ptr: int, ts_ptr: int, n: int, req_ptr: int,
                            values_ptr: int, values_cap: int, xid_ptr: int, kind_ptr: int, stream_ptr: int = 0) -> int:
@@ -808,6 +844,17 @@ class FlowEngine:
         if flags < 0:
             self._check(flags)
         return flags, lt.value, tk.value
+
+    def param_resize(self, capacity_log2):
+        """The param rules' value tables grown in place: one capacity_log2 per loaded rule, 0 keeps the size (a call of
+        zeros compacts). Afterwards the engine answers as one that had these sizes from the start."""
+        lg = np.ascontiguousarray(capacity_log2, dtype=np.int32)
+        self._check(self._L.sg_param_resize(self.h, abi.ptr(lg), len(lg)))
+
+    def param_table_used(self, rule):
+        """(used, live, capacity) of the rule's value table: slots taken (what SG_E_CAPACITY goes by), those a walker
+        has counted, and 2^capacity_log2."""
+        return _table_used(self, self._L.sg_param_table_used, rule)
 
     # ---- pace controller (RateLimiterController.canPass per CONTROL_BEHAVIOR_RATE_LIMITER FlowRule)
     def pace_load_rules(self, rules: np.ndarray):
@@ -1145,3 +1192,11 @@ class FlowEngine:
         v = C.c_int64()
         self._check(self._L.sg_cparam_read_sum(self.h, rule, int(value), now, C.byref(v)))
         return v.value
+
+    def cparam_resize(self, capacity_log2: int):
+        """The cluster param rules' value tables grown in place to 2^capacity_log2 slots each."""
+        self._check(self._L.sg_cparam_resize(self.h, capacity_log2))
+
+    def cparam_table_used(self, rule):
+        """(used, live, capacity) of the rule's value table; live = values with at least one written bucket."""
+        return _table_used(self, self._L.sg_cparam_table_used, rule)
