@@ -1324,10 +1324,96 @@ typedef struct {
 int sg_rls_should_rate_limit(sg_handle* h, const sg_rls_request* req, uint32_t n, const int32_t* desc_rule,
                              uint64_t n_desc, int32_t* overall, sg_rls_status* status);
 
+/* ---- the token server's stat log: sentinel-server.log (cluster/server/log/ClusterServerStatLogUtil.java:32-52) ----
+ * Every checker behind DefaultTokenService reports through ClusterServerStatLogUtil.log(key, count): an EagleEye
+ * StatLogger with 1-second slots (time slot t - t % 1000) and one COUNT_SUM entry per key string, written as one line
+ * per entry `time|1|key|count,0` (StatLogWriteTask.run; the key is the single string, e.g. `flow|block|123`). The
+ * device keeps that rollup across batches in an exact table in device memory and hands out rows.
+ * What is logged (the event says which key, flow_id is the rule's flowId):
+ *   flow tokens (ClusterFlowChecker.java:91, 102-107; sg_flow_decide_batch, _host, sg_flow_submit, sg_flow_enqueue):
+ *     SHOULD_WAIT → SG_SLOG_FLOW_WAITING += 1; BLOCKED → SG_SLOG_FLOW_BLOCK += acquireCount and
+ *     SG_SLOG_FLOW_BLOCK_REQUEST += 1, and for a prioritized request SG_SLOG_FLOW_OCCUPIED_BLOCK += 1. OK,
+ *     TOO_MANY_REQUEST, FAIL, NO_RULE_EXISTS and BAD_REQUEST log nothing: the default server logs no passes.
+ *   RLS (SimpleClusterFlowChecker.java:49-50, 60-61; sg_rls_should_rate_limit): OK → SG_SLOG_FLOW_PASS += acquireCount
+ *     and SG_SLOG_FLOW_PASS_REQUEST += 1; BLOCKED → SG_SLOG_FLOW_BLOCK, SG_SLOG_FLOW_BLOCK_REQUEST; no waiting or
+ *     occupied rows; a descriptor without a rule and a request with hits_addend < 0 log nothing.
+ *   concurrent tokens (ConcurrentClusterFlowChecker.java:58/67, 73, 96-99; sg_conc_decide_batch, _host): an acquire's
+ *     OK → SG_SLOG_CONC_PASS += acquireCount, its BLOCKED → SG_SLOG_CONC_BLOCK += acquireCount (once: of the two
+ *     identical Java sites one runs); RELEASE_OK → SG_SLOG_CONC_RELEASE += the token's acquireCount under the token's
+ *     flowId. ALREADY_RELEASE, NO_RULE_EXISTS, BAD_REQUEST and sg_conc_expire (RegularExpireStrategy) log nothing.
+ *   cluster param tokens (ClusterParamFlowChecker.java:58-80; sg_cparam_decide_batch, _host): OK → SG_SLOG_PARAM_PASS
+ *     += 1; BLOCKED → SG_SLOG_PARAM_BLOCK += 1 with value = blockObject, the first value in request order whose check
+ *     failed, as the caller's u64 value id (the caller turns it into %s, with sg_vdict_lookup for instance).
+ *     TOO_MANY_REQUEST, NO_RULE_EXISTS and BAD_REQUEST log nothing.
+ * Not logged: the embedded token server's decisions taken inside the local chain's cx walkers
+ * (sg_local_set_cluster_state(SERVER) decides them in the walker, and which rule decided is not recoverable
+ * afterwards); ClusterConcurrentCheckerLogListener's periodic lines (sg_conc_read_state gives the caller their
+ * numbers).
+ *   sg_server_log_enable ← the StatLogger's creation: a table of 2^capacity_log2 slots (4..24), one slot per (second,
+ *     family, flowId, value) with that key's counters side by side (96 bytes a slot, three such arrays), and every
+ *     flow, concurrent and cluster param token batch decided from then on adds its logged decisions behind its
+ *     walkers. Allowed at any time (rows record only what was decided after it); a second call with the same capacity
+ *     does nothing, with another SG_E_INVAL. The table belongs to the handle and outlives every
+ *     rule reload: rows carry the flowId, not the rule index, so a reload that renumbers the rules changes nothing. A
+ *     handle that never calls it launches exactly the kernels it launched before and stores nothing extra.
+ *   sg_server_log ← the rolling task (StatLogWriteTask) at now_ms: it first drains the pipelines, then hands out every
+ *     row whose second is complete (timestamp + 1000 <= now_ms - now_ms % 1000) into HOST memory, sorted by (timestamp,
+ *     event, flow_id, value), and removes them from the table. cap too small: SG_E_CAPACITY, *n_rows = the rows needed,
+ *     nothing changes (the lost totals included). SG_E_INVAL before sg_server_log_enable. A decision whose key found
+ *     no free slot is not logged and never changes a decision: it is counted in *lost_events and its acquireCount in
+ *     *lost_count, reported by the next successful call and cleared by it. A row exists if and only if its count is
+ *     non-zero (every request that reaches a checker has acquireCount >= 1, DefaultTokenService.java:87-93). One row
+ *     per key and second (the reference's maxEntryCount(5000) rolls the map early, so a key can have several lines in
+ *     a second: summed per key and second they equal the row). */
+#define SG_SLOG_FLOW_WAITING         0   /* flow|waiting|id            += 1            */
+#define SG_SLOG_FLOW_BLOCK           1   /* flow|block|id              += acquireCount */
+#define SG_SLOG_FLOW_BLOCK_REQUEST   2   /* flow|block_request|id      += 1            */
+#define SG_SLOG_FLOW_OCCUPIED_BLOCK  3   /* flow|occupied_block|id     += 1            */
+#define SG_SLOG_FLOW_PASS            4   /* flow|pass|id               += acquireCount (RLS only) */
+#define SG_SLOG_FLOW_PASS_REQUEST    5   /* flow|pass_request|id       += 1            (RLS only) */
+#define SG_SLOG_PARAM_PASS           6   /* param|pass|id              += 1            */
+#define SG_SLOG_PARAM_BLOCK          7   /* param|block|id|value       += 1            */
+#define SG_SLOG_CONC_PASS            8   /* concurrent|pass|id         += acquireCount */
+#define SG_SLOG_CONC_BLOCK           9   /* concurrent|block|id        += acquireCount */
+#define SG_SLOG_CONC_RELEASE        10   /* concurrent|release|id      += the token's acquireCount */
+typedef struct sg_server_row {
+    int64_t  timestamp;   /* the second: t - t % 1000                         */
+    int64_t  count;
+    int64_t  flow_id;     /* the rule's flowId, not its index                 */
+    uint64_t value;       /* SG_SLOG_PARAM_BLOCK: the blocking value's id, else 0 */
+    int32_t  event;       /* SG_SLOG_*                                        */
+    int32_t  reserved;
+} sg_server_row;
+int sg_server_log_enable(sg_handle* h, int32_t capacity_log2);
+int sg_server_log(sg_handle* h, int64_t now_ms, sg_server_row* rows, uint64_t cap, uint64_t* n_rows,
+                  uint64_t* lost_events, uint64_t* lost_count);
+/* The two logs over the node handle, with the contracts of sg_server_log_enable / sg_server_log and
+ * sg_local_block_log_enable / sg_local_block_log word for word but for these points.
+ *   sg_node_server_log_enable enables the front and every shard: sg_node_flow_decide_batch(_host), sg_node_flow_enqueue,
+ *     sg_node_conc_* and sg_node_cparam_* then log on the shard that decides, and param tokens decided on the front
+ *     (sg_node_front, rules under an enabled limiter) on the front. sg_node_local_block_log_enable enables every shard.
+ *     If one handle fails (SG_E_NOMEM, SG_E_DEVICE) the handles before it stay enabled and log, the node's log counts as
+ *     off (the fetch is SG_E_INVAL), and the same call again completes the rest.
+ *   sg_node_server_log collects every handle's rows, sums rows with equal keys (a rule served by the front and by a
+ *     shard stays one row), adds the lost totals and sorts. sg_node_local_block_log concatenates and sorts: a resource
+ *     has one owner shard, so no key can come from two; the call checks that (SG_E_DEVICE, the rows kept for the next
+ *     call, if it ever fails). cap too small: SG_E_CAPACITY with *n_rows = the sum of the parts' rows, which is
+ *     sufficient (equal keys only merge), and nothing changes. If a handle fails in the middle of a fetch, the rows
+ *     and lost totals already taken from the handles before it are kept in the node and handed out by the next
+ *     successful call; the failing handle and those after it keep theirs in their tables. */
+int sg_node_server_log_enable(sg_node* nd, int32_t capacity_log2);
+int sg_node_server_log(sg_node* nd, int64_t now_ms, sg_server_row* rows, uint64_t cap, uint64_t* n_rows,
+                       uint64_t* lost_events, uint64_t* lost_count);
+int sg_node_local_block_log_enable(sg_node* nd, int32_t capacity_log2);
+int sg_node_local_block_log(sg_node* nd, int64_t now_ms, sg_block_row* rows, uint64_t cap, uint64_t* n_rows,
+                            uint64_t* lost_events, uint64_t* lost_count);
+
 /* Testing aid: copy an internal buffer of the last batch to host memory.
  * what: 0 = records (request order, u64; on the binned flow path with compact front records, u32
  * {bin digit | key in bin | acquire code} in the buffer's first half), 1 = records sorted by flowId, 2 = window-period table
- * (u32 [8][65536]), 3 = first period per window length (i64[8]), 4 = periods per window length (u32[8]). */
+ * (u32 [8][65536]), 3 = first period per window length (i64[8]), 4 = periods per window length (u32[8]), 6 = the
+ * saturated ranges the last cluster param walk handed to its skip pass (u32; a batch with multi-value requests
+ * clears it between its rounds, SG_E_INVAL before the first cluster param batch). */
 int sg_debug_copy(sg_handle* h, int what, void* dst, uint64_t bytes);
 
 /* Library build identification (architecture the kernels were compiled for). */

@@ -179,6 +179,13 @@ BLOCK_ROW_DTYPE = np.dtype([("timestamp", "<i8"), ("count", "<i8"), ("app", "<u8
 assert BLOCK_ROW_DTYPE.itemsize == 40
 (BLOCK_APP_LIMIT_APP, BLOCK_APP_ORIGIN, BLOCK_APP_SYSTEM, BLOCK_APP_VALUE, BLOCK_APP_NULL_ARG, BLOCK_APP_NO_ARG,
  BLOCK_APP_LABEL) = range(7)
+# the token server's stat log (sg_server_log): one sentinel-server.log row; event names the key
+SERVER_ROW_DTYPE = np.dtype([("timestamp", "<i8"), ("count", "<i8"), ("flow_id", "<i8"), ("value", "<u8"),
+                             ("event", "<i4"), ("reserved", "<i4")], align=True)
+assert SERVER_ROW_DTYPE.itemsize == 40
+(SLOG_FLOW_WAITING, SLOG_FLOW_BLOCK, SLOG_FLOW_BLOCK_REQUEST, SLOG_FLOW_OCCUPIED_BLOCK, SLOG_FLOW_PASS,
+ SLOG_FLOW_PASS_REQUEST, SLOG_PARAM_PASS, SLOG_PARAM_BLOCK, SLOG_CONC_PASS, SLOG_CONC_BLOCK,
+ SLOG_CONC_RELEASE) = range(11)
 CONTROL_DEFAULT, CONTROL_WARM_UP, CONTROL_RATE_LIMITER, CONTROL_WARM_UP_RATE_LIMITER = 0, 1, 2, 3
 LIMIT_APP_DEFAULT, LIMIT_APP_OTHER = 0, -1
 STRATEGY_DIRECT, STRATEGY_RELATE, STRATEGY_CHAIN = 0, 1, 2

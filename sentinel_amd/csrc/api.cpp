@@ -283,6 +283,16 @@ struct sg_handle {
     DevBuf<int32_t> d_blog_app;       // [max_batch] LArgs::blog_app
     DevBuf<int32_t> d_lres_app;       // [K] LArgs::res_app
     std::vector<int32_t> l_res_app;   // its host copy (blocklog_rules.h), kept whether or not the log is on
+    // the token server's stat log (sg_server_log_enable; null d_slog: off)
+    DevBuf<SlogSlot> d_slog;          // the table, 2^slog_log2 slots; outlives every rule reload
+    int32_t slog_log2 = 0;
+    DevBuf<unsigned long long> d_slog_ctr;  // {lost decisions, lost count, rows / slots taken, slots kept}
+    DevBuf<SlogSlot> d_slog_rows, d_slog_keep;  // [slots] the fetch's complete slots / survivors
+    DevBuf<int64_t> d_slog_fid;       // [K] SlogArgs::fid, uploaded with the rules while the log is on
+    DevBuf<int64_t> d_slog_cpfid;     // [cluster param rules] SlogArgs::cpfid, the same way
+    DevBuf<uint32_t> d_slog_blk;      // [max_batch] CPBatch::slog_blk, from the first cluster param batch with the log on
+    DevBuf<int32_t> d_slog_rel;       // [max_batch] ConcArgs::slog_rel, from the first concurrent batch with the log on
+    bool slog_rls = false;            // SlogArgs::rls: set by sg_rls_should_rate_limit for the duration of its batch
 
     int kbits = 0, ibits = 0, abits = 0;
     int32_t shard_rank = 0, shard_world = 1;  // sg_set_shard: this handle's share of a node's flowIds
@@ -770,6 +780,48 @@ int sg_set_namespaces(sg_handle* h, const sg_namespace* ns, uint32_t n) {
 
 namespace {
 
+// The stat log's flowId of every flow rule (SlogArgs::fid), uploaded when the log is enabled and with every rule load
+// while it is on. The caller has drained the pipelines: no batch in flight reads the array it replaces.
+int slog_sync_fids(sg_handle* h) {
+    if (!h->d_slog) return SG_OK;
+    std::vector<int64_t> fid(std::max<uint32_t>(h->K, 1u), 0);
+    for (uint32_t k = 0; k < h->K; ++k) fid[k] = h->rules[k].flow_id;
+    std::vector<int64_t> cpfid(std::max<size_t>(h->cprules.size(), 1), 0);
+    for (size_t k = 0; k < h->cprules.size(); ++k) cpfid[k] = h->cprules[k].flow_id;
+    DevBuf<int64_t> d, dc;  // both built before either replaces the live one: a failure leaves the pair as it was
+    if (!d.alloc(fid.size()) || !dc.alloc(cpfid.size())) return fail(h, SG_E_NOMEM, "server log flowIds");
+    HIP_TRY(h, hipMemcpy(d, fid.data(), sizeof(int64_t) * fid.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(dc, cpfid.data(), sizeof(int64_t) * cpfid.size(), hipMemcpyHostToDevice));
+    h->d_slog_fid = std::move(d);
+    h->d_slog_cpfid = std::move(dc);
+    return SG_OK;
+}
+
+SlogArgs slog_args(sg_handle* h) {
+    SlogArgs s{};
+    s.tab = h->d_slog;
+    s.mask = h->d_slog.size() - 1;
+    s.lost = h->d_slog_ctr;
+    s.fid = h->d_slog_fid;
+    s.cpfid = h->d_slog_cpfid;
+    s.rls = h->slog_rls ? 1 : 0;
+    return s;
+}
+
+// The stat log's add for the decided flow batch a (flow_back, a node shard's back half): behind launch_skip_apply,
+// where the results of the wave walker's skipped ranges exist, and before the workspace's next user.
+int slog_add_flow(sg_handle* h, const BatchArgs& a, hipStream_t stream, uint64_t n_req = 0) {
+    SlogArgs s = slog_args(h);
+    s.n_req = n_req;
+    s.drop = a.rec4 ? a.bin_tot + kBinDrop : nullptr;
+    HIP_TRY(h, launch_slog_add_flow(a, s, stream));
+    return SG_OK;
+}
+
+}  // namespace
+
+namespace {
+
 // Every check sg_load_flow_rules makes before it changes anything (FlowRuleUtil.isValidRule / checkClusterField,
 // FlowRuleUtil.java:167-229, and the device path's limits: sampleCount <= 64 for a surviving metric's window shape
 // too, <= 8 distinct window lengths with the limiter's 100 ms): after SG_OK only allocation or device errors remain.
@@ -921,6 +973,8 @@ int flow_rules_commit(sg_handle* h, const sg_flow_rule* rules, uint32_t n, FlowL
     int rc = layout_records(h);
     if (rc) return rc;
     rc = upload_fid_table(h);
+    if (rc) return rc;
+    rc = slog_sync_fids(h);
     if (rc) return rc;
     return upload_rule_table(h);
 }
@@ -1548,6 +1602,7 @@ int flow_front(sg_handle* h, BatchArgs& a, uint32_t* hist, hipStream_t stream, b
     if (stats) HIP_TRY(h, hipEventRecord(h->ev[1], stream));
     if (a.bin_on) {  // one scatter pass by bin digit, the regular bins sorted and every segment listed in LDS
         HIP_TRY(h, launch_bin_front(a, hist, true, a.csum0 != nullptr, stream));
+        a.bin_tot = radix_tot(hist, a.n, kBinDigit);  // the stat log's add reads the rejected requests' total
         if (stats) HIP_TRY(h, hipEventRecord(h->ev[2], stream));
         return SG_OK;
     }
@@ -1581,6 +1636,10 @@ int flow_back(sg_handle* h, const BatchArgs& a, hipStream_t stream, hipStream_t 
     }
     HIP_TRY(h, launch_skip_apply(a, stream));
     if (stats) HIP_TRY(h, hipEventRecord(h->ev[3], stream));
+    if (h->d_slog) {  // the token server's stat log, behind the decisions
+        const int src = slog_add_flow(h, a, stream);
+        if (src) return src;
+    }
     HIP_TRY(h, launch_finish(a, stream));
     HIP_TRY(h, hipMemcpyAsync(err_dst, a.err, sizeof(int), hipMemcpyDeviceToHost, stream));
     if (stats) {
@@ -1988,7 +2047,9 @@ int sg_rls_should_rate_limit(sg_handle* h, const sg_rls_request* req, uint32_t n
     }
     std::vector<sg_result> res(batch.size());
     if (!batch.empty()) {
+        h->slog_rls = true;  // SimpleClusterFlowChecker's log calls for this batch (the stat log's add reads it)
         const int rc = sg_flow_decide_batch_host(h, batch.data(), batch.size(), res.data());
+        h->slog_rls = false;
         if (rc) return rc;
     }
     for (uint64_t x = 0; x < batch.size(); ++x) {
@@ -2546,7 +2607,9 @@ int sg_cparam_load_rules(sg_handle* h, const sg_cparam_rule* rules, uint32_t n, 
         const int64_t neg = -1;
         HIP_TRY(h, hipMemcpy(h->d_cplast_ts, &neg, sizeof(neg), hipMemcpyHostToDevice));
     }
-    return upload_cp_fid_table(h, rules, n);  // sg_codec_decode_param's flowId lookup
+    const int frc = upload_cp_fid_table(h, rules, n);  // sg_codec_decode_param's flowId lookup
+    if (frc) return frc;
+    return slog_sync_fids(h);
 }
 
 static CPArgs cp_args(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint64_t* values, uint64_t n_values,
@@ -2737,6 +2800,11 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
     b.mlist = h->d_cp_mlist;
     b.mcount = h->d_cp_counts + 4;
     b.lim = any_lim ? 1 : 0;
+    if (h->d_slog) {  // the stat log: the group fallback's replay notes where it blocked a request
+        if (!h->d_slog_blk && !h->d_slog_blk.alloc(h->cfg.max_batch)) return fail(h, SG_E_NOMEM, "server log positions");
+        b.slog_blk = h->d_slog_blk;
+        HIP_TRY(h, hipMemsetAsync(b.slog_blk, 0xFF, sizeof(uint32_t) * n, stream));
+    }
     HIP_TRY(h, hipMemsetAsync(h->d_cp_changed, 0, sizeof(int), stream));
     HIP_TRY(h, hipMemsetAsync(b.mcount, 0, sizeof(uint32_t), stream));
     HIP_TRY(h, launch_cp_prep2(c, b, stream));  // sets *changed iff a request has several values, lists them
@@ -2932,6 +3000,7 @@ int cparam_batch(sg_handle* h, const sg_cparam_req* req, uint64_t n, const uint6
         HIP_TRY(h, launch_cpfb(c, b, g, 3, m, stream));
     }
     h->cp_rounds = converged ? (round ? round : 1) : kMaxRounds + 1;
+    if (h->d_slog) HIP_TRY(h, launch_slog_add_param(c, b, slog_args(h), stream));  // behind the last writer of out
     HIP_TRY(h, launch_cp_finish_batch(c, stream));
     HIP_TRY(h, hipMemcpyAsync(&err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
@@ -4006,6 +4075,87 @@ int sg_local_block_log(sg_handle* h, int64_t now_ms, sg_block_row* rows, uint64_
     return SG_OK;
 }
 
+int sg_server_log_enable(sg_handle* h, int32_t capacity_log2) {
+    if (!h) return SG_E_INVAL;
+    if (!slog_capacity_ok(capacity_log2)) return fail(h, SG_E_INVAL, "capacity_log2 outside 4..24");
+    if (h->d_slog)
+        return capacity_log2 == h->slog_log2 ? SG_OK : fail(h, SG_E_INVAL, "the server log has another capacity");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);  // batches already enqueued stay unlogged: rows record what is decided from here on
+    const size_t slots = (size_t)slog_slots(capacity_log2);
+    DevBuf<SlogSlot> tab, rows, keep;
+    DevBuf<unsigned long long> ctr;
+    if (!tab.alloc(slots) || !ctr.alloc(4) || !rows.alloc(slots) || !keep.alloc(slots))
+        return fail(h, SG_E_NOMEM, "server log table");
+    HIP_TRY(h, hipMemset(tab, 0, sizeof(SlogSlot) * slots));
+    HIP_TRY(h, hipMemset(ctr, 0, sizeof(unsigned long long) * 4));
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->d_slog = std::move(tab);
+    h->d_slog_ctr = std::move(ctr);
+    h->d_slog_rows = std::move(rows);
+    h->d_slog_keep = std::move(keep);
+    h->slog_log2 = capacity_log2;
+    const int rc = slog_sync_fids(h);
+    if (rc) {  // off again, and everything the call allocated freed: a handle is never left with half of the log's state
+        h->d_slog.reset();
+        h->d_slog_ctr.reset();
+        h->d_slog_rows.reset();
+        h->d_slog_keep.reset();
+        h->d_slog_fid.reset();
+        h->d_slog_cpfid.reset();
+        h->slog_log2 = 0;
+    }
+    return rc;
+}
+
+int sg_server_log(sg_handle* h, int64_t now_ms, sg_server_row* rows, uint64_t cap, uint64_t* n_rows,
+                  uint64_t* lost_events, uint64_t* lost_count) {
+    if (!h || !n_rows || !lost_events || !lost_count || (!rows && cap)) return SG_E_INVAL;
+    *n_rows = *lost_events = *lost_count = 0;
+    if (!h->d_slog) return fail(h, SG_E_INVAL, "sg_server_log_enable first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    HIP_TRY(h, hipDeviceSynchronize());  // the device-resident entry points' batches too
+    const SlogArgs b = slog_args(h);
+    unsigned long long* ctr = h->d_slog_ctr;
+    const int64_t limit = now_ms - now_ms % 1000;
+    unsigned long long c[4] = {0, 0, 0, 0};
+    // the count pass changes nothing: a capacity that is too small leaves the table and the lost totals as they were
+    HIP_TRY(h, hipMemsetAsync(ctr + 2, 0, 2 * sizeof(unsigned long long), 0));
+    HIP_TRY(h, launch_slog_take(b, limit, 0, nullptr, nullptr, ctr + 2, ctr + 3, 0));
+    HIP_TRY(h, hipMemcpy(c, ctr, sizeof(c), hipMemcpyDeviceToHost));
+    if (slog_cap_answer(c[2], cap, n_rows) != SG_OK) return fail(h, SG_E_CAPACITY, "server log rows exceed cap");
+    if (c[2]) {
+        // copy the complete slots out and list the others (the table itself is only read), expand on the host, and only
+        // when the rows are what the count pass promised clear the table and put the open seconds' slots back
+        HIP_TRY(h, hipMemsetAsync(ctr + 2, 0, 2 * sizeof(unsigned long long), 0));
+        HIP_TRY(h, launch_slog_take(b, limit, 1, h->d_slog_rows, h->d_slog_keep, ctr + 2, ctr + 3, 0));
+        unsigned long long taken = 0;
+        HIP_TRY(h, hipMemcpy(&taken, ctr + 2, sizeof(taken), hipMemcpyDeviceToHost));
+        std::vector<SlogSlot> slots((size_t)taken);
+        if (taken)
+            HIP_TRY(h, hipMemcpy(slots.data(), h->d_slog_rows, sizeof(SlogSlot) * taken, hipMemcpyDeviceToHost));
+        std::vector<sg_server_row> out;
+        out.reserve((size_t)c[2]);
+        for (const SlogSlot& s : slots) {
+            SlogCounters k{s.ts, s.flow_id, s.value, s.family, {}};
+            for (int x = 0; x < kSlogCtrs; ++x) k.c[x] = s.c[x];
+            slog_expand(k, out);
+        }
+        slog_sort_merge(out);  // a handle's keys are distinct: the sort alone
+        if (out.size() != c[2])  // nothing was removed yet: the table still holds every row
+            return fail(h, SG_E_DEVICE, "server log rows changed between the count and the fetch");
+        HIP_TRY(h, hipMemsetAsync(h->d_slog, 0, sizeof(SlogSlot) * h->d_slog.size(), 0));
+        HIP_TRY(h, launch_slog_put(b, h->d_slog_keep, ctr + 3, 0));
+        std::copy(out.begin(), out.end(), rows);
+    }
+    HIP_TRY(h, hipMemset(ctr, 0, 2 * sizeof(unsigned long long)));
+    HIP_TRY(h, hipDeviceSynchronize());
+    *lost_events = c[0];
+    *lost_count = c[1];
+    return SG_OK;
+}
+
 int sg_local_poll(sg_handle* h, uint64_t ticket) { return sg_flow_poll(h, ticket); }
 
 int sg_local_wait(sg_handle* h, uint64_t ticket) { return sg_flow_wait(h, ticket); }
@@ -4759,8 +4909,13 @@ int sg_conc_decide_batch(sg_handle* h, const sg_conc_req* req, uint64_t n, sg_co
     c.rec = h->ws[0].rec;
     c.kshift = 64 - kbits;
     c.imask = (1ull << c.kshift) - 1;
+    if (h->d_slog) {  // the stat log: the walker stores each released token's count beside its result
+        if (!h->d_slog_rel && !h->d_slog_rel.alloc(h->cfg.max_batch)) return fail(h, SG_E_NOMEM, "server log release counts");
+        c.slog_rel = h->d_slog_rel;
+    }
     HIP_TRY(h, hipMemsetAsync(h->ws[0].err, 0, sizeof(int), stream));
     HIP_TRY(h, launch_conc_batch(c, h->ws[0].rec_sorted, h->ws[0].hist, stream));
+    if (h->d_slog) HIP_TRY(h, launch_slog_add_conc(c, slog_args(h), stream));  // behind the batch's last writer of out
     HIP_TRY(h, hipMemcpyAsync(h->h_err, h->ws[0].err, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
     if (*h->h_err & kErrTime)
@@ -5079,9 +5234,10 @@ int sg_debug_copy(sg_handle* h, int what, void* dst, uint64_t bytes) {
     case 3: src = h->ws[0].p0; cap = sizeof(int64_t) * kMaxWl; break;
     case 4: src = h->ws[0].np; cap = sizeof(uint32_t) * kMaxWl; break;
     case 5: src = h->d_dbg; cap = 128 * 8; break;
+    case 6: src = h->d_cp_skip_count; cap = h->d_cp_skip_count ? sizeof(uint32_t) : 0; break;
     default: return SG_E_INVAL;
     }
-    if (bytes > cap) return SG_E_INVAL;
+    if (bytes > cap || !src) return SG_E_INVAL;
     HIP_TRY(h, hipSetDevice(h->device));
     if (what == 1 && h->last_rec4_n > 0 && src == h->ws[0].rec_sorted && h->ws[0].bin_buf) {
         // the compact layout keeps 4-byte sorted records: the 8-byte view is rebuilt from them and the batch's segment
@@ -5233,6 +5389,13 @@ struct sg_node {
     DevBuf<MergeSlots> d_mslots;
     DevBuf<sg_metric_node> d_mrows;         // the shards' raw rows (grown on demand)
     DevBuf<sg_metric_node> d_mout;          // the host form's merged table
+    // the node's logs (sg_node_server_log_enable / sg_node_local_block_log_enable; 0: off). Rows a fetch took from
+    // some handles before another failed, and lost totals already consumed from a handle, wait here for the next
+    // successful fetch: nothing a handle handed out is dropped.
+    int32_t slog_log2 = 0, blog_log2 = 0;
+    std::vector<sg_server_row> slog_held;
+    std::vector<sg_block_row> blog_held;
+    uint64_t slog_lost[2] = {0, 0}, blog_lost[2] = {0, 0};
 };
 
 namespace {
@@ -5326,8 +5489,9 @@ void node_sync_shards(sg_node* nd, uint32_t g) {
 // One shard's slice of a node batch on the records path: the sort of its records (node request indices), its
 // segments, both walkers and the skipped BLOCK counts, its error word into err_dst. `front` carries the sort and
 // segments, `back` the walkers (the same stream for a synchronous node batch); front_done (may be null) joins them.
-int node_shard_rec(sg_handle* h, BatchArgs b, uint64_t cnt, uint32_t* hist, hipStream_t front, hipStream_t back,
-                   hipStream_t aux, hipEvent_t fork, hipEvent_t join, hipEvent_t front_done, int* err_dst) {
+int node_shard_rec(sg_handle* h, BatchArgs b, uint64_t cnt, uint64_t n_node, uint32_t* hist, hipStream_t front,
+                   hipStream_t back, hipStream_t aux, hipEvent_t fork, hipEvent_t join, hipEvent_t front_done,
+                   int* err_dst) {
     HIP_TRY(h, hipMemsetAsync(b.err, 0, sizeof(int), front));
     HIP_TRY(h, hipMemsetAsync(b.long_count, 0, (1 + kClasses) * sizeof(uint32_t), front));
     HIP_TRY(h, hipMemsetAsync(b.skip_count, 0, sizeof(uint32_t), front));
@@ -5347,6 +5511,10 @@ int node_shard_rec(sg_handle* h, BatchArgs b, uint64_t cnt, uint32_t* hist, hipS
     HIP_TRY(h, hipEventRecord(join, aux));
     HIP_TRY(h, hipStreamWaitEvent(back, join, 0));
     HIP_TRY(h, launch_skip_apply(b, back));
+    if (h->d_slog) {  // the token server's stat log (sg_node_server_log_enable), behind the slice's decisions
+        const int src = slog_add_flow(h, b, back, n_node);
+        if (src) return src;
+    }
     HIP_TRY(h, hipMemcpyAsync(err_dst, b.err, sizeof(int), hipMemcpyDeviceToHost, back));
     return SG_OK;
 }
@@ -5668,7 +5836,7 @@ int sg_node_flow_decide_batch(sg_node* nd, const sg_req* req, uint64_t n, sg_res
             b.np = a.np;
             b.walk_cus = node_walk_cus(nd, g, 0);
             hipStream_t st = nd->sh[g].stream;
-            rc = node_shard_rec(h, b, cnt, direct ? w.hist : sw.hist, st, st, h->aux, h->fork, h->join, nullptr,
+            rc = node_shard_rec(h, b, cnt, n, direct ? w.hist : sw.hist, st, st, h->aux, h->fork, h->join, nullptr,
                                 nd->sh[g].h_err);
             if (rc) {
                 node_sync_shards(nd, g + 1);
@@ -5848,7 +6016,7 @@ int sg_node_flow_enqueue(sg_node* nd, const sg_req* req, uint64_t n, sg_result* 
             src[g] = SG_E_DEVICE;
             return;
         }
-        src[g] = node_shard_rec(h, b, cnt, direct ? w.hist : sw.hist, h->s_front, h->s_back, h->s_aux2, h->pfork,
+        src[g] = node_shard_rec(h, b, cnt, n, direct ? w.hist : sw.hist, h->s_front, h->s_back, h->s_aux2, h->pfork,
                                 h->pjoin, h->front_done[x], &sl.h_err[g]);
         if (src[g] == SG_OK && hipEventRecord(h->back_done[x], h->s_back) != hipSuccess) src[g] = SG_E_DEVICE;
     };
@@ -5896,6 +6064,132 @@ static int node_collect(sg_node* nd, uint64_t ticket, bool block) {
         return st == SG_OK ? 1 : st;
     }
     return nfail(nd, SG_E_INVAL, "unknown or already collected ticket");
+}
+
+// One fetch over several handles, for both logs. Phase 1 asks every handle for its row count with cap 0, which
+// changes nothing there (a handle without complete rows answers SG_OK and has handed out its lost totals: they are
+// kept in lost[]); the sum, with the rows held from an earlier failed fetch, is what the caller's cap must hold.
+// Phase 2 takes each handle's rows into held[]; an error ends the call with the rows taken so far still held.
+extern "C++" {
+template <class Row, class Fetch>
+static int node_log_fetch(sg_node* nd, const std::vector<sg_handle*>& hs, Fetch fetch, std::vector<Row>& held,
+                          uint64_t* lost, uint64_t cap, uint64_t* n_rows) {
+    std::vector<uint64_t> need(hs.size(), 0);
+    uint64_t sum = held.size();
+    for (size_t g = 0; g < hs.size(); ++g) {
+        uint64_t le = 0, lc = 0;
+        const int rc = fetch(hs[g], (Row*)nullptr, 0, &need[g], &le, &lc);
+        if (rc == SG_OK) {
+            lost[0] += le;
+            lost[1] += lc;
+        } else if (rc != SG_E_CAPACITY) {
+            return node_child(nd, hs[g], rc);
+        }
+        sum += need[g];
+    }
+    *n_rows = sum;
+    if (sum > cap) return nfail(nd, SG_E_CAPACITY, "log rows exceed cap");
+    for (size_t g = 0; g < hs.size(); ++g) {
+        if (!need[g]) continue;
+        std::vector<Row> tmp((size_t)need[g]);
+        uint64_t m = 0, le = 0, lc = 0;
+        const int rc = fetch(hs[g], tmp.data(), need[g], &m, &le, &lc);
+        if (rc) return node_child(nd, hs[g], rc);
+        held.insert(held.end(), tmp.begin(), tmp.begin() + (size_t)m);
+        lost[0] += le;
+        lost[1] += lc;
+    }
+    return SG_OK;
+}
+}  // extern "C++"
+
+static std::vector<sg_handle*> node_log_handles(sg_node* nd, bool with_front) {
+    std::vector<sg_handle*> hs;
+    if (with_front && nd->front) hs.push_back(nd->front);
+    hs.insert(hs.end(), nd->shards.begin(), nd->shards.end());
+    return hs;
+}
+
+int sg_node_server_log_enable(sg_node* nd, int32_t capacity_log2) {
+    if (!nd) return SG_E_INVAL;
+    if (!slog_capacity_ok(capacity_log2)) return nfail(nd, SG_E_INVAL, "capacity_log2 outside 4..24");
+    if (nd->slog_log2)
+        return capacity_log2 == nd->slog_log2 ? SG_OK : nfail(nd, SG_E_INVAL, "the server log has another capacity");
+    node_drain(nd);
+    for (sg_handle* h : node_log_handles(nd, true)) {  // the front too: it decides param tokens under a limiter
+        const int rc = sg_server_log_enable(h, capacity_log2);
+        if (rc) return node_child(nd, h, rc);  // the handles before it stay on; the same call again completes the rest
+    }
+    nd->slog_log2 = capacity_log2;
+    return SG_OK;
+}
+
+int sg_node_server_log(sg_node* nd, int64_t now_ms, sg_server_row* rows, uint64_t cap, uint64_t* n_rows,
+                       uint64_t* lost_events, uint64_t* lost_count) {
+    if (!nd || !n_rows || !lost_events || !lost_count || (!rows && cap)) return SG_E_INVAL;
+    *n_rows = *lost_events = *lost_count = 0;
+    if (!nd->slog_log2) return nfail(nd, SG_E_INVAL, "sg_node_server_log_enable first");
+    node_drain(nd);
+    const int rc = node_log_fetch<sg_server_row>(
+        nd, node_log_handles(nd, true),
+        [&](sg_handle* h, sg_server_row* r, uint64_t c, uint64_t* n, uint64_t* le, uint64_t* lc) {
+            return sg_server_log(h, now_ms, r, c, n, le, lc);
+        },
+        nd->slog_held, nd->slog_lost, cap, n_rows);
+    if (rc) return rc;
+    slog_sort_merge(nd->slog_held);  // a rule served by the front and by a shard stays one row
+    *n_rows = nd->slog_held.size();
+    std::copy(nd->slog_held.begin(), nd->slog_held.end(), rows);
+    nd->slog_held.clear();
+    *lost_events = nd->slog_lost[0];
+    *lost_count = nd->slog_lost[1];
+    nd->slog_lost[0] = nd->slog_lost[1] = 0;
+    return SG_OK;
+}
+
+int sg_node_local_block_log_enable(sg_node* nd, int32_t capacity_log2) {
+    if (!nd) return SG_E_INVAL;
+    if (capacity_log2 < 4 || capacity_log2 > 24) return nfail(nd, SG_E_INVAL, "capacity_log2 outside 4..24");
+    if (nd->blog_log2)
+        return capacity_log2 == nd->blog_log2 ? SG_OK : nfail(nd, SG_E_INVAL, "the block log has another capacity");
+    node_drain(nd);
+    for (sg_handle* h : nd->shards) {
+        const int rc = sg_local_block_log_enable(h, capacity_log2);
+        if (rc) return node_child(nd, h, rc);  // the shards before it stay on; the same call again completes the rest
+    }
+    nd->blog_log2 = capacity_log2;
+    return SG_OK;
+}
+
+int sg_node_local_block_log(sg_node* nd, int64_t now_ms, sg_block_row* rows, uint64_t cap, uint64_t* n_rows,
+                            uint64_t* lost_events, uint64_t* lost_count) {
+    if (!nd || !n_rows || !lost_events || !lost_count || (!rows && cap)) return SG_E_INVAL;
+    *n_rows = *lost_events = *lost_count = 0;
+    if (!nd->blog_log2) return nfail(nd, SG_E_INVAL, "sg_node_local_block_log_enable first");
+    node_drain(nd);
+    const int rc = node_log_fetch<sg_block_row>(
+        nd, node_log_handles(nd, false),
+        [&](sg_handle* h, sg_block_row* r, uint64_t c, uint64_t* n, uint64_t* le, uint64_t* lc) {
+            return sg_local_block_log(h, now_ms, r, c, n, le, lc);
+        },
+        nd->blog_held, nd->blog_lost, cap, n_rows);
+    if (rc) return rc;
+    auto key = [](const sg_block_row& x) {
+        return std::tie(x.timestamp, x.resource, x.status, x.app_kind, x.app, x.origin);
+    };
+    std::sort(nd->blog_held.begin(), nd->blog_held.end(),
+              [&](const sg_block_row& x, const sg_block_row& y) { return key(x) < key(y); });
+    // a resource has one owner shard, so no key comes from two of them: checked, not trusted (the rows stay held)
+    for (size_t i = 1; i < nd->blog_held.size(); ++i)
+        if (key(nd->blog_held[i - 1]) == key(nd->blog_held[i]))
+            return nfail(nd, SG_E_DEVICE, "a block log key came from two shards: a resource has one owner");
+    *n_rows = nd->blog_held.size();
+    std::copy(nd->blog_held.begin(), nd->blog_held.end(), rows);
+    nd->blog_held.clear();
+    *lost_events = nd->blog_lost[0];
+    *lost_count = nd->blog_lost[1];
+    nd->blog_lost[0] = nd->blog_lost[1] = 0;
+    return SG_OK;
 }
 
 int sg_node_flow_poll(sg_node* nd, uint64_t ticket) { return node_collect(nd, ticket, false); }

@@ -132,7 +132,9 @@ __global__ void __launch_bounds__(256) k_conc_walk(ConcArgs c) {
                 const uint64_t j = e.token_id - c.base - 1;
                 if (c.alive[j]) {
                     c.alive[j] = 0;
-                    now = (int32_t)((uint32_t)now - (uint32_t)c.req[j].acquire);
+                    const int32_t cnt = c.req[j].acquire;
+                    now = (int32_t)((uint32_t)now - (uint32_t)cnt);
+                    if (c.slog_rel) c.slog_rel[i] = cnt;  // the stat log's concurrent|release count
                     put(c, i, SG_STATUS_RELEASE_OK, 0);
                 } else {
                     put(c, i, SG_STATUS_ALREADY_RELEASE, 0);
@@ -143,7 +145,9 @@ __global__ void __launch_bounds__(256) k_conc_walk(ConcArgs c) {
                     put(c, i, SG_STATUS_ALREADY_RELEASE, 0);
                 } else {
                     c.tab[s].state = 2;
-                    now = (int32_t)((uint32_t)now - (uint32_t)c.tab[s].acquire);
+                    const int32_t cnt = c.tab[s].acquire;
+                    now = (int32_t)((uint32_t)now - (uint32_t)cnt);
+                    if (c.slog_rel) c.slog_rel[i] = cnt;
                     put(c, i, SG_STATUS_RELEASE_OK, 0);
                 }
             }

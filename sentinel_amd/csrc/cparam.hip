@@ -1276,13 +1276,16 @@ __global__ void __launch_bounds__(256) k_cpfb_replay(CPArgs c, CPBatch b, CPGrou
             const int64_t P = q.ts_ms / r.wl;
             bool pass = true;
             double rem = -1;
+            uint32_t at = 0;  // the position whose check failed (ClusterParamFlowChecker's blockObject)
             for (uint32_t v = 0; v < q.value_count && pass; ++v) {
                 const uint64_t gs = b.pslot[q.value_begin + v];
                 int64_t cur = 0;
                 const int64_t other = cp_window(c.ring + gs * (uint64_t)c.stride, r.S, r.wl, P, &cur);
                 rem = cp_threshold(c, r, c.values[q.value_begin + v]) - avg_div((double)(other + cur), r.isec) - (double)q.acquire;
                 pass = rem >= 0;
+                at = v;
             }
+            if (b.slog_blk && !pass) b.slog_blk[i] = at;  // the stat log's param|block value
             if (pass) {
                 for (uint32_t v = 0; v < q.value_count; ++v) {
                     CPBucket& bk = c.ring[(uint64_t)b.pslot[q.value_begin + v] * c.stride + (int)(P % r.S)];

@@ -9,6 +9,7 @@
 #include "../../include/sentinel_gpu.h"
 #include "authority_rules.h"
 #include "blocklog_rules.h"
+#include "serverlog_rules.h"
 #include "system_rules.h"
 #include "search_dev.h"
 
@@ -453,6 +454,8 @@ struct CPBatch {
     uint2* skips;             // saturated ranges [x, y) of sorted records handed to k_cp_skipfill (null: no skipping)
     uint32_t* skip_count;     // zeroed by the host before round 0, by k_cp_relist before the next round
     uint32_t skip_cap;
+    uint32_t* slog_blk;       // the stat log is on: [n] the position in its value list at which the group fallback's
+                              // replay blocked a request (~0 before: the request's checks in chk[] name it); null: off
 };
 hipError_t launch_cp_prep2(const CPArgs& c, const CPBatch& b, hipStream_t stream);
 hipError_t launch_cp_walk2(const CPArgs& c, const CPBatch& b, const BatchArgs& sg, hipStream_t stream, hipStream_t aux,
@@ -588,6 +591,8 @@ struct ConcArgs {
     uint8_t* alive;           // per request: an acquire of this batch whose token is live
     int* err;
     int64_t* last_ts;
+    int32_t* slog_rel;        // the stat log is on: [n] the acquireCount of the token a RELEASE_OK gave back (a release
+                              // request carries neither the count nor the flowId); null: off, no store
 };
 
 hipError_t launch_conc_batch(ConcArgs& c, uint64_t* b_buf, uint32_t* hist, hipStream_t stream);
@@ -875,6 +880,52 @@ hipError_t launch_blog_add(const LArgs& L, const BlogArgs& b, hipStream_t stream
 hipError_t launch_blog_take(const BlogArgs& b, int64_t limit, int emit, sg_block_row* rows, sg_block_row* keep,
                             unsigned long long* count, unsigned long long* n_keep, hipStream_t stream);
 hipError_t launch_blog_put(const BlogArgs& b, const sg_block_row* keep, const unsigned long long* n_keep,
+                           hipStream_t stream);
+
+// ---- token server stat log (serverlog.hip): sentinel-server.log's per-second rollup of the flow token batches ----
+// One slot per (second, family, flowId, value) holding that family's counters side by side (serverlog_rules.h names
+// them): a blocked prioritized request adds to three of one slot's counters, so a run of one flowId in one second is one
+// carried key. tag as BlogSlot's: 0 empty, kSlogBusy claimed, else the key's hash with bit 63 set, published with
+// release order after the key words (serverlog.hip slog_wave_insert: the lanes of a wave insert side by side).
+constexpr uint64_t kSlogBusy = 1;
+struct alignas(16) SlogSlot {
+    uint64_t tag;
+    int64_t ts;               // the second: t - t % 1000
+    int64_t flow_id;          // the rule's flowId, not its index: rows outlive a reload that renumbers the rules
+    uint64_t value;           // kSlogParam: the blocking value's id, else 0
+    uint32_t family, pad;     // kSlogFlow / kSlogParam / kSlogConc
+    int64_t c[kSlogCtrs];     // 64-bit integer adds: the order of arrival does not show
+    uint64_t pad2;
+};
+static_assert(sizeof(SlogSlot) == 96, "SlogSlot layout");
+struct SlogArgs {
+    SlogSlot* tab;
+    uint64_t mask;            // slots - 1
+    unsigned long long* lost; // [2] decisions and Σ acquireCount that found no slot
+    const int64_t* fid;       // [K] flowId of each flow rule
+    int rls;                  // 1: the batch is sg_rls_should_rate_limit's (SimpleClusterFlowChecker logs passes, no
+                              // waiting / occupied rows)
+    uint64_t n_req;           // a node shard's slice: the node batch's request count (its records carry node request
+                              // indices, BatchArgs::n is the slice's length); 0: BatchArgs::n
+    const int64_t* cpfid;     // [cluster param rules] flowId of each
+    const uint32_t* drop;     // compact sorted records (BatchArgs::rec4): the rejected requests' digit total — they
+                              // have no sorted copy, the words past n - *drop are stale; else null
+};
+// The logged decisions of the decided flow batch a (after launch_skip_apply; nothing when *a.err != 0) added to the
+// table, in sorted-record order on all three record layouts.
+hipError_t launch_slog_add_flow(const BatchArgs& a, const SlogArgs& s, hipStream_t stream);
+// The same for the decided concurrent token batch c (after k_conc_walk; c.slog_rel set): ConcArgs::rec_sorted groups
+// the acquires and releases by rule, in arrival order.
+hipError_t launch_slog_add_conc(const ConcArgs& c, const SlogArgs& s, hipStream_t stream);
+// The same for the decided cluster param batch (after its last round or the group fallback; b.slog_blk set), in
+// request order: param|block keys carry the blocking value and rarely form runs.
+hipError_t launch_slog_add_param(const CPArgs& c, const CPBatch& b, const SlogArgs& s, hipStream_t stream);
+// The slots of the complete seconds (ts + 1000 <= limit): their non-zero counters counted into *count (emit 0: the
+// rows the fetch will hand out), or the slots moved to rows[] and the others to keep[] (*count, *n_keep slots) — the
+// caller clears the table and puts keep[] back (launch_slog_put).
+hipError_t launch_slog_take(const SlogArgs& s, int64_t limit, int emit, SlogSlot* rows, SlogSlot* keep,
+                            unsigned long long* count, unsigned long long* n_keep, hipStream_t stream);
+hipError_t launch_slog_put(const SlogArgs& s, const SlogSlot* keep, const unsigned long long* n_keep,
                            hipStream_t stream);
 
 // SystemSlot (local.hip): the clear proof over the time-ordered batch before it is decided (k_sys_scan: verdict in

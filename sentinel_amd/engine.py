@@ -45,7 +45,9 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_node_local_merge_rows", "sg_local_load_authority_rules", "sg_node_local_load_authority_rules",
            "sg_local_load_system_rules", "sg_local_set_system_status", "sg_local_read_entry_node",
            "sg_local_system_last_path", "sg_local_system_first_unproven",
-           "sg_local_block_log_enable", "sg_local_block_log"]
+           "sg_local_block_log_enable", "sg_local_block_log", "sg_server_log_enable", "sg_server_log",
+           "sg_node_server_log_enable", "sg_node_server_log", "sg_node_local_block_log_enable",
+           "sg_node_local_block_log"]
 
 _lib = None
 
@@ -179,6 +181,12 @@ def load_library():
         "sg_local_set_system_status": (C.c_int, [vp, C.c_double, C.c_double]),
         "sg_local_block_log_enable": (C.c_int, [vp, C.c_int32]),
         "sg_local_block_log": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "sg_server_log_enable": (C.c_int, [vp, C.c_int32]),
+        "sg_server_log": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "sg_node_server_log_enable": (C.c_int, [vp, C.c_int32]),
+        "sg_node_server_log": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "sg_node_local_block_log_enable": (C.c_int, [vp, C.c_int32]),
+        "sg_node_local_block_log": (C.c_int, [vp, i64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "sg_local_read_entry_node": (C.c_int, [vp, vp, C.POINTER(C.c_int64)]),
         "sg_local_system_last_path": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "sg_local_system_first_unproven": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
@@ -424,6 +432,35 @@ class NodeEngine:
         out = np.zeros(max(1, n.value), abi.METRIC_NODE_DTYPE)
         self._check(self._L.sg_node_local_metrics(self.h, now_ms, abi.ptr(out), n.value, C.byref(n)))
         return out[:n.value]
+
+    def _log_fetch(self, fn, dtype, now_ms):
+        n, le, lc = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = fn(self.h, now_ms, None, 0, C.byref(n), C.byref(le), C.byref(lc))
+        if rc == 0:  # no complete row: this call was the fetch, and it reported and cleared the lost totals
+            return np.zeros(0, dtype), le.value, lc.value
+        if rc != abi.SG_E_CAPACITY:
+            self._check(rc)
+        out = np.zeros(max(1, n.value), dtype)
+        self._check(fn(self.h, now_ms, abi.ptr(out), len(out), C.byref(n), C.byref(le), C.byref(lc)))
+        return out[:n.value], le.value, lc.value
+
+    def server_log_enable(self, capacity_log2=16):
+        """sg_node_server_log_enable: the token server's stat log on the front and every shard."""
+        self._check(self._L.sg_node_server_log_enable(self.h, capacity_log2))
+
+    def server_log(self, now_ms):
+        """sg_node_server_log: (rows, lost_events, lost_count) — the node's sentinel-server.log rows
+        (abi.SERVER_ROW_DTYPE, sorted, equal keys of the front and the shards summed) of every complete second."""
+        return self._log_fetch(self._L.sg_node_server_log, abi.SERVER_ROW_DTYPE, now_ms)
+
+    def block_log_enable(self, capacity_log2=16):
+        """sg_node_local_block_log_enable: LogSlot's rollup on every shard."""
+        self._check(self._L.sg_node_local_block_log_enable(self.h, capacity_log2))
+
+    def block_log(self, now_ms):
+        """sg_node_local_block_log: (rows, lost_events, lost_count) — the shards' sentinel-block.log rows
+        (abi.BLOCK_ROW_DTYPE) of every complete second, in one order."""
+        return self._log_fetch(self._L.sg_node_local_block_log, abi.BLOCK_ROW_DTYPE, now_ms)
 
     def local_metrics_device(self, now_ms, out) -> int:
         """sg_node_local_metrics_device into `out` (a device tensor on devices[0], int64 [cap, 8]); returns the row
@@ -1009,6 +1046,26 @@ class FlowEngine:
         out = np.zeros(max(1, n.value), abi.BLOCK_ROW_DTYPE)
         self._check(self._L.sg_local_block_log(self.h, now_ms, abi.ptr(out), len(out), C.byref(n), C.byref(le),
                                                C.byref(lc)))
+        return out[:n.value], le.value, lc.value
+
+    def server_log_enable(self, capacity_log2=16):
+        """sg_server_log_enable: the token server's per-second stat log (sentinel-server.log), kept on the device from
+        now on in a table of 2^capacity_log2 slots."""
+        self._check(self._L.sg_server_log_enable(self.h, capacity_log2))
+
+    def server_log(self, now_ms):
+        """sg_server_log: (rows, lost_events, lost_count) — the sentinel-server.log rows (abi.SERVER_ROW_DTYPE, sorted)
+        of every second complete at now_ms, removed from the device table, and the decisions / their summed
+        acquireCount that found no free slot since the last call."""
+        n, le, lc = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self._L.sg_server_log(self.h, now_ms, None, 0, C.byref(n), C.byref(le), C.byref(lc))
+        if rc == 0:  # no complete row: this call was the fetch, and it reported and cleared the lost totals
+            return np.zeros(0, abi.SERVER_ROW_DTYPE), le.value, lc.value
+        if rc != abi.SG_E_CAPACITY:
+            self._check(rc)
+        out = np.zeros(max(1, n.value), abi.SERVER_ROW_DTYPE)
+        self._check(self._L.sg_server_log(self.h, now_ms, abi.ptr(out), len(out), C.byref(n), C.byref(le),
+                                          C.byref(lc)))
         return out[:n.value], le.value, lc.value
 
     def local_metrics_raw(self, now_ms) -> np.ndarray:

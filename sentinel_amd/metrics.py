@@ -329,3 +329,26 @@ def block_log_lines(rows, resource_names, origin_names, value_str=str, label_str
                    f"{BLOCK_EXCEPTION_NAMES[int(r['status'])]},"
                    f"{block_rule_limit_app(r, origin_names, value_str, label_str)},{origin}|{int(r['count'])},0\n")
     return out
+
+
+SERVER_LOG_KEYS = {
+    abi.SLOG_FLOW_WAITING: "flow|waiting|{id}", abi.SLOG_FLOW_BLOCK: "flow|block|{id}",
+    abi.SLOG_FLOW_BLOCK_REQUEST: "flow|block_request|{id}", abi.SLOG_FLOW_OCCUPIED_BLOCK: "flow|occupied_block|{id}",
+    abi.SLOG_FLOW_PASS: "flow|pass|{id}", abi.SLOG_FLOW_PASS_REQUEST: "flow|pass_request|{id}",
+    abi.SLOG_PARAM_PASS: "param|pass|{id}", abi.SLOG_PARAM_BLOCK: "param|block|{id}|{value}",
+    abi.SLOG_CONC_PASS: "concurrent|pass|{id}", abi.SLOG_CONC_BLOCK: "concurrent|block|{id}",
+    abi.SLOG_CONC_RELEASE: "concurrent|release|{id}",
+}
+
+
+def server_log_lines(rows, value_str=str, tz=datetime.timezone.utc):
+    """The sentinel-server.log lines of sg_server_log rows, one per row in row order (StatLogWriteTask.run,
+    StatLogController.java:130-152, with ClusterServerStatLogUtil's logger: the key is the single string the checker
+    built, the COUNT_SUM entry's stat type is 1 and nothing adds to the value sum):
+    `yyyy-MM-dd HH:mm:ss|1|flow|block|123|7,0`. value_str turns the value id of a param|block row into the
+    String.valueOf of the blocking value (sg_vdict_lookup, for instance)."""
+    out = []
+    for r in rows:
+        key = SERVER_LOG_KEYS[int(r["event"])].format(id=int(r["flow_id"]), value=value_str(int(r["value"])))
+        out.append(f"{_date(int(r['timestamp']), tz)}|1|{key}|{int(r['count'])},0\n")
+    return out
