@@ -84,6 +84,11 @@ class sg_batch_stats(C.Structure):
                 ("touched_keys", C.c_uint64), ("long_segments", C.c_uint64), ("skipped_ranges", C.c_uint64)]
 
 
+class sg_sweep_stats(C.Structure):
+    _fields_ = [("values_removed", C.c_uint64), ("claims_dropped", C.c_uint64), ("threads_removed", C.c_uint64),
+                ("values_kept", C.c_uint64)]
+
+
 # numpy views of the request / result records (same layout as the C structs)
 REQ_DTYPE = np.dtype([("ts_ms", "<i8"), ("key", "<u4"), ("acquire", "<i4")], align=True)
 # sg_rls_request / sg_rls_status (Envoy RLS entry point)

@@ -2403,6 +2403,77 @@ int sg_param_table_used(sg_handle* h, uint32_t rule, uint64_t* used, uint64_t* l
     return SG_OK;
 }
 
+namespace {
+
+// The time order of a sweep at now_ms against the last timestamps `ts` (device words; null: that path is not set up)
+// of the paths that read the swept tables. check: SG_E_TIME when one of them lies after now_ms; raise: each becomes
+// max(itself, now_ms), so a later batch that starts before now_ms is refused as any out-of-order batch is. The raise
+// comes before the swap: swept tables under a timestamp left behind could answer an older batch differently, while
+// a raised timestamp over unswept tables (a copy that fails midway: SG_E_DEVICE) only refuses more.
+int sweep_time_check(sg_handle* h, int64_t now_ms, int64_t* const* ts, int n) {
+    if (now_ms < 0) return fail(h, SG_E_TIME, "now_ms must be >= 0");
+    for (int k = 0; k < n; ++k) {
+        if (!ts[k]) continue;
+        int64_t last = -1;
+        HIP_TRY(h, hipMemcpy(&last, ts[k], sizeof(last), hipMemcpyDeviceToHost));
+        if (now_ms < last) return fail(h, SG_E_TIME, "now_ms lies before a batch that read the swept tables");
+    }
+    return SG_OK;
+}
+
+int sweep_time_raise(sg_handle* h, int64_t now_ms, int64_t* const* ts, int n) {
+    for (int k = 0; k < n; ++k) {
+        if (!ts[k]) continue;
+        int64_t last = -1;
+        HIP_TRY(h, hipMemcpy(&last, ts[k], sizeof(last), hipMemcpyDeviceToHost));
+        if (last < now_ms) HIP_TRY(h, hipMemcpy(ts[k], &now_ms, sizeof(now_ms), hipMemcpyHostToDevice));
+    }
+    return SG_OK;
+}
+
+void sweep_stats_out(sg_sweep_stats* out, const unsigned long long* cnt) {
+    if (!out) return;
+    out->values_removed = cnt[0];
+    out->claims_dropped = cnt[1];
+    out->threads_removed = cnt[2];
+    out->values_kept = cnt[3];
+}
+
+}  // namespace
+
+// The other direction of sg_param_resize, by its mechanism: fresh tables of the same size beside the ones in force,
+// filled by grow.hip's sweep kernels with every entry that is not idle at now_ms (table_sweep.h), and swapped in at the
+// end. The thread counts of the ParamFlowSlot chain (when loaded) are rehashed the same way, entries at 0 left out.
+int sg_param_sweep(sg_handle* h, int64_t now_ms, sg_sweep_stats* out) {
+    if (!h) return SG_E_INVAL;
+    if (h->ptab.empty()) return fail(h, SG_E_INVAL, "no param rules loaded");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    // sg_param_*, sg_pslot_* and the slot chain (its param lookups go through the same tables once pslot rules are in)
+    int64_t* const ts[3] = {h->d_plast_ts.get(), h->d_ps_last_ts.get(), h->ps_loaded ? h->d_llast_ts.get() : nullptr};
+    int rc = sweep_time_check(h, now_ms, ts, 3);
+    if (rc) return rc;
+    const uint32_t n = (uint32_t)h->ptab.size();
+    const bool threads = h->ps_loaded && h->d_ps_tc;
+    DevBuf<PSlot> d_table;
+    DevBuf<PSThread> d_tc;
+    DevBuf<unsigned long long> d_cnt;
+    if (!d_table.alloc(h->ptotal) || (threads && !d_tc.alloc(h->ps_tc_slots)) || !d_cnt.alloc(4))
+        return fail(h, SG_E_NOMEM, "swept param tables");
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    HIP_TRY(h, hipMemset(d_cnt, 0, sizeof(cnt)));
+    HIP_TRY(h, launch_param_sweep(h->d_prules, n, h->d_phot, h->d_ptable, d_table, h->ptotal, now_ms, d_cnt, 0));
+    if (threads) HIP_TRY(h, launch_tc_sweep(h->d_ps_tc, d_tc, h->ps_tc_slots, d_cnt, 0));
+    HIP_TRY(h, hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipDeviceSynchronize());
+    rc = sweep_time_raise(h, now_ms, ts, 3);
+    if (rc) return rc;  // SG_E_DEVICE only; the tables in force are untouched, some timestamps may be raised
+    h->d_ptable = std::move(d_table);
+    if (threads) h->d_ps_tc = std::move(d_tc);
+    sweep_stats_out(out, cnt);
+    return SG_OK;
+}
+
 // --------------------------------------------------------------------- pace controller
 // FlowRuleUtil.generateRater (core/.../flow/FlowRuleUtil.java:132-145) builds one RateLimiterController per
 // CONTROL_BEHAVIOR_RATE_LIMITER rule; a rebuild starts every latestPassedTime at -1
@@ -3135,6 +3206,40 @@ int sg_cparam_table_used(sg_handle* h, uint32_t rule, uint64_t* used, uint64_t* 
     if (used) *used = got[0];
     if (live) *live = got[1];
     if (capacity) *capacity = R.table_mask + 1;
+    return SG_OK;
+}
+
+// sg_cparam_resize at the size in force, rings with no bucket live at now_ms left out (grow.hip k_cpsweep_claim, then
+// the move pass of the growth). The rules on the device stay: bases and masks do not change.
+int sg_cparam_sweep(sg_handle* h, int64_t now_ms, sg_sweep_stats* out) {
+    if (!h) return SG_E_INVAL;
+    if (h->cptab.empty()) return fail(h, SG_E_INVAL, "no cluster param rules loaded");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    // sg_cparam_* and the embedded token server of the slot chain stamp the same word (pslot_embed, LArgs::ps)
+    int64_t* const ts[1] = {h->d_cplast_ts.get()};
+    int rc = sweep_time_check(h, now_ms, ts, 1);
+    if (rc) return rc;
+    DevBuf<uint64_t> d_keys;
+    DevBuf<CPBucket> d_ring;
+    DevBuf<uint32_t> d_map;
+    DevBuf<unsigned long long> d_cnt;
+    if (!d_keys.alloc(h->cptotal) || !d_ring.alloc((size_t)h->cptotal * h->cpstride) || !d_map.alloc(h->cptotal) ||
+        !d_cnt.alloc(4))
+        return fail(h, SG_E_NOMEM, "swept cluster param tables");
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    HIP_TRY(h, hipMemset(d_cnt, 0, sizeof(cnt)));
+    CPArgs nc = cp_args(h, nullptr, 0, nullptr, 0, nullptr);
+    nc.keys = d_keys;
+    nc.ring = d_ring;
+    HIP_TRY(h, launch_cp_sweep(nc, h->d_cpkeys, h->d_cpring, now_ms, d_map, d_cnt, 0));
+    HIP_TRY(h, hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipDeviceSynchronize());
+    rc = sweep_time_raise(h, now_ms, ts, 1);
+    if (rc) return rc;  // SG_E_DEVICE only; the tables in force are untouched, some timestamps may be raised
+    h->d_cpkeys = std::move(d_keys);
+    h->d_cpring = std::move(d_ring);
+    sweep_stats_out(out, cnt);
     return SG_OK;
 }
 
@@ -7379,6 +7484,58 @@ int sg_node_cparam_resize(sg_node* nd, int32_t capacity_log2) {
     }
     (void)hipSetDevice(nd->devices[0]);
     return rc;
+}
+
+namespace {
+void sweep_stats_add(sg_sweep_stats& sum, const sg_sweep_stats& s) {
+    sum.values_removed += s.values_removed;
+    sum.claims_dropped += s.claims_dropped;
+    sum.threads_removed += s.threads_removed;
+    sum.values_kept += s.values_kept;
+}
+}  // namespace
+
+// As sg_node_param_resize: the front first (it refuses what any shard would, before one has changed), then the shards
+// in order; a swept entry is invisible, so a shard that fails leaves nothing to undo — call again to complete. The
+// node's own time order comes first: a node batch validates against l_last_ts before any shard sees it.
+int sg_node_param_sweep(sg_node* nd, int64_t now_ms, sg_sweep_stats* out) {
+    if (!nd) return SG_E_INVAL;
+    if (!nd->l_ps_loaded) return nfail(nd, SG_E_INVAL, "sg_node_pslot_load_rules first");
+    if (now_ms < 0 || now_ms < nd->l_last_ts) return nfail(nd, SG_E_TIME, "now_ms lies before the node's earlier local batches");
+    node_drain(nd);
+    sg_sweep_stats sum{}, one{};
+    int rc = node_child(nd, nd->front, sg_param_sweep(nd->front, now_ms, nullptr));
+    // a swept handle refuses batches before now_ms: from the first one on, so does the node, also when a later shard fails
+    if (!rc) nd->l_last_ts = std::max(nd->l_last_ts, now_ms);
+    for (size_t g = 0; !rc && g < nd->shards.size(); ++g) {
+        rc = node_child(nd, nd->shards[g], sg_param_sweep(nd->shards[g], now_ms, &one));
+        if (!rc) sweep_stats_add(sum, one);
+    }
+    (void)hipSetDevice(nd->devices[0]);
+    if (rc) return rc;
+    if (out) *out = sum;
+    return SG_OK;
+}
+
+int sg_node_cparam_sweep(sg_node* nd, int64_t now_ms, sg_sweep_stats* out) {
+    if (!nd) return SG_E_INVAL;
+    if (nd->cp_rules.empty()) return nfail(nd, SG_E_INVAL, "no cluster param rules loaded");
+    if (now_ms < 0 || now_ms < nd->cp_last_ts) return nfail(nd, SG_E_TIME, "now_ms lies before the node's earlier param batches");
+    node_drain(nd);
+    sg_sweep_stats sum{}, one{};
+    int rc = SG_OK;
+    for (size_t g = 0; !rc && g < nd->shards.size(); ++g) {
+        sg_handle* h = nd->shards[g];
+        if (h->cptab.empty()) continue;  // owns no flowId
+        rc = node_child(nd, h, sg_cparam_sweep(h, now_ms, &one));
+        if (rc) break;
+        sweep_stats_add(sum, one);
+        nd->cp_last_ts = std::max(nd->cp_last_ts, now_ms);  // with the first swept shard, also when a later one fails
+    }
+    (void)hipSetDevice(nd->devices[0]);
+    if (rc) return rc;
+    if (out) *out = sum;
+    return SG_OK;
 }
 
 int sg_node_cparam_table_used(sg_node* nd, uint32_t rule, uint64_t* used, uint64_t* live, uint64_t* capacity) {

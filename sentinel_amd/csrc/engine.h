@@ -500,6 +500,16 @@ hipError_t launch_cp_grow(const CPArgs& nc, const CPRule* orules, uint64_t oper,
 // out2[0] = slots of keys[base .. base + n) that hold a value, out2[1] = those with a written bucket among the first S
 hipError_t launch_cp_used(const uint64_t* keys, const CPBucket* ring, int stride, int S, uint64_t base, uint64_t n,
                           unsigned long long* out2, hipStream_t stream);
+// grow.hip, the sweeps: the same rehash into cleared tables of the same size, entries idle at `now` (table_sweep.h)
+// left out. cnt4 += {idle entries given back, claimed-never-counted entries dropped, thread counts at 0, entries kept}.
+//   param   `table` [total] from `old` under the rules in force (rules, hot)
+//   cparam  nc.keys / nc.ring (nc.rules, nc.per, nc.total_slots: those in force) from okeys / oring; map: [total] words
+//   tc      ParameterMetric's thread counts, `tc` [slots] from `old`, entries above 0 only
+hipError_t launch_param_sweep(const PRule* rules, uint32_t n_rules, const sg_param_hot_item* hot, const PSlot* old,
+                              PSlot* table, uint64_t total, int64_t now, unsigned long long* cnt4, hipStream_t stream);
+hipError_t launch_cp_sweep(const CPArgs& nc, const uint64_t* okeys, const CPBucket* oring, int64_t now, uint32_t* map,
+                           unsigned long long* cnt4, hipStream_t stream);
+hipError_t launch_tc_sweep(const PSThread* old, PSThread* tc, uint64_t slots, unsigned long long* cnt4, hipStream_t stream);
 hipError_t launch_cp_read(const CPArgs& c, uint32_t rule, uint64_t value, int64_t now, int64_t* out_dev, hipStream_t stream);
 struct CPTop {                // a (rule, value) window sum for ClusterParamMetric.getTopValues
     uint64_t value;

@@ -215,7 +215,7 @@ __device__ inline void ps_threads(const PSArgs& s, uint32_t res, uint32_t arg_be
                 if (x >= 0) s.tc[x].count += 1;
             } else {
                 const int64_t x = ps_tc(s, res, (int32_t)idx, v, false);
-                if (x >= 0) s.tc[x].count = s.tc[x].count > 0 ? s.tc[x].count - 1 : 0;  // <= 0: removed (reads 0)
+                if (x >= 0) s.tc[x].count = s.tc[x].count > 0 ? s.tc[x].count - 1 : 0;  // <= 0: reads 0; the entry stays until sg_param_sweep
                 else ps_tc(s, res, (int32_t)idx, v, true);                             // putIfAbsent(0)
             }
         }

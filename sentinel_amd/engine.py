@@ -213,6 +213,10 @@ def load_library():
         "sg_cparam_resize": (C.c_int, [vp, C.c_int32]),
         "sg_cparam_table_used": (C.c_int, [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "sg_vdict_grow": (C.c_int, [vp, C.c_int32, u64]),
+        "sg_param_sweep": (C.c_int, [vp, C.c_int64, C.POINTER(abi.sg_sweep_stats)]),
+        "sg_cparam_sweep": (C.c_int, [vp, C.c_int64, C.POINTER(abi.sg_sweep_stats)]),
+        "sg_node_param_sweep": (C.c_int, [vp, C.c_int64, C.POINTER(abi.sg_sweep_stats)]),
+        "sg_node_cparam_sweep": (C.c_int, [vp, C.c_int64, C.POINTER(abi.sg_sweep_stats)]),
         "sg_node_param_resize": (C.c_int, [vp, vp, u32]),
         "sg_node_param_table_used": (C.c_int, [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "sg_node_cparam_resize": (C.c_int, [vp, C.c_int32]),
@@ -582,6 +586,19 @@ class NodeEngine:
         """(used, live, capacity) of the rule's value table on its owner."""
         return _table_used(self, self._L.sg_node_cparam_table_used, rule)
 
+    # ---- idle values swept out of the value tables (sg_node_*_sweep), stats summed over the shards
+    def param_sweep(self, now_ms: int):
+        return _sweep(self, self._L.sg_node_param_sweep, now_ms)
+
+    def cparam_sweep(self, now_ms: int):
+        return _sweep(self, self._L.sg_node_cparam_sweep, now_ms)
+
+
+def _sweep(eng, fn, now_ms):
+    st = abi.sg_sweep_stats()
+    eng._check(fn(eng.h, now_ms, C.byref(st)))
+    return {name: int(getattr(st, name)) for name, _ in abi.sg_sweep_stats._fields_}
+
 
 def _table_used(eng, fn, rule):
     used, live, cap = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -892,6 +909,12 @@ class FlowEngine:
         """(used, live, capacity) of the rule's value table: slots taken (what SG_E_CAPACITY goes by), those a walker
         has counted, and 2^capacity_log2."""
         return _table_used(self, self._L.sg_param_table_used, rule)
+
+    def param_sweep(self, now_ms: int):
+        """Gives back every param value (and thread count) that no request at or after now_ms can tell from absence:
+        refilled token buckets, counts at 0, claims never counted. now_ms must not lie before the last param, pslot or
+        slot-chain batch, and later batches must not start before it. Returns sg_sweep_stats as a dict."""
+        return _sweep(self, self._L.sg_param_sweep, now_ms)
 
     # ---- pace controller (RateLimiterController.canPass per CONTROL_BEHAVIOR_RATE_LIMITER FlowRule)
     def pace_load_rules(self, rules: np.ndarray):
@@ -1257,3 +1280,8 @@ class FlowEngine:
     def cparam_table_used(self, rule):
         """(used, live, capacity) of the rule's value table; live = values with at least one written bucket."""
         return _table_used(self, self._L.sg_cparam_table_used, rule)
+
+    def cparam_sweep(self, now_ms: int):
+        """Gives back every cluster param value whose ring holds no bucket live at now_ms (sg_cparam_sweep), under the
+        time order of param_sweep against the cluster param batches. Returns sg_sweep_stats as a dict."""
+        return _sweep(self, self._L.sg_cparam_sweep, now_ms)
