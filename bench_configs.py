@@ -16,6 +16,8 @@ bench.py (which measures the headline C3 workload).
   --workload slot  the whole slot chain at C5 size with 10 % of the resources carrying an origin-limitApp rule, a
                  WarmUp rule or a ParamFlowRule (the cx walker's share); every batch checked against the oracle.
   --workload node  the C3 workload through the node handle (G same-device shards, --shards), pipelined.
+  --workload gateway  GatewayFlowSlot: --resources routes with 3 item rules (client IP, EXACT header, CONTAINS URL
+                  parameter) and an item-less rule each; times sg_gateway_parse_batch alone and parse + the slot chain.
   --workload pace  1M resources, each a FlowRule with CONTROL_BEHAVIOR_RATE_LIMITER (RateLimiterController,
                  count U{1..64}, maxQueueingTimeMs 500), 16M canPass calls per 1000 ms batch, Zipf(1.0),
                  acquire 1 (10 % U{2..4}).
@@ -662,9 +664,164 @@ def node(args, dev):
             "data": "synthetic (GPU-generated, seeded): bench.py's C3 batches"}
 
 
+def gateway(args, dev):
+    """GatewayFlowSlot from the adapter's side: --resources routes, each with 3 item rules (client IP with no pattern, a
+    header with an EXACT pattern, a URL parameter with a CONTAINS pattern) and one item-less rule; --events requests per
+    1000 ms batch with Zipf(1.0) routes and Zipf(1.1) client IPs. Timed: sg_gateway_parse_batch alone, and parse +
+    sg_slot_decide_batch over the arg spans the parser wrote into the ext records."""
+    K, n = args.resources, args.events
+    n_clients = min(1 << 20, max(1024, n // 4))
+    L = (12, 8, 12)                   # bytes of the client IP, the header value and the URL parameter
+    stride = sum(L)
+    g = np.zeros(4 * K, abi.GATEWAY_RULE_DTYPE)
+    g["resource"] = np.repeat(np.arange(K, dtype=np.uint32), 4)
+    g["grade"], g["interval_sec"], g["max_queueing_timeout_ms"], g["pattern_null"] = 1, 1, 500, 1
+    g["capacity_log2"] = 10
+    res_cdf, res_perm = zipf_cdf(K, 1.0, 31)
+    # the client-IP rule's table holds every client the route sees: sized from the route's share of the traffic
+    share = np.diff(res_cdf, prepend=0.0)
+    seen = np.minimum(n_clients, share * n * (args.warmup + args.steps) * 2.0)
+    cap = np.zeros(K, np.int32)
+    cap[res_perm] = np.maximum(10, np.ceil(np.log2(np.maximum(seen, 1.0))).astype(np.int32) + 1)
+    pat = b"tier-vipid=7"
+    ip, hdr, url, dflt = g[0::4], g[1::4], g[2::4], g[3::4]
+    ip["has_item"], ip["parse_strategy"], ip["count"] = 1, abi.GW_PARSE_CLIENT_IP, 5
+    ip["capacity_log2"] = cap
+    hdr["has_item"], hdr["parse_strategy"], hdr["match_strategy"], hdr["count"] = 1, abi.GW_PARSE_HEADER, abi.GW_MATCH_EXACT, 50
+    hdr["pattern_null"], hdr["pattern_off"], hdr["pattern_len"] = 0, 0, 8
+    url["has_item"], url["parse_strategy"], url["match_strategy"], url["count"] = 1, abi.GW_PARSE_URL_PARAM, abi.GW_MATCH_CONTAINS, 20
+    url["pattern_null"], url["pattern_off"], url["pattern_len"] = 0, 8, 4
+    dflt["count"] = 200
+    eng = FlowEngine(device=0, max_batch=2 * n)
+    eng.vdict_init(max(12, int(np.ceil(np.log2(n_clients + 4096))) + 1), max(64 << 20, n_clients * 24), 8 * n)
+    eng.local_load_rules(_gateway_local_rules(K), 2, 1000, 500)
+    eng.gateway_load_rules(g, pat, K)
+    ip_cdf, ip_perm = zipf_cdf(n_clients, 1.1, 32)
+    res_cdf_t, res_perm_t = torch.from_numpy(res_cdf).to(dev), torch.from_numpy(res_perm).to(dev)
+    ip_cdf_t, ip_perm_t = torch.from_numpy(ip_cdf).to(dev), torch.from_numpy(ip_perm).to(dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(33)
+    hexd = torch.tensor(list(b"0123456789abcdef"), dtype=torch.uint8, device=dev)
+
+    def text(prefix, x, digits):      # prefix + `digits` hex digits of x, [n, len(prefix) + digits] bytes
+        cols = [torch.full((n,), c, dtype=torch.uint8, device=dev) for c in prefix]
+        cols += [hexd[(x >> (4 * (digits - 1 - j))) & 15] for j in range(digits)]
+        return torch.stack(cols, dim=1)
+
+    def entries(b):                   # (route, [n, stride] string bytes, sorted arrival ms)
+        route = gpu_keys(res_cdf_t, res_perm_t, n, gen)
+        client = gpu_keys(ip_cdf_t, ip_perm_t, n, gen)
+        u = torch.rand(n, generator=gen, device=dev)
+        tier = torch.where(u < 0.2, torch.zeros_like(route), 1 + (u * 64).long() % 5)
+        v = torch.randint(0, 16, (n,), generator=gen, device=dev)
+        hdr_b = text(b"tier-", tier + 0xAAA, 3)
+        hdr_b[tier == 0] = torch.tensor(list(b"tier-vip"), dtype=torch.uint8, device=dev)
+        rows = torch.cat([text(b"10.c", client, 8), hdr_b, text(b"a=1&id=", (((v & 3) + 5) << 16) | v, 5)], dim=1)
+        ts = T0 + b * 1000 + torch.sort(torch.randint(0, 1000, (n,), generator=gen, device=dev)).values
+        return route, rows.contiguous(), ts
+
+    def records(route, m):            # sg_gateway_req[m]: request i owns items [3i, 3i + 3)
+        req = torch.zeros((m, 4), dtype=torch.int32, device=dev)
+        req[:, 0], req[:, 2], req[:, 3] = route.int(), torch.arange(m, device=dev, dtype=torch.int32) * 3, 3
+        return req.reshape(-1).contiguous()
+
+    N2 = 2 * n                        # a step of the chain: the exits of the last step's passed entries, then n entries
+    off = torch.arange(N2, device=dev, dtype=torch.int64) * stride
+    items = torch.zeros((N2, 3, 4), dtype=torch.int32, device=dev)
+    items[:, 0, 0], items[:, 1, 0], items[:, 2, 0] = off.int(), (off + L[0]).int(), (off + L[0] + L[1]).int()
+    items[:, 0, 1], items[:, 1, 1], items[:, 2, 1] = L
+    items = items.reshape(-1).contiguous()
+    batches = [entries(b) for b in range(args.warmup + args.steps)]
+    reqs = [records(route, n) for route, _, _ in batches]
+    a_t = torch.empty(4 * N2 * 16, dtype=torch.uint8, device=dev)
+    v_t = torch.empty(4 * N2 * 8, dtype=torch.uint8, device=dev)
+    ext = torch.zeros(N2 * 16, dtype=torch.uint8, device=dev)
+    out = torch.empty(N2 * 8, dtype=torch.uint8, device=dev)
+    s = torch.cuda.current_stream(dev).cuda_stream
+
+    def parse(req, rows, m):
+        return eng.gateway_parse_device(req.data_ptr(), m, items.data_ptr(), 3 * m, rows.data_ptr(), stride * m,
+                                        a_t.data_ptr(), 4 * N2, v_t.data_ptr(), 4 * N2, ext.data_ptr(), 0, s)
+
+    # the parse step alone over every batch first: it fills the dictionary as the timed steps then find it (steady state:
+    # known clients; the first sight of a client is the dedupe / commit passes' work)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for b in range(args.warmup + args.steps):
+        n_args, n_values = parse(reqs[b], batches[b][1], n)
+    torch.cuda.synchronize()
+    first_ms = (time.perf_counter() - t0) * 1000.0 / (args.warmup + args.steps)
+    el_parse = timed(lambda b: parse(reqs[b], batches[b][1], n), args.warmup, args.steps)
+    strings, _ = eng.vdict_size()
+
+    # parse + the slot chain: every step parses and decides the exits of the last step's passed entries (an exit carries
+    # its entry's request: ParamFlowStatisticExitCallback lowers the thread counts of the same args) and nc new entries.
+    # The chain's thread-count table has 2^20 slots for every (route, paramIdx, value) in flight, so a step takes at
+    # most 2^18 entries, and the counts that returned to 0 are swept between the steps (outside the timed region).
+    nc = min(n, 1 << 18)
+    chain = {"ms": None, "requests_per_step": None, "error": None}
+    try:
+        el, served, prev = 0.0, 0, None
+        for b in range(args.warmup + args.steps):
+            route, rows, ts = batches[b][0][:nc], batches[b][1][:nc], batches[b][2][:nc]
+            entry_route, entry_rows = route, rows
+            x = 0 if prev is None else len(prev[0])
+            if x:
+                eng.param_sweep(T0 + b * 1000)
+                route, rows = torch.cat([prev[0], route]), torch.cat([prev[1], rows]).contiguous()
+            m = x + nc
+            ev = torch.zeros((m, 4), dtype=torch.int64, device=dev)   # sg_local_event: ts, create_ts, resource | count, kind | origin
+            ev[:, 2] = route | (1 << 32)
+            ev[x:, 0] = ts
+            if x:
+                ev[:x, 0], ev[:x, 1], ev[:x, 3] = T0 + b * 1000, prev[2], abi.LOCAL_EXIT
+            req = records(route, m)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            na, nv = parse(req, rows, m)
+            eng.slot_decide_device(ev.data_ptr(), ext.data_ptr(), m, a_t.data_ptr(), na, v_t.data_ptr(), nv,
+                                   out.data_ptr(), s)
+            torch.cuda.synchronize()
+            if b >= args.warmup:
+                el += time.perf_counter() - t0
+                served += m
+            status = out[: m * 8].view(torch.int32)[0::2][x:]
+            ok = (status == abi.LOCAL_PASS) | (status == abi.LOCAL_PASS_WAIT)
+            prev = (entry_route[ok], entry_rows[ok], ts[ok])
+        chain = {"ms": el * 1000.0 / args.steps, "requests_per_step": served / args.steps, "error": None}
+    except Exception as e:  # the parse figures stand on their own
+        chain["error"] = str(e)
+        el, served = el_parse, n * args.steps
+    b_alg = n * 16 + 3 * n * 16 + stride * n + n_args * 16 + n_values * 8 + n * 16
+    return {"metric": "gateway requests/sec (GatewayParamParser on the device + the whole slot chain)",
+            "workload": f"gateway: {K} routes x (client IP, EXACT header, CONTAINS URL parameter, item-less) rules, "
+                        f"{n} requests per parse batch; chain steps of {nc} entries plus the exits of the passed ones, "
+                        f"Zipf(1.0) routes, "
+                        f"Zipf(1.1) over {n_clients} client IPs",
+            "value": served / el, "el": el, "n": n, "b_alg": b_alg, "touched": strings, "cpu": None,
+            "unit": "requests/s", "dtype": "u8",
+            "extra": {"gateway": {"parse_ms": el_parse * 1000.0 / args.steps, "parse_first_sight_ms": first_ms,
+                                  "parse_requests_per_s": n * args.steps / el_parse,
+                                  "parse_items_per_s": 3 * n * args.steps / el_parse,
+                                  "parse_decide_ms": chain["ms"], "parse_decide_requests_per_step": chain["requests_per_step"],
+                                  "parse_decide_requests_per_s": served / el if chain["ms"] else None,
+                                  "parse_decide_error": chain["error"],
+                                  "algorithmic_bytes": {"requests": n * 16, "items": 3 * n * 16, "strings": stride * n,
+                                                        "args": n_args * 16, "values": n_values * 8, "ext": n * 16},
+                                  "dictionary_strings": strings}},
+            "data": "synthetic (GPU-generated, seeded): fixed-width client IP, header and URL parameter strings"}
+
+
+def _gateway_local_rules(K):
+    r = np.zeros(K, abi.LOCAL_RULE_DTYPE)
+    r["flow_grade"] = abi.FLOW_GRADE_NONE
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["c2", "c4", "c5", "codec", "pace", "cparam", "node", "slot"], default="c2")
+    ap.add_argument("--workload", choices=["c2", "c4", "c5", "codec", "pace", "cparam", "node", "slot", "gateway"],
+                    default="c2")
     ap.add_argument("--shards", type=int, default=0,
                     help="node: shard handles on the one GPU (default 2); cparam: decide through the node handle "
                          "with this many shards (default: one handle)")
@@ -685,7 +842,7 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     r = {"c2": c2, "c4": c4, "c5": c5, "codec": codec, "pace": pace, "cparam": cparam, "node": node,
-         "slot": slot}[args.workload](args, dev)
+         "slot": slot, "gateway": gateway}[args.workload](args, dev)
     ms = r["el"] * 1000.0 / args.steps
     gbs = r["b_alg"] / (ms / 1000.0) / 1e9
     res = {"metric": r["metric"], "value": r["value"], "unit": r.get("unit", "decisions/s"), "n_gpus": 1,

@@ -1332,6 +1332,108 @@ int sg_codec_decode_param(sg_handle* h, const uint8_t* payload, const uint32_t* 
 int sg_codec_encode_param(sg_handle* h, const int32_t* xid, const uint8_t* kind, const sg_result* res, uint64_t n,
                           uint8_t* frames_out, void* stream);
 
+/* ---- GatewayFlowSlot (sentinel-api-gateway-adapter-common): gateway rules and the request parameter parser ----
+ * GatewayFlowSlot.checkGatewayParamFlow (slot/GatewayFlowSlot.java:47-71) is ParamFlowChecker.passCheck over the
+ * ParamFlowRules GatewayRuleManager converted from the gateway rules, on the Object[] GatewayParamParser built for the
+ * request. The check itself is sg_pslot_* / sg_slot_decide_batch; these calls are the two parts in front of it.
+ *
+ * Rules. sg_gateway_rule is a GatewayFlowRule with its GatewayParamFlowItem flattened (has_item = 0: no paramItem).
+ * The resource is the caller's resource index (route id or custom API name, resource_mode says which), the field name
+ * stays with the caller (field_blank = StringUtil.isBlank(fieldName)), the pattern is bytes [pattern_off, + pattern_len)
+ * of one blob (pattern_null = 1: null). capacity_log2 is handed to the converted rule's value table.
+ *   sg_gateway_load_rules  needs sg_vdict_init (else SG_E_INVAL); completes enqueued work; drops what
+ *     GatewayRuleManager.isValidRule drops (rule/GatewayRuleManager.java:117-145), silently; converts as
+ *     applyGatewayRuleInternal (:179-237) per resource in the caller's order: rules with an item get paramIdx 0, 1, 2, …
+ *     and, when the pattern is non-null, the hot item ("$NM", 10,000,000) of GatewayRuleConverter
+ *     .generateNonMatchPassParamItem; every rule without an item gets paramIdx = the number of item rules, and item-less
+ *     rules whose converted rules are equal collapse into the first (the reference keeps them in a HashSet). "$NM" and
+ *     then "$D" are interned as SG_PARAM_TYPE_STRING values (known strings keep their ids). The parser's per-resource
+ *     tables go to the device. A resource >= n_resources or a pattern range outside the blob is SG_E_INVAL; a failed
+ *     load leaves the rules loaded before in force. Rules of one resource with different resource modes are legal.
+ *   sg_gateway_converted  the converted rules sorted by (resource, paramIdx, caller order), their hot items and
+ *     source_out[i] = the index of the gateway rule behind converted rule i. The reference's order within a resource is a
+ *     HashSet's iteration order; this one is fixed. The caller puts them IN FRONT OF its ordinary
+ *     ParamFlowRules (hot_begin of those shifted by *n_hot) and calls sg_pslot_load_rules once: per resource the walkers
+ *     then check the gateway rules first and the ordinary ones after, on the same args — GatewayFlowSlot (order -4000)
+ *     before ParamFlowSlot (-3000). A cap too small: SG_E_CAPACITY with *n_rules / *n_hot set. Null outputs with cap 0
+ *     ask for the counts.
+ *   sg_gateway_param_rule_count  a resource's number of item rules and whether it has an item-less rule (0 / 0 for a
+ *     resource without valid gateway rules or >= n_resources).
+ *   sg_gateway_parse_batch  GatewayParamParser.parseParameterFor (param/GatewayParamParser.java:51-84, :156-174) for n
+ *     requests; every pointer but h, n_args and n_values is a DEVICE pointer. req[i].resource_mode is the adapter's
+ *     predicate (rule.getResourceMode() == resource_mode). Item k of a request — items[item_begin + k] — is what the
+ *     caller's RequestItemParser returned for the resource's item rule with paramIdx k (remote address, Host, header,
+ *     URL parameter or cookie by the rule's parse strategy): bytes [off, off + len) of `bytes`, or SG_GW_ITEM_NULL.
+ *     SG_GW_ITEM_REGEX_MATCH is java.util.regex's verdict for a REGEX rule (Pattern.matcher(value).matches()), also to
+ *     be set when the pattern did not compile (GatewayRegexCache null keeps the value). No item may belong to two
+ *     requests. Per request: a resource without valid gateway rules or >= n_resources gets arg_count 0; an item rule
+ *     whose resource_mode differs from the request's gives arg_count 0 (item-less rules are not asked); otherwise one
+ *     arg per item rule and a last "$D" arg when the resource has an item-less rule. An arg is SG_ARG_NULL (value_count
+ *     0) for a null item or a parse strategy above 4, else SG_ARG_VALUE with one value: the dictionary id of the item's
+ *     string when gw_match keeps it (no or empty pattern; EXACT equal bytes; CONTAINS a byte substring; REGEX the
+ *     verdict bit; PREFIX and every other strategy keep the value, the reference's default branch), else the id of
+ *     "$NM". args_out / values_out are in request order, then arg index; value_begin of every arg is the running value
+ *     count. ext_inout (sg_slot_ext[n]) and pev_inout (sg_pslot_event[n]), where non-null, get arg_begin, arg_count and
+ *     args_null = 0, their other fields are left: the result feeds sg_slot_decide_batch / sg_pslot_decide_batch as it
+ *     is. New strings get ids in order of first appearance (request, then arg). Exits are parsed like entries.
+ *     The call runs on `stream` and returns after it completed. All or nothing, each of these before anything is
+ *     interned: item_count != the resource's item-rule count, an item range or byte range out of bounds, an item of two
+ *     requests, a string of 2^24 bytes or more, `bytes` not 4-byte aligned (SG_E_INVAL); n or the value count above
+ *     max_batch_values, args_cap / values_cap too small (SG_E_CAPACITY, *n_args / *n_values set); the dictionary or its
+ *     arena full (SG_E_CAPACITY, dictionary unchanged; outputs undefined). SG_E_INVAL before sg_gateway_load_rules.
+ * Not covered: regular expressions on the device, GatewayApiDefinitionManager's path matching, the node handle. */
+#define SG_GW_PARSE_CLIENT_IP  0
+#define SG_GW_PARSE_HOST       1
+#define SG_GW_PARSE_HEADER     2
+#define SG_GW_PARSE_URL_PARAM  3
+#define SG_GW_PARSE_COOKIE     4
+#define SG_GW_MATCH_EXACT      0
+#define SG_GW_MATCH_PREFIX     1
+#define SG_GW_MATCH_REGEX      2
+#define SG_GW_MATCH_CONTAINS   3
+#define SG_GW_ITEM_NULL         1u  /* the RequestItemParser returned null                        */
+#define SG_GW_ITEM_REGEX_MATCH  2u  /* REGEX rules: the value matches (or the pattern is invalid) */
+#define SG_GW_NM_THRESHOLD  10000000 /* generateNonMatchPassParamItem's count                     */
+typedef struct sg_gateway_rule {
+    double   count;
+    int64_t  interval_sec;             /* → durationInSec                                         */
+    uint32_t resource;
+    int32_t  resource_mode;            /* RESOURCE_MODE_ROUTE_ID 0 / CUSTOM_API_NAME 1            */
+    int32_t  grade;
+    int32_t  control_behavior;
+    int32_t  burst;
+    int32_t  max_queueing_timeout_ms;
+    int32_t  capacity_log2;            /* the converted rule's sg_param_rule.capacity_log2        */
+    int32_t  has_item;                 /* 0: paramItem == null; the fields below are then unread  */
+    int32_t  parse_strategy;           /* SG_GW_PARSE_*                                           */
+    int32_t  field_blank;              /* StringUtil.isBlank(fieldName)                           */
+    int32_t  match_strategy;           /* SG_GW_MATCH_*                                           */
+    int32_t  pattern_null;             /* pattern == null                                         */
+    uint32_t pattern_off;
+    uint32_t pattern_len;
+} sg_gateway_rule;                     /* 72 bytes */
+typedef struct sg_gateway_req {
+    uint32_t resource;
+    int32_t  resource_mode;
+    uint32_t item_begin;
+    uint32_t item_count;
+} sg_gateway_req;                      /* 16 bytes */
+typedef struct sg_gateway_item {
+    uint32_t off;
+    uint32_t len;
+    uint32_t flags;                    /* SG_GW_ITEM_*                                            */
+    uint32_t reserved;
+} sg_gateway_item;                     /* 16 bytes */
+int sg_gateway_load_rules(sg_handle* h, const sg_gateway_rule* rules, uint32_t n, const uint8_t* pattern_bytes,
+                          uint64_t n_pattern_bytes, uint32_t n_resources);
+int sg_gateway_converted(sg_handle* h, sg_pslot_rule* rules_out, uint32_t cap, uint32_t* n_rules,
+                         sg_param_hot_item* hot_out, uint32_t hot_cap, uint32_t* n_hot, uint32_t* source_out);
+int sg_gateway_param_rule_count(sg_handle* h, uint32_t resource, uint32_t* n_item_rules, int32_t* has_item_less);
+int sg_gateway_parse_batch(sg_handle* h, const sg_gateway_req* req, uint64_t n, const sg_gateway_item* items,
+                           uint64_t n_items, const uint8_t* bytes, uint64_t n_bytes, sg_pslot_arg* args_out,
+                           uint64_t args_cap, uint64_t* values_out, uint64_t values_cap, sg_slot_ext* ext_inout,
+                           sg_pslot_event* pev_inout, uint64_t* n_args, uint64_t* n_values, void* stream);
+
 /* ---------- Envoy rate-limit service ----------
  * SentinelEnvoyRlsServiceImpl.shouldRateLimit (sentinel-cluster/sentinel-cluster-server-envoy-rls/.../service/v3/
  * SentinelEnvoyRlsServiceImpl.java:34-85) for a time-ordered batch of n RateLimitRequests on a handle whose flow

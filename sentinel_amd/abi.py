@@ -191,6 +191,21 @@ assert SERVER_ROW_DTYPE.itemsize == 40
 (SLOG_FLOW_WAITING, SLOG_FLOW_BLOCK, SLOG_FLOW_BLOCK_REQUEST, SLOG_FLOW_OCCUPIED_BLOCK, SLOG_FLOW_PASS,
  SLOG_FLOW_PASS_REQUEST, SLOG_PARAM_PASS, SLOG_PARAM_BLOCK, SLOG_CONC_PASS, SLOG_CONC_BLOCK,
  SLOG_CONC_RELEASE) = range(11)
+# GatewayFlowSlot (sg_gateway_*): a GatewayFlowRule with its GatewayParamFlowItem flattened, a request, one raw item
+GATEWAY_RULE_DTYPE = np.dtype([("count", "<f8"), ("interval_sec", "<i8"), ("resource", "<u4"), ("resource_mode", "<i4"),
+                               ("grade", "<i4"), ("control_behavior", "<i4"), ("burst", "<i4"),
+                               ("max_queueing_timeout_ms", "<i4"), ("capacity_log2", "<i4"), ("has_item", "<i4"),
+                               ("parse_strategy", "<i4"), ("field_blank", "<i4"), ("match_strategy", "<i4"),
+                               ("pattern_null", "<i4"), ("pattern_off", "<u4"), ("pattern_len", "<u4")], align=True)
+GATEWAY_REQ_DTYPE = np.dtype([("resource", "<u4"), ("resource_mode", "<i4"), ("item_begin", "<u4"),
+                              ("item_count", "<u4")], align=True)
+GATEWAY_ITEM_DTYPE = np.dtype([("off", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")], align=True)
+assert GATEWAY_RULE_DTYPE.itemsize == 72 and GATEWAY_REQ_DTYPE.itemsize == 16 and GATEWAY_ITEM_DTYPE.itemsize == 16
+GW_PARSE_CLIENT_IP, GW_PARSE_HOST, GW_PARSE_HEADER, GW_PARSE_URL_PARAM, GW_PARSE_COOKIE = range(5)
+GW_MATCH_EXACT, GW_MATCH_PREFIX, GW_MATCH_REGEX, GW_MATCH_CONTAINS = range(4)
+GW_ITEM_NULL, GW_ITEM_REGEX_MATCH = 1, 2
+GW_NM_THRESHOLD = 10_000_000
+GW_RESOURCE_MODE_ROUTE_ID, GW_RESOURCE_MODE_CUSTOM_API_NAME = 0, 1
 CONTROL_DEFAULT, CONTROL_WARM_UP, CONTROL_RATE_LIMITER, CONTROL_WARM_UP_RATE_LIMITER = 0, 1, 2, 3
 LIMIT_APP_DEFAULT, LIMIT_APP_OTHER = 0, -1
 STRATEGY_DIRECT, STRATEGY_RELATE, STRATEGY_CHAIN = 0, 1, 2

@@ -201,6 +201,20 @@ struct sg_handle {
         DevBuf<uint64_t> totals;              // [2] device: scan total, miss count
     } vd;
 
+    // GatewayFlowSlot: the converted rules and the parser's tables (gateway_rules.h, gateway.hip)
+    struct Gateway {
+        bool on = false;
+        GwConverted conv;                     // host copy: sg_gateway_converted, sg_gateway_param_rule_count
+        uint64_t nm_id = 0, d_id = 0;         // "$NM", "$D"
+        DevBuf<GwRes> res;
+        DevBuf<GwItemRule> rules;
+        DevBuf<uint8_t> patterns;
+        DevBuf<uint64_t> cnt;                 // batch scratch, grown on demand: [n + 1]
+        DevBuf<uint64_t> item_map;            // [n_items]
+        DevBuf<uint64_t> sums;                // scan workspace for n + 1
+        DevBuf<uint32_t> err;                 // [1]
+    } gw;
+
     // local slot chain
     sg_local_config lcfg{2, 1000, 500, 0};
     std::vector<LRule> ltab;          // [K] the resources (sg_local_load_rules), origin nodes not included
@@ -1362,6 +1376,148 @@ int sg_codec_encode_param(sg_handle* h, const int32_t* xid, const uint8_t* kind,
     c.res = res;
     c.frames = frames_out;
     HIP_TRY(h, launch_pcodec_encode(c, (hipStream_t)stream));
+    return SG_OK;
+}
+
+// ------------------------------------------------- GatewayFlowSlot: rules and the param parser (gateway.hip)
+
+int sg_gateway_load_rules(sg_handle* h, const sg_gateway_rule* rules, uint32_t n, const uint8_t* pattern_bytes,
+                          uint64_t n_pattern_bytes, uint32_t n_resources) {
+    if (!h) return SG_E_INVAL;
+    if (!h->vd.on) return fail(h, SG_E_INVAL, "sg_vdict_init first");
+    if ((n && !rules) || (n_pattern_bytes && !pattern_bytes)) return fail(h, SG_E_INVAL, "null buffer");
+    if (n_pattern_bytes >= (1ull << 32)) return fail(h, SG_E_INVAL, "pattern blob of 4 GiB or more");
+    if (!gw_ranges_ok(rules, n, n_pattern_bytes, n_resources))
+        return fail(h, SG_E_INVAL, "gateway rule: resource >= n_resources or pattern outside the blob");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    // "$NM" then "$D": a known string keeps its id, so a reload (or a header value that came first) moves nothing
+    static const uint8_t types[2] = {SG_PARAM_TYPE_STRING, SG_PARAM_TYPE_STRING};
+    static const uint32_t offsets[3] = {0, 3, 5};
+    static const uint8_t bytes[5] = {'$', 'N', 'M', '$', 'D'};
+    uint64_t ids[2] = {0, 0};
+    const int irc = sg_vdict_intern(h, types, offsets, bytes, 2, ids);
+    if (irc) return irc;
+    GwConverted conv = gw_convert(rules, n, n_resources, ids[0]);
+    DevBuf<GwRes> d_res;
+    DevBuf<GwItemRule> d_rules;
+    DevBuf<uint8_t> d_pat;
+    DevBuf<uint32_t> d_err;
+    if (!d_res.alloc(conv.res.size() ? conv.res.size() : 1) || !d_rules.alloc(conv.items.size() ? conv.items.size() : 1) ||
+        !d_pat.alloc(n_pattern_bytes ? n_pattern_bytes : 1) || !d_err.alloc(1))
+        return fail(h, SG_E_NOMEM, "gateway parser tables");
+    if (!conv.res.empty())
+        HIP_TRY(h, hipMemcpy(d_res, conv.res.data(), sizeof(GwRes) * conv.res.size(), hipMemcpyHostToDevice));
+    if (!conv.items.empty())
+        HIP_TRY(h, hipMemcpy(d_rules, conv.items.data(), sizeof(GwItemRule) * conv.items.size(), hipMemcpyHostToDevice));
+    if (n_pattern_bytes) HIP_TRY(h, hipMemcpy(d_pat, pattern_bytes, n_pattern_bytes, hipMemcpyHostToDevice));
+    auto& g = h->gw;
+    g.conv = std::move(conv);
+    g.nm_id = ids[0];
+    g.d_id = ids[1];
+    g.res = std::move(d_res);
+    g.rules = std::move(d_rules);
+    g.patterns = std::move(d_pat);
+    g.err = std::move(d_err);
+    g.on = true;
+    return SG_OK;
+}
+
+int sg_gateway_converted(sg_handle* h, sg_pslot_rule* rules_out, uint32_t cap, uint32_t* n_rules,
+                         sg_param_hot_item* hot_out, uint32_t hot_cap, uint32_t* n_hot, uint32_t* source_out) {
+    if (!h) return SG_E_INVAL;
+    if (!h->gw.on) return fail(h, SG_E_INVAL, "sg_gateway_load_rules first");
+    if (!n_rules || !n_hot) return fail(h, SG_E_INVAL, "null buffer");
+    const GwConverted& c = h->gw.conv;
+    *n_rules = (uint32_t)c.rules.size();
+    *n_hot = (uint32_t)c.hot.size();
+    if (c.rules.size() > cap || c.hot.size() > hot_cap) return fail(h, SG_E_CAPACITY, "converted rule buffers too small");
+    if ((!c.rules.empty() && !rules_out) || (!c.hot.empty() && !hot_out)) return fail(h, SG_E_INVAL, "null buffer");
+    std::copy(c.rules.begin(), c.rules.end(), rules_out);
+    std::copy(c.hot.begin(), c.hot.end(), hot_out);
+    if (source_out) std::copy(c.source.begin(), c.source.end(), source_out);
+    return SG_OK;
+}
+
+int sg_gateway_param_rule_count(sg_handle* h, uint32_t resource, uint32_t* n_item_rules, int32_t* has_item_less) {
+    if (!h) return SG_E_INVAL;
+    if (!h->gw.on) return fail(h, SG_E_INVAL, "sg_gateway_load_rules first");
+    const auto& res = h->gw.conv.res;
+    const GwRes r = resource < res.size() ? res[resource] : GwRes{0, 0, 0, 0};
+    if (n_item_rules) *n_item_rules = r.n_items;
+    if (has_item_less) *has_item_less = (int32_t)r.has_item_less;
+    return SG_OK;
+}
+
+int sg_gateway_parse_batch(sg_handle* h, const sg_gateway_req* req, uint64_t n, const sg_gateway_item* items,
+                           uint64_t n_items, const uint8_t* bytes, uint64_t n_bytes, sg_pslot_arg* args_out,
+                           uint64_t args_cap, uint64_t* values_out, uint64_t values_cap, sg_slot_ext* ext_inout,
+                           sg_pslot_event* pev_inout, uint64_t* n_args, uint64_t* n_values, void* stream) {
+    if (!h) return SG_E_INVAL;
+    if (!n_args || !n_values) return fail(h, SG_E_INVAL, "null buffer");
+    *n_args = 0;
+    *n_values = 0;
+    if (!h->vd.on) return fail(h, SG_E_INVAL, "sg_vdict_init first");
+    auto& gw = h->gw;
+    if (!gw.on) return fail(h, SG_E_INVAL, "sg_gateway_load_rules first");
+    if (n == 0) return SG_OK;
+    if (!req || (n_items && !items) || (n_bytes && !bytes) || (args_cap && !args_out) || (values_cap && !values_out))
+        return fail(h, SG_E_INVAL, "null buffer");
+    if (((uintptr_t)bytes & 3u) != 0) return fail(h, SG_E_INVAL, "bytes must be 4-byte aligned");
+    if (n_items >= (1ull << 31) || n_bytes >= (1ull << 32))  // args and values (<= n_items + n) fit 32 bits each
+        return fail(h, SG_E_INVAL, "2^31 items or 2^32 bytes, or more");
+    auto& v = h->vd;
+    if (n > v.max_batch) return fail(h, SG_E_CAPACITY, "more requests than max_batch_values");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!gw.cnt.reserve(n + 1) || !gw.item_map.reserve(n_items ? n_items : 1) || !gw.sums.reserve(scan_blocks(n + 1) + 1))
+        return fail(h, SG_E_NOMEM, "gateway batch buffers");
+    GwArgs g{};
+    g.n = n;
+    g.req = req;
+    g.items = items;
+    g.n_items = n_items;
+    g.bytes = bytes;
+    g.n_bytes = n_bytes;
+    g.res = gw.res;
+    g.n_resources = (uint32_t)gw.conv.res.size();
+    g.rules = gw.rules;
+    g.patterns = gw.patterns;
+    g.nm_id = gw.nm_id;
+    g.d_id = gw.d_id;
+    g.cnt = gw.cnt;
+    g.item_map = gw.item_map;
+    g.err = gw.err;
+    g.args = args_out;
+    g.ext = ext_inout;
+    g.pev = pev_inout;
+    HIP_TRY(h, hipMemsetAsync(gw.err, 0, 4, st));
+    if (n_items) HIP_TRY(h, hipMemsetAsync(gw.item_map, 0, 8 * n_items, st));
+    HIP_TRY(h, launch_gw_count(g, st));
+    HIP_TRY(h, launch_scan_u64(gw.cnt, n + 1, gw.sums, v.totals, st));
+    HIP_TRY(h, hipMemsetAsync(v.totals + 1, 0, 8, st));
+    uint64_t total = 0;
+    uint32_t err = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, v.totals, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(&err, gw.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (err & kGwErrItemCount) return fail(h, SG_E_INVAL, "item_count differs from the resource's item-rule count");
+    if (err & kGwErrRange) return fail(h, SG_E_INVAL, "item range or byte range out of bounds, or a string of 16 MiB or more");
+    if (err & kGwErrShared) return fail(h, SG_E_INVAL, "an item belongs to two requests");
+    const uint64_t na = total >> 32, nv = total & 0xFFFFFFFFull;
+    *n_args = na;
+    *n_values = nv;
+    if (na > args_cap) return fail(h, SG_E_CAPACITY, "args_out too small");
+    if (nv > values_cap) return fail(h, SG_E_CAPACITY, "values_out too small");
+    if (nv > v.max_batch) return fail(h, SG_E_CAPACITY, "more values than max_batch_values");
+    if (nv) {
+        g.vd = vd_args(h, nv, bytes, values_out);
+        HIP_TRY(h, launch_gw_match(g, st));
+        const int frc = vd_finish(h, g.vd, st);
+        if (frc) return frc;
+    }
+    HIP_TRY(h, launch_gw_emit(g, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
     return SG_OK;
 }
 

@@ -9,6 +9,7 @@
 #include "../../include/sentinel_gpu.h"
 #include "authority_rules.h"
 #include "blocklog_rules.h"
+#include "gateway_rules.h"
 #include "serverlog_rules.h"
 #include "system_rules.h"
 #include "search_dev.h"
@@ -1255,5 +1256,36 @@ hipError_t launch_vd_rehash(const VDictArgs& v, hipStream_t stream);
 hipError_t launch_vd_gather(const VEntry* entries, const uint64_t* ids, uint64_t n, VEntry* out, hipStream_t stream);
 hipError_t launch_vd_bytes(const VEntry* e, const uint32_t* offsets, uint64_t n, const uint8_t* arena, uint8_t* out,
                            hipStream_t stream);
+
+// ---- GatewayFlowSlot's request parameter parser (gateway.hip; the tables come from gateway_rules.h) ----
+
+constexpr uint32_t kGwErrItemCount = 1;  // item_count != the resource's item-rule count
+constexpr uint32_t kGwErrRange = 2;      // an item range or byte range out of bounds, a string of 2^24 bytes or more
+constexpr uint32_t kGwErrShared = 4;     // an item of two requests
+
+struct GwArgs {
+    uint64_t n;                 // requests
+    const sg_gateway_req* req;
+    const sg_gateway_item* items;
+    uint64_t n_items;
+    const uint8_t* bytes;
+    uint64_t n_bytes;
+    const GwRes* res;           // [n_resources]
+    uint32_t n_resources;
+    const GwItemRule* rules;
+    const uint8_t* patterns;
+    uint64_t nm_id, d_id;       // "$NM", "$D"
+    uint64_t* cnt;              // [n + 1] args << 32 | values per request, then their exclusive scan; cnt[n] = totals
+    uint64_t* item_map;         // [n_items] 0 = no live request reads the item, else (request + 1) << 32 | value ordinal
+    uint32_t* err;              // kGwErr* bits
+    VDictArgs vd;               // ids = values_out
+    sg_pslot_arg* args;
+    sg_slot_ext* ext;           // nullable
+    sg_pslot_event* pev;        // nullable
+};
+
+hipError_t launch_gw_count(const GwArgs& g, hipStream_t stream);
+hipError_t launch_gw_match(const GwArgs& g, hipStream_t stream);
+hipError_t launch_gw_emit(const GwArgs& g, hipStream_t stream);
 
 }  // namespace sg

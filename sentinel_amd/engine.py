@@ -47,7 +47,8 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_local_system_last_path", "sg_local_system_first_unproven",
            "sg_local_block_log_enable", "sg_local_block_log", "sg_server_log_enable", "sg_server_log",
            "sg_node_server_log_enable", "sg_node_server_log", "sg_node_local_block_log_enable",
-           "sg_node_local_block_log"]
+           "sg_node_local_block_log",
+           "sg_gateway_load_rules", "sg_gateway_converted", "sg_gateway_param_rule_count", "sg_gateway_parse_batch"]
 
 _lib = None
 
@@ -141,6 +142,11 @@ def load_library():
         "sg_vdict_size": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "sg_codec_decode_param": (C.c_int, [vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64), vp, vp, vp]),
         "sg_codec_encode_param": (C.c_int, [vp, vp, vp, vp, u64, vp, vp]),
+        "sg_gateway_load_rules": (C.c_int, [vp, vp, u32, vp, u64, u32]),
+        "sg_gateway_converted": (C.c_int, [vp, vp, u32, C.POINTER(u32), vp, u32, C.POINTER(u32), vp]),
+        "sg_gateway_param_rule_count": (C.c_int, [vp, u32, C.POINTER(u32), C.POINTER(C.c_int32)]),
+        "sg_gateway_parse_batch": (C.c_int, [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, C.POINTER(u64),
+                                             C.POINTER(u64), vp]),
         "sg_pace_load_rules": (C.c_int, [vp, vp, u32]),
         "sg_pace_decide_batch": (C.c_int, [vp, vp, u64, vp, vp]),
         "sg_pace_decide_batch_host": (C.c_int, [vp, vp, u64, vp]),
@@ -766,6 +772,106 @@ class FlowEngine:
                                                   C.c_void_p(res_ptr), n, C.c_void_p(frames_ptr),
                                                   C.c_void_p(stream_ptr)))
 
+    # ---- GatewayFlowSlot: gateway rules and the request parameter parser (sg_gateway_*)
+    def gateway_load_rules(self, rules, patterns=b"", n_resources=None, extra_pslot_rules=None, extra_hot=None):
+        """GatewayRuleManager.loadRules: validates and converts the gateway rules (abi.GATEWAY_RULE_DTYPE, patterns =
+        the blob their pattern ranges index), loads the parser's tables, and loads the converted ParamFlowRules IN
+        FRONT OF the ordinary ones (extra_pslot_rules / extra_hot, hot_begin relative to extra_hot) with one
+        pslot_load_rules (skipped when there is no rule of either kind). Needs vdict_init. Returns (rules, hot, source): what was loaded, source[i] = the gateway
+        rule behind loaded rule i (-1 for an ordinary one)."""
+        rules = np.ascontiguousarray(rules, dtype=abi.GATEWAY_RULE_DTYPE).reshape(-1)
+        pat = np.frombuffer(bytes(patterns), np.uint8).copy()
+        n_res = (int(rules["resource"].max()) + 1 if len(rules) else 1) if n_resources is None else n_resources
+        self._check(self._L.sg_gateway_load_rules(self.h, abi.ptr(rules) if len(rules) else None, len(rules),
+                                                  abi.ptr(pat) if len(pat) else None, len(pat), n_res))
+        conv, hot, source = self.gateway_converted()
+        extra = np.ascontiguousarray(np.zeros(0, abi.PSLOT_RULE_DTYPE) if extra_pslot_rules is None
+                                     else extra_pslot_rules, dtype=abi.PSLOT_RULE_DTYPE).reshape(-1).copy()
+        ehot = np.ascontiguousarray(np.zeros(0, abi.PARAM_HOT_DTYPE) if extra_hot is None else extra_hot,
+                                    dtype=abi.PARAM_HOT_DTYPE).reshape(-1)
+        extra["rule"]["hot_begin"] += len(hot)
+        all_rules, all_hot = np.concatenate([conv, extra]), np.concatenate([hot, ehot])
+        if len(all_rules):
+            self.pslot_load_rules(all_rules, all_hot, n_res)
+        return all_rules, all_hot, np.concatenate([source.astype(np.int64), np.full(len(extra), -1, np.int64)])
+
+    def gateway_converted(self):
+        """The converted ParamFlowRules sorted by (resource, paramIdx, caller order), their hot items, and the index
+        of the gateway rule behind each."""
+        nr, nh = C.c_uint32(), C.c_uint32()
+        rc = self._L.sg_gateway_converted(self.h, None, 0, C.byref(nr), None, 0, C.byref(nh), None)
+        if rc not in (0, abi.SG_E_CAPACITY):
+            self._check(rc)
+        conv = np.zeros(nr.value, abi.PSLOT_RULE_DTYPE)
+        hot = np.zeros(nh.value, abi.PARAM_HOT_DTYPE)
+        source = np.zeros(nr.value, np.uint32)
+        self._check(self._L.sg_gateway_converted(self.h, abi.ptr(conv), len(conv), C.byref(nr), abi.ptr(hot), len(hot),
+                                                 C.byref(nh), abi.ptr(source)))
+        return conv, hot, source
+
+    def gateway_param_rule_count(self, resource):
+        """(item rules, has an item-less rule) of a resource: how many items a request of it carries."""
+        k, d = C.c_uint32(), C.c_int32()
+        self._check(self._L.sg_gateway_param_rule_count(self.h, resource, C.byref(k), C.byref(d)))
+        return int(k.value), bool(d.value)
+
+    def gateway_parse_device(self, req_ptr: int, n: int, items_ptr: int, n_items: int, bytes_ptr: int, n_bytes: int,
+                             args_ptr: int, args_cap: int, values_ptr: int, values_cap: int, ext_ptr: int = 0,
+                             pev_ptr: int = 0, stream_ptr: int = 0):
+        """Device addresses: sg_gateway_req[n], sg_gateway_item[n_items], the items' bytes → sg_pslot_arg, u64 value
+        ids, and the arg spans written into sg_slot_ext[n] / sg_pslot_event[n] where given. Returns (n_args,
+        n_values) after the stream has completed; an EngineError carries them in .n_args / .n_values."""
+        na, nv = C.c_uint64(), C.c_uint64()
+        rc = self._L.sg_gateway_parse_batch(self.h, C.c_void_p(req_ptr), n, C.c_void_p(items_ptr), n_items,
+                                            C.c_void_p(bytes_ptr), n_bytes, C.c_void_p(args_ptr), args_cap,
+                                            C.c_void_p(values_ptr), values_cap, C.c_void_p(ext_ptr),
+                                            C.c_void_p(pev_ptr), C.byref(na), C.byref(nv), C.c_void_p(stream_ptr))
+        if rc != 0:
+            e = EngineError(rc, self._L.sg_last_error(self.h).decode())
+            e.n_args, e.n_values = int(na.value), int(nv.value)
+            raise e
+        return int(na.value), int(nv.value)
+
+    def gateway_parse_host(self, req, items, data, args_cap=None, values_cap=None, ext=None, pev=None,
+                           with_device=False):
+        """Testing aid: gateway_parse_device over host arrays staged through torch. Returns (args, values, ext, pev):
+        the sg_pslot_arg records, the value ids, and the ext / pev arrays with their arg spans filled in (None where
+        not given). with_device: a fifth element, the device tensors {"args", "values", "ext", "pev"} the parser
+        wrote, to hand to slot_decide_device / pslot_decide_device as they are."""
+        import torch
+        req = np.ascontiguousarray(req, dtype=abi.GATEWAY_REQ_DTYPE).reshape(-1)
+        items = np.ascontiguousarray(items, dtype=abi.GATEWAY_ITEM_DTYPE).reshape(-1)
+        data = np.frombuffer(bytes(data), np.uint8)
+        n, n_items = len(req), len(items)
+        if args_cap is None:
+            args_cap = n_items + n
+        if values_cap is None:
+            values_cap = n_items + n
+
+        def dev(a, itemsize):
+            raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            t = torch.zeros(max(len(raw), itemsize), dtype=torch.uint8, device="cuda")
+            t[:len(raw)] = torch.from_numpy(raw.copy())
+            return t
+
+        r_t, i_t, b_t = dev(req, 16), dev(items, 16), dev(data, 4)
+        a_t = torch.zeros(max(args_cap, 1) * 16, dtype=torch.uint8, device="cuda")
+        v_t = torch.zeros(max(values_cap, 1) * 8, dtype=torch.uint8, device="cuda")
+        e_t = None if ext is None else dev(np.ascontiguousarray(ext, dtype=abi.SLOT_EXT_DTYPE), 16)
+        p_t = None if pev is None else dev(np.ascontiguousarray(pev, dtype=abi.PSLOT_EVENT_DTYPE), 32)
+        na, nv = self.gateway_parse_device(r_t.data_ptr(), n, i_t.data_ptr(), n_items, b_t.data_ptr(), len(data),
+                                           a_t.data_ptr(), args_cap, v_t.data_ptr(), values_cap,
+                                           0 if e_t is None else e_t.data_ptr(), 0 if p_t is None else p_t.data_ptr(),
+                                           torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        args = a_t.cpu().numpy().view(abi.PSLOT_ARG_DTYPE)[:na].copy()
+        values = v_t.cpu().numpy().view(np.uint64)[:nv].copy()
+        ext_out = None if e_t is None else e_t.cpu().numpy().view(abi.SLOT_EXT_DTYPE)[:n].copy()
+        pev_out = None if p_t is None else p_t.cpu().numpy().view(abi.PSLOT_EVENT_DTYPE)[:n].copy()
+        if with_device:
+            return args, values, ext_out, pev_out, {"args": a_t, "values": v_t, "ext": e_t, "pev": p_t}
+        return args, values, ext_out, pev_out
+
     def decide_host(self, req: np.ndarray) -> np.ndarray:
         req = np.ascontiguousarray(req, dtype=abi.REQ_DTYPE)
         out = np.zeros(len(req), abi.RES_DTYPE)
@@ -959,6 +1065,13 @@ class FlowEngine:
                                                        len(args), abi.ptr(values) if len(values) else None,
                                                        len(values), abi.ptr(out)))
         return out
+
+    def pslot_decide_device(self, ev_ptr: int, n: int, args_ptr: int, n_args: int, values_ptr: int, n_values: int,
+                            out_ptr: int, stream_ptr: int = 0):
+        """DEVICE pointers: sg_pslot_event[n], sg_pslot_arg, u64 values → sg_pslot_result[n]."""
+        self._check(self._L.sg_pslot_decide_batch(self.h, C.c_void_p(ev_ptr), n, C.c_void_p(args_ptr or None), n_args,
+                                                  C.c_void_p(values_ptr or None), n_values, C.c_void_p(out_ptr),
+                                                  C.c_void_p(stream_ptr)))
 
     def pslot_thread_count(self, res, idx, value):
         v = C.c_int64()
