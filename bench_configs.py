@@ -18,6 +18,9 @@ bench.py (which measures the headline C3 workload).
   --workload node  the C3 workload through the node handle (G same-device shards, --shards), pipelined.
   --workload gateway  GatewayFlowSlot: --resources routes with 3 item rules (client IP, EXACT header, CONTAINS URL
                   parameter) and an item-less rule each; times sg_gateway_parse_batch alone and parse + the slot chain.
+  --workload gateway_api  the gateway workload behind its front: --resources routes plus --resources / 4 custom APIs (half
+                  exact paths, half /x…/** definitions, a URL-parameter rule and an item-less rule each); HTTP requests
+                  with a path and three fields; times sg_gateway_expand_batch alone and expand + parse + the slot chain.
   --workload pace  1M resources, each a FlowRule with CONTROL_BEHAVIOR_RATE_LIMITER (RateLimiterController,
                  count U{1..64}, maxQueueingTimeMs 500), 16M canPass calls per 1000 ms batch, Zipf(1.0),
                  acquire 1 (10 % U{2..4}).
@@ -812,6 +815,180 @@ def gateway(args, dev):
             "data": "synthetic (GPU-generated, seeded): fixed-width client IP, header and URL parameter strings"}
 
 
+def gateway_api(args, dev):
+    """The gateway workload from the HTTP request on: --resources routes with the gateway workload's four rules each, and
+    A = max(16, --resources / 4) custom APIs, even ones defined by an exact path, odd ones by /x<id>/**, each with a
+    URL-parameter rule and an item-less rule. A request has a route (Zipf 1.0), a 16-byte path (40 % the exact path of a
+    Zipf(1.0) API, 40 % under an Ant API's prefix, 20 % matching nothing) and three fields (client IP, header, URL
+    parameter). Timed: sg_gateway_expand_batch alone; sg_gateway_parse_batch alone over the expansion; and expand + parse
+    + sg_slot_decide_batch on steps of at most 2^16 requests (entries only: no exits, so the step stays small)."""
+    K, n = args.resources, args.events
+    A = max(16, K // 4)
+    n_clients = min(1 << 20, max(1024, n // 4))
+    L = (12, 8, 12)                   # bytes of the client IP, the header value and the URL parameter
+    stride, P = sum(L), 16            # field bytes and path bytes per request
+    HDR, UID = 1, 2                   # the caller's field name ids
+    g = np.zeros(4 * K + 2 * A, abi.GATEWAY_RULE_DTYPE)
+    g["grade"], g["interval_sec"], g["max_queueing_timeout_ms"], g["pattern_null"] = 1, 1, 500, 1
+    g["capacity_log2"] = 10
+    g["resource"][:4 * K] = np.repeat(np.arange(K, dtype=np.uint32), 4)
+    g["resource"][4 * K:] = K + np.repeat(np.arange(A, dtype=np.uint32), 2)
+    field_id = np.zeros(len(g), np.uint32)
+    pat = b"tier-vipid=7"
+    r4 = g[:4 * K]
+    ip, hdr, url, dflt = r4[0::4], r4[1::4], r4[2::4], r4[3::4]
+    ip["has_item"], ip["parse_strategy"], ip["count"] = 1, abi.GW_PARSE_CLIENT_IP, 5
+    # the client-IP rule's table holds every client the route sees in the chain steps
+    res_cdf, res_perm = zipf_cdf(K, 1.0, 31)
+    nc = min(n, 1 << 16)
+    seen = np.minimum(n_clients, np.diff(res_cdf, prepend=0.0) * nc * (args.warmup + args.steps) * 2.0)
+    cap = np.zeros(K, np.int32)
+    cap[res_perm] = np.maximum(10, np.ceil(np.log2(np.maximum(seen, 1.0))).astype(np.int32) + 1)
+    ip["capacity_log2"] = cap
+    hdr["has_item"], hdr["parse_strategy"], hdr["match_strategy"], hdr["count"] = 1, abi.GW_PARSE_HEADER, abi.GW_MATCH_EXACT, 50
+    hdr["pattern_null"], hdr["pattern_off"], hdr["pattern_len"] = 0, 0, 8
+    url["has_item"], url["parse_strategy"], url["match_strategy"], url["count"] = 1, abi.GW_PARSE_URL_PARAM, abi.GW_MATCH_CONTAINS, 20
+    url["pattern_null"], url["pattern_off"], url["pattern_len"] = 0, 8, 4
+    dflt["count"] = 200
+    field_id[1:4 * K:4], field_id[2:4 * K:4] = HDR, UID
+    a_url, a_dflt = g[4 * K::2], g[4 * K + 1::2]
+    a_url["resource_mode"], a_dflt["resource_mode"] = 1, 1
+    a_url["has_item"], a_url["parse_strategy"], a_url["count"] = 1, abi.GW_PARSE_URL_PARAM, 30
+    a_dflt["count"] = 400
+    field_id[4 * K::2] = UID
+    # definitions: API a is resource K + a; one predicate each, the pattern 16 bytes
+    apis = np.zeros(A, abi.GATEWAY_API_DTYPE)
+    apis["resource"], apis["pred_begin"], apis["pred_count"] = K + np.arange(A), np.arange(A), 1
+    preds = np.zeros(A, abi.GATEWAY_API_PRED_DTYPE)
+    names = [b"/exact/%09x" % a if a % 2 == 0 else b"/x%08x/**" % a for a in range(A)]
+    preds["match_strategy"] = [abi.GW_URL_MATCH_EXACT if a % 2 == 0 else abi.GW_URL_MATCH_PREFIX for a in range(A)]
+    preds["pattern_len"] = [len(x) for x in names]
+    preds["pattern_off"] = np.concatenate([[0], np.cumsum(preds["pattern_len"])[:-1]])
+    R = K + A
+    eng = FlowEngine(device=0, max_batch=2 * n)
+    eng.vdict_init(max(12, int(np.ceil(np.log2(n_clients + 4096))) + 1), max(64 << 20, n_clients * 24), 8 * n)
+    eng.local_load_rules(_gateway_local_rules(R), 2, 1000, 500)
+    eng.gateway_load_apis(apis, preds, b"".join(names), R, 0)
+    eng.gateway_load_rules(g, pat, R)
+    eng.gateway_set_item_fields(field_id)
+    api_cdf, api_perm = zipf_cdf(A // 2, 1.0, 34)
+    ip_cdf, ip_perm = zipf_cdf(n_clients, 1.1, 32)
+    to = lambda x: torch.from_numpy(x).to(dev)
+    res_cdf_t, res_perm_t, api_cdf_t, api_perm_t = to(res_cdf), to(res_perm), to(api_cdf), to(api_perm)
+    ip_cdf_t, ip_perm_t = to(ip_cdf), to(ip_perm)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(35)
+    hexd = torch.tensor(list(b"0123456789abcdef"), dtype=torch.uint8, device=dev)
+
+    def text(prefix, x, digits, suffix=b""):
+        cols = [torch.full((n,), c, dtype=torch.uint8, device=dev) for c in prefix]
+        cols += [hexd[(x >> (4 * (digits - 1 - j))) & 15] for j in range(digits)]
+        cols += [torch.full((n,), c, dtype=torch.uint8, device=dev) for c in suffix]
+        return torch.stack(cols, dim=1)
+
+    fields = torch.zeros((n, 3, 4), dtype=torch.int32, device=dev)      # sg_gateway_field: kind, name_id, off, len
+    base = (n * P + torch.arange(n, device=dev, dtype=torch.int64) * stride)
+    fields[:, 0, 0], fields[:, 1, 0], fields[:, 2, 0] = abi.GW_PARSE_CLIENT_IP, abi.GW_PARSE_HEADER, abi.GW_PARSE_URL_PARAM
+    fields[:, 1, 1], fields[:, 2, 1] = HDR, UID
+    fields[:, 0, 2], fields[:, 1, 2], fields[:, 2, 2] = base.int(), (base + L[0]).int(), (base + L[0] + L[1]).int()
+    fields[:, 0, 3], fields[:, 1, 3], fields[:, 2, 3] = L
+    fields = fields.reshape(-1).contiguous()
+
+    def batch(b):                     # (sg_gateway_http_req[n] as int32 words, the blob: n paths then n field rows)
+        route = gpu_keys(res_cdf_t, res_perm_t, n, gen)
+        api = gpu_keys(api_cdf_t, api_perm_t, n, gen)
+        client = gpu_keys(ip_cdf_t, ip_perm_t, n, gen)
+        u = torch.rand(n, generator=gen, device=dev)
+        w = torch.rand(n, generator=gen, device=dev)
+        tier = torch.where(u < 0.2, torch.zeros_like(route), 1 + (u * 64).long() % 5)
+        v = torch.randint(0, 16, (n,), generator=gen, device=dev)
+        hdr_b = text(b"tier-", tier + 0xAAA, 3)
+        hdr_b[tier == 0] = torch.tensor(list(b"tier-vip"), dtype=torch.uint8, device=dev)
+        rows = torch.cat([text(b"10.c", client, 8), hdr_b, text(b"a=1&id=", (((v & 3) + 5) << 16) | v, 5)], dim=1)
+        path = text(b"/none/", client, 10)
+        path = torch.where((w < 0.4)[:, None], text(b"/exact/", 2 * api, 9), path)
+        path = torch.where(((w >= 0.4) & (w < 0.8))[:, None], text(b"/x", 2 * api + 1, 8, b"/items"), path)
+        blob = torch.cat([path.reshape(-1), rows.reshape(-1)]).contiguous()
+        ts = T0 + b * 1000 + torch.sort(torch.randint(0, 1000, (n,), generator=gen, device=dev)).values
+        q = torch.zeros((n, 12), dtype=torch.int32, device=dev)
+        q[:, 0:2] = ts.view(torch.int32).view(n, 2)
+        q[:, 2] = route.int()
+        i = torch.arange(n, device=dev, dtype=torch.int32)
+        q[:, 5], q[:, 6], q[:, 7], q[:, 8] = i * P, P, i * 3, 3
+        return q.reshape(-1).contiguous(), blob
+
+    batches = [batch(b) for b in range(args.warmup + args.steps)]
+    nbytes = n * (P + stride)
+    verd = torch.zeros(4, dtype=torch.int32, device=dev)
+    E, I = 2 * n, 4 * n                # a request makes at most two entries: three route items and one API item
+    req_o = torch.empty(E * 16, dtype=torch.uint8, device=dev)
+    items_o = torch.empty(I * 16, dtype=torch.uint8, device=dev)
+    src_o = torch.empty(E * 4, dtype=torch.uint8, device=dev)
+    ev_o = torch.empty(E * 32, dtype=torch.uint8, device=dev)
+    ext_o = torch.zeros(E * 16, dtype=torch.uint8, device=dev)
+    a_t = torch.empty((I + E) * 16, dtype=torch.uint8, device=dev)
+    v_t = torch.empty((I + E) * 8, dtype=torch.uint8, device=dev)
+    out = torch.empty(E * 8, dtype=torch.uint8, device=dev)
+    s = torch.cuda.current_stream(dev).cuda_stream
+
+    def expand(b, m):                 # the first m requests of batch b
+        q, blob = batches[b]
+        return eng.gateway_expand_device(q.data_ptr(), m, fields.data_ptr(), 3 * n, verd.data_ptr(), 0, blob.data_ptr(),
+                                         nbytes, req_o.data_ptr(), E, items_o.data_ptr(), I, src_o.data_ptr(),
+                                         ev_o.data_ptr(), ext_o.data_ptr(), s)
+
+    def parse(b, ne, ni):
+        return eng.gateway_parse_device(req_o.data_ptr(), ne, items_o.data_ptr(), ni, batches[b][1].data_ptr(), nbytes,
+                                        a_t.data_ptr(), I + E, v_t.data_ptr(), I + E, ext_o.data_ptr(), 0, s)
+
+    el_expand = timed(lambda b: expand(b, n), args.warmup, args.steps)
+    ne, ni = expand(0, n)
+    for b in range(args.warmup + args.steps):      # the dictionary sees every client once before the parse is timed
+        parse(b, *expand(b, n))
+    counts = [expand(b, n) for b in range(args.warmup + args.steps)]
+    last = args.warmup + args.steps - 1            # req_o / items_o now hold the last batch's expansion
+    t_parse = timed(lambda b: parse(last, *counts[last]), args.warmup, args.steps)
+    strings, _ = eng.vdict_size()
+    chain = {"ms": None, "entries_per_step": None, "error": None}
+    try:
+        el, served = 0.0, 0
+        for b in range(args.warmup + args.steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            me, mi = expand(b, nc)
+            na, nv = parse(b, me, mi)
+            eng.slot_decide_device(ev_o.data_ptr(), ext_o.data_ptr(), me, a_t.data_ptr(), na, v_t.data_ptr(), nv,
+                                   out.data_ptr(), s)
+            torch.cuda.synchronize()
+            if b >= args.warmup:
+                el += time.perf_counter() - t0
+                served += nc
+        chain = {"ms": el * 1000.0 / args.steps, "entries_per_step": me, "error": None}
+    except Exception as e:  # the expand figures stand on their own
+        chain["error"] = str(e)
+        el, served = el_expand, n * args.steps
+    b_alg = n * 48 + 3 * n * 16 + n * P + ne * (16 + 4 + 32 + 4) + ni * 16
+    return {"metric": "gateway HTTP requests/sec (API matching and expansion on the device + parser + the whole slot chain)",
+            "workload": f"gateway_api: {K} routes x 4 rules, {A} custom APIs (half exact, half /x../**) x 2 rules, {n} "
+                        f"requests per expand batch (16-byte paths, 3 fields); chain steps of {nc} requests, entries only, "
+                        f"Zipf(1.0) routes and APIs, Zipf(1.1) over {n_clients} client IPs",
+            "value": served / el, "el": el, "n": n, "b_alg": b_alg, "touched": strings, "cpu": None,
+            "unit": "requests/s", "dtype": "u8",
+            "extra": {"gateway_api": {"expand_ms": el_expand * 1000.0 / args.steps,
+                                      "expand_requests_per_s": n * args.steps / el_expand,
+                                      "entries_per_batch": ne, "items_per_batch": ni,
+                                      "parse_ms": t_parse * 1000.0 / args.steps,
+                                      "expand_parse_decide_ms": chain["ms"],
+                                      "expand_parse_decide_requests_per_step": nc,
+                                      "expand_parse_decide_entries_per_step": chain["entries_per_step"],
+                                      "expand_parse_decide_requests_per_s": served / el if chain["ms"] else None,
+                                      "expand_parse_decide_error": chain["error"],
+                                      "algorithmic_bytes": {"requests": n * 48, "fields": 3 * n * 16, "paths": n * P,
+                                                            "entries": ne * 56, "items": ni * 16},
+                                      "dictionary_strings": strings}},
+            "data": "synthetic (GPU-generated, seeded): fixed-width paths, client IP, header and URL parameter strings"}
+
+
 def _gateway_local_rules(K):
     r = np.zeros(K, abi.LOCAL_RULE_DTYPE)
     r["flow_grade"] = abi.FLOW_GRADE_NONE
@@ -820,7 +997,8 @@ def _gateway_local_rules(K):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["c2", "c4", "c5", "codec", "pace", "cparam", "node", "slot", "gateway"],
+    ap.add_argument("--workload", choices=["c2", "c4", "c5", "codec", "pace", "cparam", "node", "slot", "gateway",
+                                              "gateway_api"],
                     default="c2")
     ap.add_argument("--shards", type=int, default=0,
                     help="node: shard handles on the one GPU (default 2); cparam: decide through the node handle "
@@ -842,7 +1020,7 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     r = {"c2": c2, "c4": c4, "c5": c5, "codec": codec, "pace": pace, "cparam": cparam, "node": node,
-         "slot": slot, "gateway": gateway}[args.workload](args, dev)
+         "slot": slot, "gateway": gateway, "gateway_api": gateway_api}[args.workload](args, dev)
     ms = r["el"] * 1000.0 / args.steps
     gbs = r["b_alg"] / (ms / 1000.0) / 1e9
     res = {"metric": r["metric"], "value": r["value"], "unit": r.get("unit", "decisions/s"), "n_gpus": 1,

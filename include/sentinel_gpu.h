@@ -1381,7 +1381,8 @@ int sg_codec_encode_param(sg_handle* h, const int32_t* xid, const uint8_t* kind,
  *     requests, a string of 2^24 bytes or more, `bytes` not 4-byte aligned (SG_E_INVAL); n or the value count above
  *     max_batch_values, args_cap / values_cap too small (SG_E_CAPACITY, *n_args / *n_values set); the dictionary or its
  *     arena full (SG_E_CAPACITY, dictionary unchanged; outputs undefined). SG_E_INVAL before sg_gateway_load_rules.
- * Not covered: regular expressions on the device, GatewayApiDefinitionManager's path matching, the node handle. */
+ * Not covered: regular expressions on the device, the node handle. GatewayApiDefinitionManager's path matching and the
+ * expansion of HTTP requests into these records are the block below (sg_gateway_load_apis, sg_gateway_expand_batch). */
 #define SG_GW_PARSE_CLIENT_IP  0
 #define SG_GW_PARSE_HOST       1
 #define SG_GW_PARSE_HEADER     2
@@ -1433,6 +1434,116 @@ int sg_gateway_parse_batch(sg_handle* h, const sg_gateway_req* req, uint64_t n, 
                            uint64_t n_items, const uint8_t* bytes, uint64_t n_bytes, sg_pslot_arg* args_out,
                            uint64_t args_cap, uint64_t* values_out, uint64_t values_cap, sg_slot_ext* ext_inout,
                            sg_pslot_event* pev_inout, uint64_t* n_args, uint64_t* n_values, void* stream);
+
+/* ---- Gateway API definitions (GatewayApiDefinitionManager, the Spring Cloud Gateway adapter's API matchers) and the
+ * expansion of HTTP requests into entries: the front of the gateway path ----
+ * SentinelGatewayFilter.filter (sentinel-spring-cloud-gateway-adapter/.../sc/SentinelGatewayFilter.java:72-100) makes
+ * one entry for the request's route and one for every custom API whose ApiDefinition matches the request path
+ * (pickMatchingApiDefinitions :106-112), each with the Object[] of parseParameterFor. These calls decide the path
+ * predicates on the device and write the records sg_gateway_parse_batch and sg_slot_decide_batch take as they are.
+ *
+ * Definitions. sg_gateway_api is an ApiDefinition: `resource` is the caller's index of the API name, its predicates are
+ * preds[pred_begin, + pred_count), SG_GW_API_NAME_BLANK / SG_GW_API_PREDS_NULL say what isValidApi looks at.
+ * sg_gateway_api_pred is an ApiPredicateItem: the pattern is bytes [pattern_off, + pattern_len) of one blob.
+ *   sg_gateway_load_apis  completes enqueued work; drops what GatewayApiDefinitionManager.isValidApi drops (blank
+ *     name, null predicate set), silently; of valid definitions with one `resource` the LAST in caller order is the
+ *     definition (the reference keeps them in a HashSet). A predicate that is not an ApiPathPredicateItem
+ *     or whose pattern is null or blank (empty or ASCII whitespace only: 9-13, 28-32; a caller whose pattern is blank
+ *     by other white space sets SG_GW_PRED_PATTERN_NULL) is skipped (WebExchangeApiMatcher.fromApiPathPredicate); a
+ *     definition matches when any other predicate does. Each predicate is classified once:
+ *       exact         a strategy other than PREFIX and REGEX: the path bytes equal the pattern bytes
+ *       ant           PREFIX with `*` or `?`, no `{` `}`, at most one `**` segment: the Ant matcher below
+ *       never         PREFIX without `*` and `?` (AntPathMatcher.isPattern is false: not even its own text matches),
+ *                     and REGEX with SG_GW_PRED_REGEX_INVALID (the reference aborts the definition's matcher at a
+ *                     Set-order-dependent point; here the predicate never matches and the others stay; §9)
+ *       host verdict  REGEX; PREFIX holding `{` or `}`; PREFIX with two or more `**` segments. The caller evaluates
+ *                     these (java.util.regex, Spring's AntPathMatcher) and hands the true ones over as verdict ids.
+ *     Verdict ids: the host-verdict predicates in the order of preds[] (every one, referenced or not) are 0, 1, …;
+ *     behind them come the kept gateway rules whose item has SG_GW_MATCH_REGEX, in the caller's rule order. Either
+ *     load renumbers them; sg_gateway_verdict_ids lists them. default_context is the context id API entries get.
+ *     A load replaces the definitions all or nothing: a resource >= n_resources, a predicate range outside preds or a
+ *     pattern range outside the blob is SG_E_INVAL and leaves the old definitions in force.
+ *   The Ant matcher (AntPathMatcher.doMatch(pattern, path, fullMatch = true) of Spring 5.3.18, default settings,
+ *     patterns with at most one `**` segment): pattern and path both start with `/` or both do not, else no match. Both
+ *     are split at `/`, empty tokens dropped, nothing trimmed, case-sensitive. Pattern segments before the `**` (all,
+ *     without one) match the leading path segments one by one; both exhausted together: pattern ends with `/` == path
+ *     ends with `/`; path exhausted first: a match iff the one remaining pattern segment is `*` and the path ends with
+ *     `/`, or every remaining segment is `**`; pattern exhausted first: no match. Segments after the `**` match the
+ *     trailing path segments from the back; at the last pattern segment, pattern ends with `/` != path ends with `/` is
+ *     no match; when either side runs out, a match iff only `**` is left. Within a segment `?` is one UTF-8 sequence
+ *     (its length from the lead byte, cut at the segment's end; any other byte counts as one), `*` any run, `a**b` is
+ *     `a*b`, everything else literal bytes.
+ *   sg_gateway_verdict_ids  kind_out[i] 0: index_out[i] is a preds[] index; 1: a gateway rule index. A cap too small:
+ *     SG_E_CAPACITY with *n set. Null outputs with cap 0 ask for the count.
+ *   sg_gateway_set_item_fields  field_id[i] = the caller's id of gateway rule i's fieldName (read for HEADER, URL_PARAM
+ *     and COOKIE items); n must be the rule count of the last sg_gateway_load_rules (else SG_E_INVAL), which drops them.
+ *   sg_gateway_expand_batch  n HTTP requests → entries; every pointer but h, n_req and n_items is a DEVICE pointer.
+ *     A request's path is bytes [path_off, + path_len) of `bytes`, its fields (what the RequestItemParser can read:
+ *     kind SG_GW_PARSE_*, name_id for kinds 2-4) are fields[field_begin, + field_count), and verdicts[verdict_begin,
+ *     + verdict_count) holds the verdict ids that are true for it, ascending and unique. Entries come in request order:
+ *     the route entry first (route != SG_GW_NO_ROUTE; resource_mode 0, the request's origin and context), then one per
+ *     matching API by ascending caller index of its definition (resource_mode 1, origin 0, the default context; the
+ *     reference's order is a HashSet's, §9). Per entry: req_out (item_count = the resource's item-rule count, items at
+ *     items_out[item_begin ..]), src_out (the request index), ev_out (ts_ms, create_ts 0, count 1, SG_LOCAL_ENTRY) and
+ *     ext_out.context (the arg fields are left for the parser). Item k is the request's first field with kind == the
+ *     rule's parse strategy and, for kinds 2-4, name_id == the rule's field id; SG_GW_ITEM_NULL without one, for a
+ *     strategy outside 0-4 and while no fields are set; SG_GW_ITEM_REGEX_MATCH when the rule's verdict id is listed.
+ *     Every entry of a request is written; what the adapter does after a request's first blocked entry (the later
+ *     transformers are not subscribed) stays with the caller. The call runs on `stream` and returns after it
+ *     completed. All or nothing: a field, path or verdict range out of bounds, a verdict slice not ascending, a verdict
+ *     id out of range, `bytes` not 4-byte aligned (SG_E_INVAL); n above max_batch, req_cap or items_cap too small
+ *     (SG_E_CAPACITY, *n_req / *n_items set), a batch that expands to 2^32 entries or items, or more (SG_E_CAPACITY). SG_E_INVAL
+ *     before sg_gateway_load_apis and sg_gateway_load_rules both succeeded. */
+#define SG_GW_URL_MATCH_EXACT   0
+#define SG_GW_URL_MATCH_PREFIX  1
+#define SG_GW_URL_MATCH_REGEX   2
+#define SG_GW_API_NAME_BLANK      1u  /* StringUtil.isBlank(apiName)                              */
+#define SG_GW_API_PREDS_NULL      2u  /* getPredicateItems() == null                              */
+#define SG_GW_PRED_PATTERN_NULL   1u  /* pattern == null                                          */
+#define SG_GW_PRED_NOT_PATH       2u  /* not an ApiPathPredicateItem                              */
+#define SG_GW_PRED_REGEX_INVALID  4u  /* Pattern.compile threw                                    */
+#define SG_GW_NO_ROUTE  0xFFFFFFFFu   /* exchange has no GATEWAY_ROUTE_ATTR                       */
+typedef struct sg_gateway_api {
+    uint32_t resource;
+    uint32_t pred_begin;
+    uint32_t pred_count;
+    uint32_t flags;                    /* SG_GW_API_*                                             */
+} sg_gateway_api;                      /* 16 bytes */
+typedef struct sg_gateway_api_pred {
+    int32_t  match_strategy;           /* SG_GW_URL_MATCH_*; any other value is exact             */
+    uint32_t flags;                    /* SG_GW_PRED_*                                            */
+    uint32_t pattern_off;
+    uint32_t pattern_len;
+} sg_gateway_api_pred;                 /* 16 bytes */
+typedef struct sg_gateway_http_req {
+    int64_t  ts_ms;
+    uint32_t route;                    /* resource index of the route id, or SG_GW_NO_ROUTE       */
+    int32_t  origin;                   /* the route entry's sg_local_event.origin                 */
+    uint32_t context;                  /* the route entry's sg_slot_ext.context                   */
+    uint32_t path_off;
+    uint32_t path_len;
+    uint32_t field_begin;
+    uint32_t field_count;
+    uint32_t verdict_begin;
+    uint32_t verdict_count;
+    uint32_t reserved;
+} sg_gateway_http_req;                 /* 48 bytes */
+typedef struct sg_gateway_field {
+    uint32_t kind;                     /* SG_GW_PARSE_*                                           */
+    uint32_t name_id;                  /* kinds 2-4: the caller's id of the header / parameter / cookie name */
+    uint32_t off;
+    uint32_t len;
+} sg_gateway_field;                    /* 16 bytes */
+int sg_gateway_load_apis(sg_handle* h, const sg_gateway_api* apis, uint32_t n_apis, const sg_gateway_api_pred* preds,
+                         uint32_t n_preds, const uint8_t* pattern_bytes, uint64_t n_pattern_bytes, uint32_t n_resources,
+                         uint32_t default_context);
+int sg_gateway_verdict_ids(sg_handle* h, uint8_t* kind_out, uint32_t* index_out, uint32_t cap, uint32_t* n);
+int sg_gateway_set_item_fields(sg_handle* h, const uint32_t* field_id, uint32_t n);
+int sg_gateway_expand_batch(sg_handle* h, const sg_gateway_http_req* req, uint64_t n, const sg_gateway_field* fields,
+                            uint64_t n_fields, const uint32_t* verdicts, uint64_t n_verdicts, const uint8_t* bytes,
+                            uint64_t n_bytes, sg_gateway_req* req_out, uint64_t req_cap, sg_gateway_item* items_out,
+                            uint64_t items_cap, uint32_t* src_out, sg_local_event* ev_out, sg_slot_ext* ext_out,
+                            uint64_t* n_req, uint64_t* n_items, void* stream);
 
 /* ---------- Envoy rate-limit service ----------
  * SentinelEnvoyRlsServiceImpl.shouldRateLimit (sentinel-cluster/sentinel-cluster-server-envoy-rls/.../service/v3/

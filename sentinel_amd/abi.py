@@ -206,6 +206,23 @@ GW_MATCH_EXACT, GW_MATCH_PREFIX, GW_MATCH_REGEX, GW_MATCH_CONTAINS = range(4)
 GW_ITEM_NULL, GW_ITEM_REGEX_MATCH = 1, 2
 GW_NM_THRESHOLD = 10_000_000
 GW_RESOURCE_MODE_ROUTE_ID, GW_RESOURCE_MODE_CUSTOM_API_NAME = 0, 1
+# Gateway API definitions and request expansion (sg_gateway_load_apis / sg_gateway_expand_batch): an ApiDefinition, one
+# of its predicates, an HTTP request, one field the RequestItemParser can read
+GATEWAY_API_DTYPE = np.dtype([("resource", "<u4"), ("pred_begin", "<u4"), ("pred_count", "<u4"), ("flags", "<u4")],
+                             align=True)
+GATEWAY_API_PRED_DTYPE = np.dtype([("match_strategy", "<i4"), ("flags", "<u4"), ("pattern_off", "<u4"),
+                                   ("pattern_len", "<u4")], align=True)
+GATEWAY_HTTP_REQ_DTYPE = np.dtype([("ts_ms", "<i8"), ("route", "<u4"), ("origin", "<i4"), ("context", "<u4"),
+                                   ("path_off", "<u4"), ("path_len", "<u4"), ("field_begin", "<u4"),
+                                   ("field_count", "<u4"), ("verdict_begin", "<u4"), ("verdict_count", "<u4"),
+                                   ("reserved", "<u4")], align=True)
+GATEWAY_FIELD_DTYPE = np.dtype([("kind", "<u4"), ("name_id", "<u4"), ("off", "<u4"), ("len", "<u4")], align=True)
+assert GATEWAY_API_DTYPE.itemsize == 16 and GATEWAY_API_PRED_DTYPE.itemsize == 16
+assert GATEWAY_HTTP_REQ_DTYPE.itemsize == 48 and GATEWAY_FIELD_DTYPE.itemsize == 16
+GW_URL_MATCH_EXACT, GW_URL_MATCH_PREFIX, GW_URL_MATCH_REGEX = range(3)
+GW_API_NAME_BLANK, GW_API_PREDS_NULL = 1, 2
+GW_PRED_PATTERN_NULL, GW_PRED_NOT_PATH, GW_PRED_REGEX_INVALID = 1, 2, 4
+GW_NO_ROUTE = 0xFFFFFFFF
 CONTROL_DEFAULT, CONTROL_WARM_UP, CONTROL_RATE_LIMITER, CONTROL_WARM_UP_RATE_LIMITER = 0, 1, 2, 3
 LIMIT_APP_DEFAULT, LIMIT_APP_OTHER = 0, -1
 STRATEGY_DIRECT, STRATEGY_RELATE, STRATEGY_CHAIN = 0, 1, 2

@@ -215,6 +215,25 @@ struct sg_handle {
         DevBuf<uint32_t> err;                 // [1]
     } gw;
 
+    // Gateway API definitions and the expansion's view of the gateway rules (gateway_api.h, gateway_api.hip)
+    struct GatewayApi {
+        bool on = false;
+        GwaTables t;                          // host copy: sg_gateway_verdict_ids
+        uint32_t default_context = 0;
+        DevBuf<GwaSlot> exact, bucket;
+        DevBuf<uint32_t> exact_list, vid_begin, vid_apis, api_res;
+        DevBuf<GwaPred> ant, wild;
+        DevBuf<uint8_t> patterns;
+        // per item rule of gw.conv.items, rebuilt by either load (the verdict ids) and sg_gateway_set_item_fields
+        std::vector<uint32_t> item_source;    // the gateway rule behind it
+        std::vector<uint32_t> vid_rule;       // verdict id - n API verdict ids → gateway rule index
+        uint32_t n_rules = 0;                 // the rule count of the last sg_gateway_load_rules
+        bool fields_set = false;
+        DevBuf<uint32_t> item_field, item_vid;
+        DevBuf<uint64_t> cnt, sums;           // batch scratch, grown on demand: 2 x [n + 1], the scan's workspace
+        DevBuf<uint32_t> err;                 // [1]
+    } gwa;
+
     // local slot chain
     sg_local_config lcfg{2, 1000, 500, 0};
     std::vector<LRule> ltab;          // [K] the resources (sg_local_load_rules), origin nodes not included
@@ -580,6 +599,26 @@ int flow_seg_alloc(sg_handle* h, DevBuf<uint32_t>& seg, uint32_t K) {
     if (!seg.alloc(2 * cap)) return fail(h, SG_E_NOMEM, "segment marks");
     HIP_TRY(h, hipMemset(seg, 0, sizeof(uint32_t) * cap));
     HIP_TRY(h, hipMemset(seg + cap, 0xFF, sizeof(uint32_t) * cap));
+    return SG_OK;
+}
+
+// A device copy of v (one element at least, so that no table pointer is null).
+template <class T>
+static bool gwa_upload(DevBuf<T>& d, const std::vector<T>& v) {
+    if (!d.alloc(v.empty() ? 1 : v.size())) return false;
+    return v.empty() || hipMemcpy(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// The gateway rules' verdict ids behind those of the API predicates: after either load. The rules' tables are in
+// force by then; a failure here leaves the expansion refusing (fields unset, no ids) until the next load.
+static int gwa_renumber(sg_handle* h) {
+    auto& a = h->gwa;
+    if (!h->gw.on) return SG_OK;
+    const std::vector<uint32_t> vid =
+        gwa_item_vids(h->gw.conv, a.item_source, a.on ? (uint32_t)a.t.vid_pred.size() : 0u, a.vid_rule);
+    if (!gwa_upload(a.item_vid, vid)) return fail(h, SG_E_NOMEM, "gateway verdict ids");
+    if (!a.fields_set && !gwa_upload(a.item_field, std::vector<uint32_t>(vid.size(), 0u)))
+        return fail(h, SG_E_NOMEM, "gateway item fields");
     return SG_OK;
 }
 
@@ -1420,7 +1459,10 @@ int sg_gateway_load_rules(sg_handle* h, const sg_gateway_rule* rules, uint32_t n
     g.patterns = std::move(d_pat);
     g.err = std::move(d_err);
     g.on = true;
-    return SG_OK;
+    h->gwa.n_rules = n;
+    h->gwa.fields_set = false;  // the field ids belonged to the rules before
+    h->gwa.item_source = gwa_item_sources(g.conv);
+    return gwa_renumber(h);
 }
 
 int sg_gateway_converted(sg_handle* h, sg_pslot_rule* rules_out, uint32_t cap, uint32_t* n_rules,
@@ -1517,6 +1559,162 @@ int sg_gateway_parse_batch(sg_handle* h, const sg_gateway_req* req, uint64_t n, 
         if (frc) return frc;
     }
     HIP_TRY(h, launch_gw_emit(g, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return SG_OK;
+}
+
+// ------------------------------------------------- Gateway API definitions and request expansion (gateway_api.hip)
+
+int sg_gateway_load_apis(sg_handle* h, const sg_gateway_api* apis, uint32_t n_apis, const sg_gateway_api_pred* preds,
+                         uint32_t n_preds, const uint8_t* pattern_bytes, uint64_t n_pattern_bytes, uint32_t n_resources,
+                         uint32_t default_context) {
+    if (!h) return SG_E_INVAL;
+    if ((n_apis && !apis) || (n_preds && !preds) || (n_pattern_bytes && !pattern_bytes))
+        return fail(h, SG_E_INVAL, "null buffer");
+    if (n_pattern_bytes >= (1ull << 32)) return fail(h, SG_E_INVAL, "pattern blob of 4 GiB or more");
+    if (!gwa_ranges_ok(apis, n_apis, preds, n_preds, n_pattern_bytes, n_resources))
+        return fail(h, SG_E_INVAL, "API definition: resource >= n_resources, predicates outside preds or pattern outside the blob");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    static const uint8_t none = 0;
+    GwaTables t = gwa_build(apis, n_apis, preds, n_preds, pattern_bytes ? pattern_bytes : &none);
+    sg_handle::GatewayApi d;  // the new tables, moved in only when all of them are up
+    const std::vector<uint8_t> blob(pattern_bytes, pattern_bytes + n_pattern_bytes);
+    if (!gwa_upload(d.exact, t.exact) || !gwa_upload(d.bucket, t.bucket) || !gwa_upload(d.exact_list, t.exact_list) ||
+        !gwa_upload(d.vid_begin, t.vid_begin) || !gwa_upload(d.vid_apis, t.vid_apis) || !gwa_upload(d.api_res, t.api_res) ||
+        !gwa_upload(d.ant, t.ant) || !gwa_upload(d.wild, t.wild) || !gwa_upload(d.patterns, blob) || !d.err.alloc(1))
+        return fail(h, SG_E_NOMEM, "API definition tables");
+    auto& a = h->gwa;
+    a.t = std::move(t);
+    a.default_context = default_context;
+    a.exact = std::move(d.exact);
+    a.bucket = std::move(d.bucket);
+    a.exact_list = std::move(d.exact_list);
+    a.vid_begin = std::move(d.vid_begin);
+    a.vid_apis = std::move(d.vid_apis);
+    a.api_res = std::move(d.api_res);
+    a.ant = std::move(d.ant);
+    a.wild = std::move(d.wild);
+    a.patterns = std::move(d.patterns);
+    a.err = std::move(d.err);
+    a.on = true;
+    return gwa_renumber(h);
+}
+
+int sg_gateway_verdict_ids(sg_handle* h, uint8_t* kind_out, uint32_t* index_out, uint32_t cap, uint32_t* n) {
+    if (!h) return SG_E_INVAL;
+    if (!n) return fail(h, SG_E_INVAL, "null buffer");
+    const auto& a = h->gwa;
+    const size_t n_api = a.on ? a.t.vid_pred.size() : 0, n_rule = h->gw.on ? a.vid_rule.size() : 0;
+    *n = (uint32_t)(n_api + n_rule);
+    if (n_api + n_rule > cap) return fail(h, SG_E_CAPACITY, "verdict id buffers too small");
+    if ((n_api + n_rule) && (!kind_out || !index_out)) return fail(h, SG_E_INVAL, "null buffer");
+    for (size_t i = 0; i < n_api + n_rule; ++i) {
+        kind_out[i] = i < n_api ? 0 : 1;
+        index_out[i] = i < n_api ? a.t.vid_pred[i] : a.vid_rule[i - n_api];
+    }
+    return SG_OK;
+}
+
+int sg_gateway_set_item_fields(sg_handle* h, const uint32_t* field_id, uint32_t n) {
+    if (!h) return SG_E_INVAL;
+    if (!h->gw.on) return fail(h, SG_E_INVAL, "sg_gateway_load_rules first");
+    auto& a = h->gwa;
+    if (n != a.n_rules) return fail(h, SG_E_INVAL, "n differs from the rule count of the last sg_gateway_load_rules");
+    if (n && !field_id) return fail(h, SG_E_INVAL, "null buffer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    std::vector<uint32_t> f(a.item_source.size());
+    for (size_t j = 0; j < f.size(); ++j) f[j] = field_id[a.item_source[j]];
+    DevBuf<uint32_t> d;
+    if (!gwa_upload(d, f)) return fail(h, SG_E_NOMEM, "gateway item fields");
+    a.item_field = std::move(d);
+    a.fields_set = true;
+    return SG_OK;
+}
+
+int sg_gateway_expand_batch(sg_handle* h, const sg_gateway_http_req* req, uint64_t n, const sg_gateway_field* fields,
+                            uint64_t n_fields, const uint32_t* verdicts, uint64_t n_verdicts, const uint8_t* bytes,
+                            uint64_t n_bytes, sg_gateway_req* req_out, uint64_t req_cap, sg_gateway_item* items_out,
+                            uint64_t items_cap, uint32_t* src_out, sg_local_event* ev_out, sg_slot_ext* ext_out,
+                            uint64_t* n_req, uint64_t* n_items, void* stream) {
+    if (!h) return SG_E_INVAL;
+    if (!n_req || !n_items) return fail(h, SG_E_INVAL, "null buffer");
+    *n_req = 0;
+    *n_items = 0;
+    auto& a = h->gwa;
+    auto& gw = h->gw;
+    if (!a.on || !gw.on) return fail(h, SG_E_INVAL, "sg_gateway_load_apis and sg_gateway_load_rules first");
+    if (a.item_vid.size() < std::max<size_t>(gw.conv.items.size(), 1) || a.item_field.size() < std::max<size_t>(gw.conv.items.size(), 1))
+        return fail(h, SG_E_INVAL, "the gateway rules' verdict ids are not in place: load again");
+    if (n == 0) return SG_OK;
+    if (!req || (n_fields && !fields) || (n_verdicts && !verdicts) || (n_bytes && !bytes) ||
+        (req_cap && (!req_out || !src_out || !ev_out || !ext_out)) || (items_cap && !items_out))
+        return fail(h, SG_E_INVAL, "null buffer");
+    if (((uintptr_t)bytes & 3u) != 0) return fail(h, SG_E_INVAL, "bytes must be 4-byte aligned");
+    if (n_fields >= (1ull << 32) || n_verdicts >= (1ull << 32) || n_bytes >= (1ull << 32))
+        return fail(h, SG_E_INVAL, "2^32 fields, verdicts or bytes, or more");
+    if (n > h->cfg.max_batch) return fail(h, SG_E_CAPACITY, "batch larger than max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!a.cnt.reserve(2 * (n + 1)) || !a.sums.reserve(scan_blocks(n + 1) + 4)) return fail(h, SG_E_NOMEM, "gateway batch buffers");
+    GwxArgs g{};
+    g.n = n;
+    g.req = req;
+    g.fields = fields;
+    g.n_fields = n_fields;
+    g.verdicts = verdicts;
+    g.n_verdicts = n_verdicts;
+    g.bytes = bytes;
+    g.n_bytes = n_bytes;
+    g.exact = a.exact;
+    g.exact_list = a.exact_list;
+    g.bucket = a.bucket;
+    g.ant = a.ant;
+    g.wild = a.wild;
+    g.vid_begin = a.vid_begin;
+    g.vid_apis = a.vid_apis;
+    g.api_res = a.api_res;
+    g.patterns = a.patterns;
+    g.exact_mask = (uint32_t)a.t.exact.size() - 1;
+    g.bucket_mask = (uint32_t)a.t.bucket.size() - 1;
+    g.n_wild = (uint32_t)a.t.wild.size();
+    g.n_api_vids = (uint32_t)a.t.vid_pred.size();
+    g.n_vids = g.n_api_vids + (uint32_t)a.vid_rule.size();
+    g.default_context = a.default_context;
+    g.res = gw.res;
+    g.rules = gw.rules;
+    g.item_field = a.item_field;
+    g.item_vid = a.item_vid;
+    g.n_resources = (uint32_t)gw.conv.res.size();
+    g.fields_set = a.fields_set ? 1u : 0u;
+    g.cnt = a.cnt;
+    g.cnt_items = a.cnt + (n + 1);
+    g.err = a.err;
+    g.req_out = req_out;
+    g.items_out = items_out;
+    g.src_out = src_out;
+    g.ev_out = ev_out;
+    g.ext_out = ext_out;
+    uint64_t* d_total = a.sums + scan_blocks(n + 1) + 1;  // [2] behind the scan's workspace: entries, items
+    HIP_TRY(h, hipMemsetAsync(a.err, 0, 4, st));
+    HIP_TRY(h, launch_gwx_count(g, st));
+    HIP_TRY(h, launch_scan_u64(g.cnt, n + 1, a.sums, d_total, st));
+    HIP_TRY(h, launch_scan_u64(g.cnt_items, n + 1, a.sums, d_total + 1, st));
+    uint64_t total[2] = {0, 0};
+    uint32_t err = 0;
+    HIP_TRY(h, hipMemcpyAsync(total, d_total, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (err & kGwxErrRange) return fail(h, SG_E_INVAL, "a path, field or verdict range out of bounds");
+    if (err & kGwxErrVerdict) return fail(h, SG_E_INVAL, "a verdict slice not ascending, or a verdict id out of range");
+    const uint64_t ne = total[0], ni = total[1];
+    *n_req = ne;
+    *n_items = ni;
+    if (ne >= (1ull << 32) || ni >= (1ull << 32)) return fail(h, SG_E_CAPACITY, "the batch expands to 2^32 entries or items, or more");
+    if (ne > req_cap) return fail(h, SG_E_CAPACITY, "req_out too small");
+    if (ni > items_cap) return fail(h, SG_E_CAPACITY, "items_out too small");
+    if (ne) HIP_TRY(h, launch_gwx_emit(g, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     return SG_OK;
 }

@@ -9,6 +9,7 @@
 #include "../../include/sentinel_gpu.h"
 #include "authority_rules.h"
 #include "blocklog_rules.h"
+#include "gateway_api.h"
 #include "gateway_rules.h"
 #include "serverlog_rules.h"
 #include "system_rules.h"
@@ -1287,5 +1288,52 @@ struct GwArgs {
 hipError_t launch_gw_count(const GwArgs& g, hipStream_t stream);
 hipError_t launch_gw_match(const GwArgs& g, hipStream_t stream);
 hipError_t launch_gw_emit(const GwArgs& g, hipStream_t stream);
+
+// ---- Gateway API definitions: path matching and request expansion (gateway_api.hip; tables from gateway_api.h) ----
+
+constexpr uint32_t kGwxErrRange = 1;    // a path, field or verdict range out of bounds
+constexpr uint32_t kGwxErrVerdict = 2;  // a verdict slice not ascending, or an id out of range
+
+struct GwxArgs {
+    uint64_t n;                         // HTTP requests
+    const sg_gateway_http_req* req;
+    const sg_gateway_field* fields;
+    uint64_t n_fields;
+    const uint32_t* verdicts;
+    uint64_t n_verdicts;
+    const uint8_t* bytes;
+    uint64_t n_bytes;
+    // the definitions (GwaTables)
+    const GwaSlot* exact;
+    const uint32_t* exact_list;
+    const GwaSlot* bucket;
+    const GwaPred* ant;
+    const GwaPred* wild;
+    const uint32_t* vid_begin;          // [n_api_vids + 1]
+    const uint32_t* vid_apis;
+    const uint32_t* api_res;
+    const uint8_t* patterns;
+    uint32_t exact_mask, bucket_mask, n_wild;
+    uint32_t n_api_vids, n_vids;        // verdict ids of API predicates; of those and the gateway rules
+    uint32_t default_context;
+    // the gateway rules (GwConverted) and what sg_gateway_set_item_fields added
+    const GwRes* res;
+    const GwItemRule* rules;
+    const uint32_t* item_field;         // per item rule: the caller's field id
+    const uint32_t* item_vid;           // per item rule: its verdict id or kGwaNone
+    uint32_t n_resources;
+    uint32_t fields_set;
+    uint64_t* cnt;                      // [n + 1] entries per request, then their exclusive scan
+    uint64_t* cnt_items;                // [n + 1] the same for items
+    uint32_t* err;                      // kGwxErr* bits
+    sg_gateway_req* req_out;
+    sg_gateway_item* items_out;
+    uint32_t* src_out;
+    sg_local_event* ev_out;
+    sg_slot_ext* ext_out;
+};
+
+hipError_t launch_gwx_count(const GwxArgs& g, hipStream_t stream);
+hipError_t launch_gwx_emit(const GwxArgs& g, hipStream_t stream);
 
 }  // namespace sg

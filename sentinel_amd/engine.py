@@ -48,7 +48,8 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_local_block_log_enable", "sg_local_block_log", "sg_server_log_enable", "sg_server_log",
            "sg_node_server_log_enable", "sg_node_server_log", "sg_node_local_block_log_enable",
            "sg_node_local_block_log",
-           "sg_gateway_load_rules", "sg_gateway_converted", "sg_gateway_param_rule_count", "sg_gateway_parse_batch"]
+           "sg_gateway_load_rules", "sg_gateway_converted", "sg_gateway_param_rule_count", "sg_gateway_parse_batch",
+           "sg_gateway_load_apis", "sg_gateway_verdict_ids", "sg_gateway_set_item_fields", "sg_gateway_expand_batch"]
 
 _lib = None
 
@@ -147,6 +148,11 @@ def load_library():
         "sg_gateway_param_rule_count": (C.c_int, [vp, u32, C.POINTER(u32), C.POINTER(C.c_int32)]),
         "sg_gateway_parse_batch": (C.c_int, [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, C.POINTER(u64),
                                              C.POINTER(u64), vp]),
+        "sg_gateway_load_apis": (C.c_int, [vp, vp, u32, vp, u32, vp, u64, u32, u32]),
+        "sg_gateway_verdict_ids": (C.c_int, [vp, vp, vp, u32, C.POINTER(u32)]),
+        "sg_gateway_set_item_fields": (C.c_int, [vp, vp, u32]),
+        "sg_gateway_expand_batch": (C.c_int, [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp, vp,
+                                              C.POINTER(u64), C.POINTER(u64), vp]),
         "sg_pace_load_rules": (C.c_int, [vp, vp, u32]),
         "sg_pace_decide_batch": (C.c_int, [vp, vp, u64, vp, vp]),
         "sg_pace_decide_batch_host": (C.c_int, [vp, vp, u64, vp]),
@@ -871,6 +877,99 @@ class FlowEngine:
         if with_device:
             return args, values, ext_out, pev_out, {"args": a_t, "values": v_t, "ext": e_t, "pev": p_t}
         return args, values, ext_out, pev_out
+
+    # ---- Gateway API definitions and request expansion (sg_gateway_load_apis / sg_gateway_expand_batch)
+    def gateway_load_apis(self, apis, preds, patterns=b"", n_resources=None, default_context=0):
+        """GatewayApiDefinitionManager.loadApiDefinitions: abi.GATEWAY_API_DTYPE definitions over
+        abi.GATEWAY_API_PRED_DTYPE predicates whose pattern ranges index `patterns`. default_context: the context id
+        API entries get."""
+        apis = np.ascontiguousarray(apis, dtype=abi.GATEWAY_API_DTYPE).reshape(-1)
+        preds = np.ascontiguousarray(preds, dtype=abi.GATEWAY_API_PRED_DTYPE).reshape(-1)
+        pat = np.frombuffer(bytes(patterns), np.uint8).copy()
+        n_res = (int(apis["resource"].max()) + 1 if len(apis) else 1) if n_resources is None else n_resources
+        self._check(self._L.sg_gateway_load_apis(self.h, abi.ptr(apis) if len(apis) else None, len(apis),
+                                                 abi.ptr(preds) if len(preds) else None, len(preds),
+                                                 abi.ptr(pat) if len(pat) else None, len(pat), n_res, default_context))
+
+    def gateway_verdict_ids(self):
+        """[(kind, index)] by verdict id: kind 0 = an API predicate index, 1 = a gateway rule index."""
+        n = C.c_uint32()
+        rc = self._L.sg_gateway_verdict_ids(self.h, None, None, 0, C.byref(n))
+        if rc not in (0, abi.SG_E_CAPACITY):
+            self._check(rc)
+        kind, index = np.zeros(max(n.value, 1), np.uint8), np.zeros(max(n.value, 1), np.uint32)
+        self._check(self._L.sg_gateway_verdict_ids(self.h, abi.ptr(kind), abi.ptr(index), n.value, C.byref(n)))
+        return [(int(k), int(i)) for k, i in zip(kind[:n.value], index[:n.value])]
+
+    def gateway_set_item_fields(self, field_id):
+        """field_id[i] = the caller's id of gateway rule i's fieldName, for every rule of the last gateway_load_rules."""
+        f = np.ascontiguousarray(field_id, dtype=np.uint32).reshape(-1)
+        self._check(self._L.sg_gateway_set_item_fields(self.h, abi.ptr(f) if len(f) else None, len(f)))
+
+    def gateway_expand_device(self, req_ptr: int, n: int, fields_ptr: int, n_fields: int, verdicts_ptr: int,
+                              n_verdicts: int, bytes_ptr: int, n_bytes: int, req_out_ptr: int, req_cap: int,
+                              items_out_ptr: int, items_cap: int, src_out_ptr: int, ev_out_ptr: int, ext_out_ptr: int,
+                              stream_ptr: int = 0):
+        """Device addresses: sg_gateway_http_req[n], sg_gateway_field[n_fields], u32 verdict ids, the bytes →
+        sg_gateway_req / u32 source / sg_local_event / sg_slot_ext [req_cap] and sg_gateway_item[items_cap]. Returns
+        (n_req, n_items) after the stream has completed; an EngineError carries them in .n_req / .n_items."""
+        nr, ni = C.c_uint64(), C.c_uint64()
+        rc = self._L.sg_gateway_expand_batch(self.h, C.c_void_p(req_ptr), n, C.c_void_p(fields_ptr), n_fields,
+                                             C.c_void_p(verdicts_ptr), n_verdicts, C.c_void_p(bytes_ptr), n_bytes,
+                                             C.c_void_p(req_out_ptr), req_cap, C.c_void_p(items_out_ptr), items_cap,
+                                             C.c_void_p(src_out_ptr), C.c_void_p(ev_out_ptr), C.c_void_p(ext_out_ptr),
+                                             C.byref(nr), C.byref(ni), C.c_void_p(stream_ptr))
+        if rc != 0:
+            e = EngineError(rc, self._L.sg_last_error(self.h).decode())
+            e.n_req, e.n_items = int(nr.value), int(ni.value)
+            raise e
+        return int(nr.value), int(ni.value)
+
+    def gateway_expand_host(self, req, fields, verdicts, data, req_cap, items_cap, fill=0, byte_shift=0,
+                            with_device=False):
+        """Testing aid: gateway_expand_device over host arrays staged through torch; the output buffers are filled
+        with `fill` first. byte_shift: `data` is placed that many bytes into its buffer (1-3: a misaligned blob).
+        Returns {"req", "items", "src", "ev", "ext"} cut to the counts and "raw": the whole buffers as bytes;
+        with_device adds "dev": the device tensors, "data" (the blob) among them."""
+        import torch
+        req = np.ascontiguousarray(req, dtype=abi.GATEWAY_HTTP_REQ_DTYPE).reshape(-1)
+        fields = np.ascontiguousarray(fields, dtype=abi.GATEWAY_FIELD_DTYPE).reshape(-1)
+        verdicts = np.ascontiguousarray(verdicts, dtype=np.uint32).reshape(-1)
+        data = np.frombuffer(bytes(data), np.uint8)
+
+        def dev(a, shift=0):
+            raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            t = torch.zeros(len(raw) + shift + 16, dtype=torch.uint8, device="cuda")
+            t[shift:shift + len(raw)] = torch.from_numpy(raw.copy())
+            return t
+
+        def out(count, size):
+            return torch.full((max(count, 1) * size,), fill, dtype=torch.uint8, device="cuda")
+
+        r_t, f_t, v_t, b_t = dev(req), dev(fields), dev(verdicts), dev(data, byte_shift)
+        sizes = {"req": 16, "items": 16, "src": 4, "ev": abi.LOCAL_EVENT_DTYPE.itemsize, "ext": 16}
+        o = {k: out(items_cap if k == "items" else req_cap, s) for k, s in sizes.items()}
+        try:
+            nr, ni = self.gateway_expand_device(r_t.data_ptr(), len(req), f_t.data_ptr(), len(fields), v_t.data_ptr(),
+                                                len(verdicts), b_t.data_ptr() + byte_shift, len(data),
+                                                o["req"].data_ptr(), req_cap, o["items"].data_ptr(), items_cap,
+                                                o["src"].data_ptr(), o["ev"].data_ptr(), o["ext"].data_ptr(),
+                                                torch.cuda.current_stream().cuda_stream)
+        except EngineError as e:
+            torch.cuda.synchronize()
+            e.raw = {k: t.cpu().numpy().tobytes() for k, t in o.items()}
+            raise
+        torch.cuda.synchronize()
+        raw = {k: t.cpu().numpy() for k, t in o.items()}
+        res = {"req": raw["req"].view(abi.GATEWAY_REQ_DTYPE)[:nr].copy(),
+               "items": raw["items"].view(abi.GATEWAY_ITEM_DTYPE)[:ni].copy(),
+               "src": raw["src"].view(np.uint32)[:nr].copy(),
+               "ev": raw["ev"].view(abi.LOCAL_EVENT_DTYPE)[:nr].copy(),
+               "ext": raw["ext"].view(abi.SLOT_EXT_DTYPE)[:nr].copy(),
+               "raw": {k: v.tobytes() for k, v in raw.items()}}
+        if with_device:
+            res["dev"] = dict(o, data=b_t)
+        return res
 
     def decide_host(self, req: np.ndarray) -> np.ndarray:
         req = np.ascontiguousarray(req, dtype=abi.REQ_DTYPE)
