@@ -1191,11 +1191,17 @@ __global__ void __launch_bounds__(256) k_cpfb_init(CPGroups g) {
 }
 
 // Every multi-value request pulls its items' labels (and the items those labels name) down to their minimum.
+// A request the limiter refused links nothing (k_cp_mlist lists it: k_cp_prep2 flags it before the limiter runs):
+// no walker counted its records, k_cp_combine and k_cpfb_entries skip it, and the lane walker saves a slot's ring
+// only for a counted multi-value record — so every item of a group of two or more, and every item k_cp_combine
+// flags, holds a save of this batch, and k_cpfb_restore copies nothing older.
 __global__ void __launch_bounds__(256) k_cpfb_hook(CPArgs c, CPBatch b, CPGroups g) {
     const uint32_t m = *b.mcount;
     bool moved = false;
     for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < m; x += gridDim.x * blockDim.x) {
-        const sg_cparam_req q = c.req[b.mlist[x]];
+        const uint32_t i = b.mlist[x];
+        if (b.lim && c.out[i].status == SG_STATUS_TOO_MANY_REQUEST) continue;
+        const sg_cparam_req q = c.req[i];
         uint32_t lo = 0xFFFFFFFFu;
         for (uint32_t j = 0; j < q.value_count; ++j) lo = min(lo, g.label[b.slot_item[b.pslot[q.value_begin + j]]]);
         for (uint32_t j = 0; j < q.value_count; ++j) {

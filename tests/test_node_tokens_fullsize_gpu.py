@@ -3,7 +3,10 @@
 node over 2 and 3 shards of this GPU — every TokenResult equal, batch after batch, and a sample of (rule, value)
 window sums equal; concurrent tokens at 4M acquires / releases per batch over 100k flow rules — every status equal
 and nowCalls equal for every rule. (The oracle replays the smaller cases in test_node_tokens_gpu.py; here the
-single handle, itself oracle-checked at these sizes by test_fullsize_gpu.py and the benches, is the reference.)"""
+single handle is the reference. What is compared is node against single handle, not against the oracle: the single
+handle's cluster param path is oracle-checked at batches of up to 50k requests only — test_cparam_gpu.py,
+test_cparam_edges_gpu.py — and test_fullsize_gpu.py replays cluster flow tokens and the local paths at full size,
+neither cluster param nor concurrent tokens.)"""
 import numpy as np
 import pytest
 

@@ -299,7 +299,7 @@ def _cp_sets(rng, lg, k=None, exclude=None, marker=True):
 @functools.lru_cache(maxsize=None)
 def _cp_full_case(lg, S):
     rng = np.random.default_rng(200 + 10 * lg + S)
-    rules = _cp_rules(rng.integers(20, 200, 3), S=S)
+    rules = _cp_rules(rng.integers(20, 200, 3), S=S, interval=1000 if 1000 % S == 0 else 100 * S)  # S = 16: 1600 ms
     sets = _cp_sets(rng, lg)
     assert 0 in sets[1] and all(MARKER in s for s in sets)
     known = [(r, v) for r in range(3) for v in sets[r]]
@@ -319,7 +319,7 @@ def _cp_full_case(lg, S):
 
 
 @pytest.mark.parametrize("flags", WALKERS)
-@pytest.mark.parametrize("S", [10, 1])
+@pytest.mark.parametrize("S", [10, 1, 16])
 @pytest.mark.parametrize("lg", [1, 2, 4])
 def test_cparam_tables_exactly_full(lg, S, flags, monkeypatch):
     """Case 4: three rules whose sub-tables are exactly full (the side slots in use, one rule's values homed at the
