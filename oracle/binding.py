@@ -676,6 +676,8 @@ class LocalChain:
 
     def __init__(self, sample_count=2, interval_ms=1000, occupy_timeout_ms=500, cold_factor=3):
         self.h = lib().or_local_new(sample_count, interval_ms, occupy_timeout_ms)
+        if not self.h:  # SampleCountProperty / IntervalProperty: intervalInMs % sampleCount != 0 and the like
+            raise ValueError(f"or_local_new({sample_count}, {interval_ms}, {occupy_timeout_ms}) refused")
         lib().or_local_set_cold_factor(self.h, cold_factor)
         self.S = sample_count
 

@@ -916,6 +916,9 @@ struct or_local {
 };
 
 or_local* or_local_new(int second_sample_count, int second_interval_ms, int occupy_timeout_ms) {
+    /* the nodes' second window is a LeapArray(sampleCount, intervalInMs): its constructor's asserts
+     * (base/LeapArray.java:61-72), here and not at the first node */
+    if (second_sample_count <= 0 || second_interval_ms <= 0 || second_interval_ms % second_sample_count != 0) return NULL;
     or_local* l = (or_local*)calloc(1, sizeof(or_local));
     l->S = second_sample_count;            /* SampleCountProperty.SAMPLE_COUNT, default 2   */
     l->interval = second_interval_ms;      /* IntervalProperty.INTERVAL, default 1000        */

@@ -56,7 +56,7 @@ def _rule_set(rng, r, n_origins):
     return []                                                                              # no flow rule
 
 
-def _setup(n_res, rng, n_origins, breakers=False, S=2, interval=1000, flags=0, rule_sets=None):
+def _setup(n_res, rng, n_origins, breakers=False, S=2, interval=1000, flags=0, rule_sets=None, cold_factor=3):
     base = np.zeros(n_res, abi.LOCAL_RULE_DTYPE)
     for r in range(n_res):
         brk = [degrade_rule(abi.DEGRADE_EXCEPTION_RATIO, 0.3, 1, 5, 1000)] if breakers and r % 3 == 0 else []
@@ -66,11 +66,11 @@ def _setup(n_res, rng, n_origins, breakers=False, S=2, interval=1000, flags=0, r
     flat = [x for rs in rule_sets for x in rs]
     rng.shuffle(flat)
     frules = np.array(flat, abi.LOCAL_FLOW_RULE_DTYPE) if flat else np.zeros(0, abi.LOCAL_FLOW_RULE_DTYPE)
-    ora = LocalChain(S, interval, 500)
+    ora = LocalChain(S, interval, 500, cold_factor=cold_factor)
     ora.load_rules(base)
     kept = ora.load_flow_rules(frules, n_origins)
     eng = _engine(flags)
-    eng.local_load_rules(base, S, interval, 500)
+    eng.local_load_rules(base, S, interval, 500, cold_factor=cold_factor)
     assert eng.local_load_flow_rules(frules, n_origins) == kept
     return ora, eng, frules
 
@@ -140,11 +140,17 @@ def _run(ora, eng, frules, n_res, n_origins, batches, seed, rt_hi=40, err=0.05, 
 
 @pytest.mark.parametrize("flags", WALKERS)
 @pytest.mark.parametrize("seed", [1, 2])
-def test_mixed_rule_sets(flags, seed):
+def test_mixed_rule_sets(flags, seed, cold_factor=3):
     rng = np.random.default_rng(seed)
     n_res, n_origins = 40, 4
-    ora, eng, fr = _setup(n_res, rng, n_origins, breakers=True, flags=flags)
+    ora, eng, fr = _setup(n_res, rng, n_origins, breakers=True, flags=flags, cold_factor=cold_factor)
     _run(ora, eng, fr, n_res, n_origins, [(20_000, 3000), (20_000, 4000), (10_000, 2500)], seed, zipf=0.9)
+
+
+def test_mixed_rule_sets_cold_factor_5():
+    """The same with ColdFactorProperty.coldFactor 5 on both sides: the origin WarmUp rules of shape 7 among them,
+    which read an origin node's previousPassQps and never go dead."""
+    test_mixed_rule_sets(0, 1, cold_factor=5)
 
 
 @pytest.mark.parametrize("behavior", [WU, WRL])

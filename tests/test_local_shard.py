@@ -57,13 +57,13 @@ def node_setup(seed=3):
     return base, frules, relate, inbound
 
 
-def node_trace(base, frules, inbound, n_batches=3, n=6000, seed=4):
+def node_trace(base, frules, inbound, n_batches=3, n=6000, seed=4, cold_factor=3):
     """Batches of (events, results) of one sequential node replay (entries + the exits of passed entries), and the
     node's metric rows fetched after each batch at its end (the single-chain reference)."""
     from oracle.binding import LocalChain, LocalTraceGen
     from sentinel_amd.workload import zipf_keys
     rng = np.random.default_rng(seed)
-    ora = LocalChain(2, 1000, 500)
+    ora = LocalChain(2, 1000, 500, cold_factor=cold_factor)
     ora.load_rules(base)
     ora.load_flow_rules(frules, N_ORIGINS, 0)
     ora.set_entry_types(inbound)

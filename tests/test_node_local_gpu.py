@@ -30,10 +30,10 @@ def _node_case():
     return base, frules, relate, inbound, trace
 
 
-def _node(G, base, frules, inbound, flow_rules=True):
+def _node(G, base, frules, inbound, flow_rules=True, cold_factor=3):
     from sentinel_amd.engine import NodeEngine
     nd = NodeEngine([0] * G, max_batch=MAX_BATCH)
-    nd.local_load_rules(base, 2, 1000, 500)
+    nd.local_load_rules(base, 2, 1000, 500, cold_factor=cold_factor)
     if flow_rules:
         nd.local_load_flow_rules(frules, N_ORIGINS, 0)
     nd.local_set_entry_types(inbound)
@@ -108,6 +108,39 @@ def test_node_equals_node_replay(G, device):
     assert statuses == {abi.LOCAL_PASS, abi.LOCAL_BLOCK_FLOW, abi.LOCAL_BLOCK_DEGRADE, abi.LOCAL_PASS_WAIT}
     assert len(np.unique(trace[1][3]["timestamp"])) == 2
     for r in (0, 3, 10, 21, 47):
+        for a, w in zip(nd.local_state(r), one.local_state(r)):
+            assert np.array_equal(a, w), f"resource {r}: state differs from one handle's"
+
+
+def test_node_cold_factor_5():
+    """sg_local_config.cold_factor reaches every shard: the node's trace replayed by the oracle with
+    ColdFactorProperty.coldFactor 5 (other decisions than with 3), on two shards and on one handle."""
+    from oracle.binding import LocalChain
+    from sentinel_amd.engine import FlowEngine
+    base, frules, relate, inbound, trace3 = _node_case()
+    trace = node_trace(base, frules, inbound, cold_factor=5)
+    assert any(not np.array_equal(a[1], b[1]) for a, b in zip(trace, trace3)), "the cold factor decides nothing here"
+    nd = _node(2, base, frules, inbound, cold_factor=5)
+    one = FlowEngine(device=0, max_batch=MAX_BATCH)
+    one.local_load_rules(base, 2, 1000, 500, cold_factor=5)
+    one.local_load_flow_rules(frules, N_ORIGINS, 0)
+    one.local_set_entry_types(inbound)
+    for b, (ev, want, now, rows_want) in enumerate(trace):
+        assert np.array_equal(nd.local_decide_host(ev), want), f"batch {b}: the node's results differ"
+        assert np.array_equal(one.local_decide_host(ev), want), f"batch {b}: one handle's results differ"
+        assert np.array_equal(nd.local_metrics(now), rows_want) and np.array_equal(one.local_metrics(now), rows_want)
+    ora = LocalChain(2, 1000, 500, cold_factor=5)   # the controllers after the last batch: the replay once more
+    ora.load_rules(base)
+    ora.load_flow_rules(frules, N_ORIGINS, 0)
+    ora.set_entry_types(inbound)
+    for ev, want, _, _ in trace:
+        assert np.array_equal(ora.decide(ev), want)
+    warm = np.nonzero(frules["control_behavior"] == abi.CONTROL_WARM_UP)[0]
+    assert len(warm) == N_RES // 6
+    for i in warm:
+        assert np.array_equal(nd.local_controller(i), ora.controller(i)), f"rule {i}: the node's controller"
+        assert np.array_equal(one.local_controller(i), ora.controller(i)), f"rule {i}: one handle's controller"
+    for r in range(2, N_RES, 6):
         for a, w in zip(nd.local_state(r), one.local_state(r)):
             assert np.array_equal(a, w), f"resource {r}: state differs from one handle's"
 
