@@ -317,7 +317,11 @@ int sg_conc_read_state(sg_handle* h, uint32_t key, int32_t* now_calls, uint64_t*
 
 /* ---- local slot chain: StatisticSlot → FlowSlot (DefaultController) → DegradeSlot (circuit breakers) ---- */
 
-/* DegradeRule (sentinel-core/.../slots/block/degrade/DegradeRule.java). */
+/* DegradeRule (sentinel-core/.../slots/block/degrade/DegradeRule.java). A rule that DegradeRuleManager.isValidRule
+ * (DegradeRuleManager.java:183-202) drops must not be sent: sg_local_load_rules refuses the whole load with
+ * SG_E_INVAL ("invalid degrade rule") for a grade outside SG_DEGRADE_*, count < 0 or NaN, time_window_sec <= 0,
+ * min_request_amount <= 0, stat_interval_ms <= 0, an RT slow_ratio_threshold outside [0, 1] (NaN included) or an
+ * exception ratio count > 1. The bounds themselves are valid (window 1, amount 1, ratios 0.0 and 1.0). */
 #define SG_DEGRADE_RT              0
 #define SG_DEGRADE_EXCEPTION_RATIO 1
 #define SG_DEGRADE_EXCEPTION_COUNT 2
@@ -692,6 +696,9 @@ int sg_cparam_table_used(sg_handle* h, uint32_t rule, uint64_t* used, uint64_t* 
  *   sg_local_load_rules    ← FlowRuleManager.loadRules + DegradeRuleManager.loadRules for one resource each
  *                            (one DefaultController QPS/thread rule per resource, limitApp "default",
  *                            DIRECT strategy; up to two circuit breakers), with fresh StatisticNodes.
+ *                            A degrade rule that isValidRule drops (see sg_degrade_rule) is refused with
+ *                            SG_E_INVAL and the rules loaded before stay in force: the caller filters, as
+ *                            DegradeRuleManager does, before it sends.
  *   sg_local_decide_batch  ← SphU.entry(resource, count, prioritized) → StatisticSlot.entry around
  *                            FlowSlot.checkFlow (DefaultController.canPass, DefaultController.java:49-76) and
  *                            DegradeSlot.performChecking (DegradeSlot.java:43-81); Entry.exit() →

@@ -3639,9 +3639,13 @@ int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local
             b.stat_ms = 1;
             if (j >= r.n_breakers) continue;
             const sg_degrade_rule& d = r.breakers[j];
-            if (d.grade < SG_DEGRADE_RT || d.grade > SG_DEGRADE_EXCEPTION_COUNT || d.stat_interval_ms <= 0 ||
-                !(d.count >= 0))
-                return fail(h, SG_E_INVAL, "invalid degrade rule");
+            // DegradeRuleManager.isValidRule (:183-202): what it drops is refused here, the rules in force stay
+            bool valid = d.grade >= SG_DEGRADE_RT && d.grade <= SG_DEGRADE_EXCEPTION_COUNT && d.count >= 0 &&
+                         d.time_window_sec > 0 && d.min_request_amount > 0 && d.stat_interval_ms > 0;
+            if (valid && d.grade == SG_DEGRADE_RT)
+                valid = d.slow_ratio_threshold >= 0 && d.slow_ratio_threshold <= 1;  // NaN fails both
+            if (valid && d.grade == SG_DEGRADE_EXCEPTION_RATIO) valid = d.count <= 1;
+            if (!valid) return fail(h, SG_E_INVAL, "invalid degrade rule");
             b.grade = d.grade;
             b.count = d.count;
             b.slow_ratio = d.slow_ratio_threshold;

@@ -272,3 +272,84 @@ def test_no_rule_resource_passes_and_counts():
     assert c.minute_sum(0, t + 300, 2) == 10  # exceptions
     assert c.minute_sum(0, t + 300, 3) == 100  # success
     assert c.minute_sum(0, t + 300, 4) == 100 * 200  # rt sum
+
+
+# ---- circuit breaker edges the oracle alone answers for (tests/test_breaker_edges_premise.py), by hand
+
+@pytest.mark.parametrize("tw,ms", [(2_147_484, -2147483296), (4_294_968, 704)])
+def test_recovery_timeout_wraps_as_an_int(tw, ms):
+    """`protected final int recoveryTimeoutMs` (AbstractCircuitBreaker.java:36) = rule.getTimeWindow() * 1000 (:54) in
+    int arithmetic: 2 147 484 s wraps to -2 147 483 296 ms (nextRetryTimestamp lies in the past: the next entry is
+    the probe), 4 294 968 s to 704 ms. updateNextRetryTimestamp (:89-91) adds it to the long clock."""
+    assert (tw * 1000 + (1 << 31)) % (1 << 32) - (1 << 31) == ms
+    c = chain_with(degrade_rule(abi.DEGRADE_EXCEPTION_COUNT, 0, tw, min_request_amount=1, stat_interval_ms=1000))
+    t = T0_SEC + 17
+    assert c.entry(t)[0] == abi.LOCAL_PASS
+    c.exit(t + 5, t, error=True)  # 1 > 0: open
+    assert c.breaker(0, 0) == (OPEN, t + 5 + ms)
+    if ms < 0:
+        assert c.entry(t + 5)[0] == abi.LOCAL_PASS and c.breaker(0, 0)[0] == HALF_OPEN
+    else:
+        assert c.entry(t + 5 + ms - 1)[0] == abi.LOCAL_BLOCK_DEGRADE and c.breaker(0, 0)[0] == OPEN
+        assert c.entry(t + 5 + ms)[0] == abi.LOCAL_PASS and c.breaker(0, 0)[0] == HALF_OPEN
+    # the probe comes back in error: fromHalfOpenToOpen (:132-139) adds the same wrapped timeout
+    t2 = t + 5 + max(ms, 0)
+    c.exit(t2 + 9, t2, error=True)
+    assert c.breaker(0, 0) == (OPEN, t2 + 9 + ms)
+
+
+@pytest.mark.parametrize("count,max_rt", [(0.5, 1), (0.49999999999999994, 0), (10.5, 11), (1e30, (1 << 63) - 1)])
+def test_max_allowed_rt_is_math_round_of_the_count(count, max_rt):
+    """maxAllowedRt = Math.round(rule.getCount()) (ResponseTimeCircuitBreaker.java:52): ties go up (0.5 -> 1, 10.5 ->
+    11), the largest double below 0.5 gives 0 (floor(x + 0.5) in double arithmetic would give 1), 1e30 saturates at
+    Long.MAX_VALUE. `rt > maxAllowedRt` (:76) counts a slow request. Slow ratio 0.0: the first slow exit opens."""
+    c = chain_with(degrade_rule(abi.DEGRADE_RT, count, 1, min_request_amount=1, stat_interval_ms=1 << 30,
+                                slow_ratio_threshold=0.0))
+    t = T0_SEC + 3
+    at = min(max_rt, 1 << 40)
+    assert c.entry(t)[0] == abi.LOCAL_PASS
+    c.exit(t + at, t)  # rt == maxAllowedRt: not slow
+    assert c.breaker(0, 0)[0] == CLOSED and c.breaker_stat(0, 0)[1:] == (0, 1)
+    assert c.entry(t + at)[0] == abi.LOCAL_PASS
+    if max_rt == (1 << 63) - 1:
+        c.exit(t + at + (1 << 41), t + at)
+        assert c.breaker(0, 0)[0] == CLOSED and c.breaker_stat(0, 0)[1] == 0
+        return
+    c.exit(t + at + max_rt + 1, t + at)  # rt == maxAllowedRt + 1: slow, 1 / 2 > 0.0
+    assert c.breaker(0, 0)[0] == OPEN and c.breaker_stat(0, 0)[1:] == (1, 2)
+
+
+def _rt_exits(c, t, rts):
+    for i, rt in enumerate(rts):
+        assert c.entry(t + i)[0] == abi.LOCAL_PASS
+    for i, rt in enumerate(rts):
+        c.exit(t + i + rt, t + i)
+        yield c.breaker(0, 0)[0]
+
+
+def test_slow_ratio_equality_opens_only_at_1():
+    """handleStateChangeWhenThresholdExceeded (ResponseTimeCircuitBreaker.java:101-118): `currentRatio >
+    maxSlowRequestRatio` opens, and so does equality, but only when the threshold is SLOW_REQUEST_RATIO_MAX_VALUE
+    (Double.compare(...) == 0 twice, :114-115). At 0.5 a ratio of exactly 0.5 stays CLOSED."""
+    rule = lambda thr: degrade_rule(abi.DEGRADE_RT, 10, 1, min_request_amount=2, stat_interval_ms=10_000,  # noqa: E731
+                                    slow_ratio_threshold=thr)
+    t = T0_SEC + 11
+    # 1.0: one slow exit is below the amount; two of two: 1.0 == 1.0 opens; a fast one among them never does
+    assert list(_rt_exits(chain_with(rule(1.0)), t, [11, 12])) == [CLOSED, OPEN]
+    assert list(_rt_exits(chain_with(rule(1.0)), t, [11, 10, 12, 13])) == [CLOSED] * 4
+    # 0.5: 1 / 2 == 0.5 stays CLOSED, 2 / 4 too, 3 / 5 opens
+    assert list(_rt_exits(chain_with(rule(0.5)), t, [11, 10, 10, 12, 13])) == [CLOSED] * 4 + [OPEN]
+
+
+@pytest.mark.parametrize("count,n_closed", [(3, 3), (2.5, 2), (0, 0)])
+def test_exception_count_is_compared_with_greater_than(count, n_closed):
+    """`curCount > threshold` with a double threshold (ExceptionCircuitBreaker.java:105-112): 3 errors against 3 stay
+    CLOSED and the fourth opens; against 2.5 two stay CLOSED and the third opens."""
+    c = chain_with(degrade_rule(abi.DEGRADE_EXCEPTION_COUNT, count, 1, min_request_amount=1, stat_interval_ms=10_000))
+    t = T0_SEC + 29
+    for i in range(n_closed + 1):
+        assert c.entry(t + i)[0] == abi.LOCAL_PASS
+    for i in range(n_closed + 1):
+        assert c.breaker(0, 0)[0] == CLOSED
+        c.exit(t + 20 + i, t + i, error=True)
+    assert c.breaker(0, 0)[0] == OPEN and c.breaker_stat(0, 0)[1] == n_closed + 1
