@@ -494,23 +494,6 @@ double global_threshold(const sg_handle* h, const sg_flow_rule& r) {
     return base * h->cfg.exceed_count;
 }
 
-// java.lang.Math.round(double) (JDK 7u+): floor(x + 1/2) computed exactly on the bits; saturating.
-int64_t java_math_round(double a) {
-    int64_t bits;
-    std::memcpy(&bits, &a, 8);
-    const int64_t biased_exp = (bits & 0x7FF0000000000000LL) >> 52;
-    const int64_t shift = (52 - 1 + 1023) - biased_exp;
-    if ((shift & -64) == 0) {
-        int64_t r = (bits & 0x000FFFFFFFFFFFFFLL) | 0x0010000000000000LL;
-        if (bits < 0) r = -r;
-        return ((r >> shift) + 1) >> 1;
-    }
-    if (a != a) return 0;
-    if (a >= 9223372036854775807.0) return INT64_MAX;
-    if (a <= -9223372036854775808.0) return INT64_MIN;
-    return (int64_t)a;
-}
-
 
 int layout_records(sg_handle* h) {
     h->kbits = bits_for((uint64_t)h->K);  // must hold K itself (sentinel key of rejected requests)
@@ -1048,12 +1031,7 @@ int sg_load_flow_rules(sg_handle* h, const sg_flow_rule* rules, uint32_t n) {
 
 // flowId → rule index for the wire codec: open addressing, linear probing, load factor <= 1/2 (the same
 // splitmix64 finaliser as codec.hip's fid_hash). flowIds are > 0 and unique (validated above).
-static uint64_t host_fid_hash(int64_t fid) {
-    uint64_t z = (uint64_t)fid + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+static uint64_t host_fid_hash(int64_t fid) { return mix64((uint64_t)fid); }
 
 static int upload_fid_table(sg_handle* h) {
     uint64_t cap = 2;
@@ -2593,6 +2571,22 @@ int sg_param_load_rules(sg_handle* h, const sg_param_rule* rules, uint32_t n, co
     return SG_OK;
 }
 
+// The handle's millisecond table for a batch of n requests, allocated at the first call. The hot-parameter and the
+// pace batch share it: both are synchronous calls of this handle. False: out of device memory.
+static bool ms_table_for(sg_handle* h, uint64_t n, MsTable* m) {
+    if (!h->d_p_msb && (!h->d_p_msb.alloc_bytes(sizeof(uint32_t) * kMaxPeriods) ||
+                        !h->d_p_mt.alloc_bytes(2 * sizeof(int64_t))))  // {t0, {np, zero word}}
+        return false;
+    if (!h->d_p_mbk && !h->d_p_mbk.alloc_bytes(sizeof(uint16_t) * kPcBuckets)) return false;
+    m->msb = h->d_p_msb;
+    m->mt0 = h->d_p_mt;
+    m->mnp = reinterpret_cast<uint32_t*>(h->d_p_mt + 1);
+    m->mbk = h->d_p_mbk;
+    m->bshift = 0;
+    while (((n - 1) >> m->bshift) >= kPcBuckets) ++m->bshift;
+    return true;
+}
+
 int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int32_t* pass, void* stream_) {
     if (!h) return SG_E_INVAL;
     if (n == 0) return SG_OK;
@@ -2623,17 +2617,7 @@ int sg_param_decide_batch(sg_handle* h, const sg_param_req* req, uint64_t n, int
     const int gbits = bits_for(h->ptotal + 1);
     p.gshift = p.ibits + 8;  // {slot | acquire code : 8 | request index}
     if (p.gshift + gbits > 64) return fail(h, SG_E_UNSUPPORTED, "param tables x max_batch too large for 64-bit records");
-    if (!h->d_p_msb && (!h->d_p_msb.alloc_bytes(sizeof(uint32_t) * kMaxPeriods) ||
-                        !h->d_p_mt.alloc_bytes(2 * sizeof(int64_t))))  // {t0, {np, zero word}}
-        return fail(h, SG_E_NOMEM, "param millisecond table");
-    p.msb = h->d_p_msb;
-    p.mt0 = h->d_p_mt;
-    p.mnp = reinterpret_cast<uint32_t*>(h->d_p_mt + 1);
-    if (!h->d_p_mbk && !h->d_p_mbk.alloc_bytes(sizeof(uint16_t) * kPcBuckets))
-        return fail(h, SG_E_NOMEM, "param millisecond buckets");
-    p.mbk = h->d_p_mbk;
-    p.bshift = 0;
-    while ((((uint64_t)n - 1) >> p.bshift) >= kPcBuckets) ++p.bshift;
+    if (!ms_table_for(h, n, &p.ms)) return fail(h, SG_E_NOMEM, "param millisecond table");
     BatchArgs sg{};  // k_seg's lists in the main workspace; its error word: a zero word (the param flags are no errors)
     sg.err = reinterpret_cast<int*>(h->d_p_mt.get()) + 3;
     sg.short_list = h->ws[0].short_list;
@@ -2678,12 +2662,8 @@ int sg_param_read_state(sg_handle* h, uint32_t rule, uint64_t value, int64_t* la
         HIP_TRY(h, hipMemcpy(&found, h->d_ptable + R.table_base + R.table_mask + 1, sizeof(PSlot), hipMemcpyDeviceToHost));
         hit = true;
     } else {
-        // the probe sequence of param.hip's param_slot, read in chunks of 64 slots
-        uint64_t x = value + 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        x ^= x >> 31;
-        uint64_t i = x & R.table_mask, seen = 0;
+        // the probe sequence of param_slot, read in chunks of 64 slots
+        uint64_t i = table_home(value, R.table_mask), seen = 0;
         PSlot chunk[64];
         while (!hit && seen <= R.table_mask) {
             const uint64_t m = std::min<uint64_t>(64, R.table_mask + 1 - i);  // up to the table's end
@@ -2891,18 +2871,7 @@ int sg_pace_decide_batch(sg_handle* h, const sg_pace_req* req, uint64_t n, int32
     const int gbits = bits_for((uint64_t)p.n_rules + 1);
     p.gshift = p.ibits + 8;  // {rule | acquire code : 8 | request index}
     if (p.gshift + gbits > 64) return fail(h, SG_E_UNSUPPORTED, "pace rules x max_batch too large for 64-bit records");
-    // the millisecond table (shared with the hot-parameter path: both are synchronous calls of this handle)
-    if (!h->d_p_msb && (!h->d_p_msb.alloc_bytes(sizeof(uint32_t) * kMaxPeriods) ||
-                        !h->d_p_mt.alloc_bytes(2 * sizeof(int64_t))))
-        return fail(h, SG_E_NOMEM, "pace millisecond table");
-    p.msb = h->d_p_msb;
-    p.mt0 = h->d_p_mt;
-    p.mnp = reinterpret_cast<uint32_t*>(h->d_p_mt + 1);
-    if (!h->d_p_mbk && !h->d_p_mbk.alloc_bytes(sizeof(uint16_t) * kPcBuckets))
-        return fail(h, SG_E_NOMEM, "pace millisecond buckets");
-    p.mbk = h->d_p_mbk;
-    p.bshift = 0;
-    while ((((uint64_t)n - 1) >> p.bshift) >= kPcBuckets) ++p.bshift;
+    if (!ms_table_for(h, n, &p.ms)) return fail(h, SG_E_NOMEM, "pace millisecond table");
     HIP_TRY(h, hipMemsetAsync(h->ws[0].err, 0, sizeof(int), stream));
     for (int c = 0; c < kClasses; ++c) p.class_off[c] = h->class_off[c];
     HIP_TRY(h, hipMemsetAsync(h->ws[0].counts, 0, (1 + kClasses) * sizeof(uint32_t), stream));
@@ -3649,7 +3618,7 @@ int sg_local_load_rules(sg_handle* h, const sg_local_config* cfg, const sg_local
             b.grade = d.grade;
             b.count = d.count;
             b.slow_ratio = d.slow_ratio_threshold;
-            b.max_rt = java_math_round(d.count);  // ResponseTimeCircuitBreaker.java:52
+            b.max_rt = java_round(d.count);  // ResponseTimeCircuitBreaker.java:52
             b.min_request = d.min_request_amount;
             b.recovery_ms = (int32_t)((uint32_t)d.time_window_sec * 1000u);  // int arithmetic, wraps
             b.stat_ms = d.stat_interval_ms;
@@ -3827,11 +3796,7 @@ int sg_local_owners(sg_handle* h, uint32_t world, uint32_t* owner, uint32_t n) {
     std::vector<uint32_t> gkey;
     local_group_keys(h, gkey);
     for (uint32_t k = 0; k < K; ++k) {  // splitmix64(group key) mod world (sentinel_amd/cluster.py local_owners)
-        uint64_t z = (uint64_t)gkey[k] + 0x9E3779B97F4A7C15ull;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        owner[k] = (uint32_t)(z % world);
+        owner[k] = (uint32_t)(mix64((uint64_t)gkey[k]) % world);
     }
     return SG_OK;
 }
@@ -4758,13 +4723,6 @@ bool local_flow_rule_same(const sg_local_flow_rule& a, const sg_local_flow_rule&
            (a.cluster_mode == 0 || (a.cluster_mode == b.cluster_mode && a.cluster_config == b.cluster_config));
 }
 
-int32_t d2i_host(double x) {  // (int) double
-    if (x != x) return 0;
-    if (x >= 2147483647.0) return INT32_MAX;
-    if (x <= -2147483648.0) return INT32_MIN;
-    return (int32_t)x;
-}
-
 // The controller constants of one flow rule (FlowRuleUtil.generateRater; WarmUpController.construct :83-106 in
 // Java int arithmetic).
 LFlowRule make_flow_rule(const sg_local_flow_rule& r, int cold) {
@@ -4781,9 +4739,9 @@ LFlowRule make_flow_rule(const sg_local_flow_rule& r, int cold) {
     f.cluster_mode = r.cluster_mode;
     f.cluster_key = r.cluster_key;
     if (f.behavior == SG_CONTROL_WARM_UP || f.behavior == SG_CONTROL_WARM_UP_RATE_LIMITER) {
-        f.warning_token = d2i_host(r.warm_up_period_sec * r.count) / (cold - 1);
+        f.warning_token = java_d2i(r.warm_up_period_sec * r.count) / (cold - 1);
         const int32_t two_w = (int32_t)(2u * (uint32_t)r.warm_up_period_sec);  // 2 * warmUpPeriodInSec: int
-        f.max_token = (int32_t)((uint32_t)f.warning_token + (uint32_t)d2i_host(two_w * r.count / (1.0 + cold)));
+        f.max_token = (int32_t)((uint32_t)f.warning_token + (uint32_t)java_d2i(two_w * r.count / (1.0 + cold)));
         f.slope = (cold - 1.0) / r.count / (double)(int32_t)((uint32_t)f.max_token - (uint32_t)f.warning_token);
     }
     return f;
@@ -5877,11 +5835,7 @@ int nfail(sg_node* nd, int code, const std::string& msg) {
 
 // splitmix64(flowId) mod G: the owner shard (sentinel_amd/cluster.py shard_of)
 uint32_t node_owner(int64_t flow_id, uint32_t G) {
-    uint64_t z = (uint64_t)flow_id + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (uint32_t)(z % G);
+    return (uint32_t)(mix64((uint64_t)flow_id) % G);
 }
 
 // A shard's error, in the node's words.

@@ -20,8 +20,6 @@ namespace sg {
 
 namespace {
 
-__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
-
 struct BlogKey {
     int64_t ts;
     uint64_t app;
@@ -30,10 +28,10 @@ struct BlogKey {
 };
 
 __device__ __forceinline__ uint64_t blog_hash(const BlogKey& k) {
-    uint64_t h = lnode_hash(k.ro + 0x9E3779B97F4A7C15ull);
-    h = lnode_hash(h ^ k.app);
-    h = lnode_hash(h ^ (uint64_t)k.ts);
-    return lnode_hash(h ^ k.sk);
+    uint64_t h = mix64(k.ro);
+    h = mix64_final(h ^ k.app);
+    h = mix64_final(h ^ (uint64_t)k.ts);
+    return mix64_final(h ^ k.sk);
 }
 
 // One lane: find or claim the key's slot and add (sum, over `events` entries) to it; a full table counts them lost.
@@ -105,7 +103,7 @@ __device__ void blog_wave_add(const BlogArgs& b, BlogCarry& c, bool act, const B
         const uint64_t lsk = (uint64_t)__shfl((long long)k.sk, lead, 64);
         const bool same = ((todo >> lane) & 1ull) && k.ts == lts && k.app == lapp && k.ro == lro && k.sk == lsk;
         const uint64_t m = __ballot(same);
-        int64_t sum = same ? cnt : 0;
+        int64_t sum = same ? cnt : 0;  // wave_sum spelled out: the call reorders this function's instructions
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor((long long)sum, o, 64);
         const uint64_t events = (uint64_t)__popcll(m);

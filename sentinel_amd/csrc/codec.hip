@@ -10,12 +10,7 @@
 
 namespace sg {
 
-__device__ __forceinline__ uint64_t fid_hash(int64_t fid) {  // splitmix64 finaliser
-    uint64_t z = (uint64_t)fid + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+__device__ __forceinline__ uint64_t fid_hash(int64_t fid) { return mix64((uint64_t)fid); }
 
 __device__ __forceinline__ int32_t rd_be32(const uint8_t* p) {
     return (int32_t)(((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3]);

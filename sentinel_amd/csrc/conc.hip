@@ -21,12 +21,7 @@ namespace sg {
 
 namespace {
 
-__device__ __forceinline__ uint64_t tok_hash(uint64_t id) {  // splitmix64 finaliser
-    uint64_t z = id + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+__device__ __forceinline__ uint64_t tok_hash(uint64_t id) { return mix64(id); }
 
 __device__ __forceinline__ uint64_t fid_hash2(int64_t fid) {
     return tok_hash((uint64_t)fid);

@@ -23,13 +23,6 @@ namespace sg {
 
 namespace {
 
-__device__ __forceinline__ int32_t cp_d2i(double x) {  // JLS §5.1.3
-    if (x != x) return 0;
-    if (x >= 2147483647.0) return INT32_MAX;
-    if (x <= -2147483648.0) return INT32_MIN;
-    return (int32_t)x;
-}
-
 __device__ __forceinline__ void cp_store(sg_result* out, uint64_t i, int32_t st, int32_t rem) {
     sg_result r;
     r.status = st;
@@ -253,23 +246,9 @@ __device__ __forceinline__ void cp_stage_periods(const CPBatch& b) {
 
 // window period (absolute) of request i for window length w: the largest q with table[q] <= i (entry 0 unused)
 __device__ __forceinline__ int64_t cp_period(const CPBatch& b, int w, uint32_t i) {
-    uint32_t lo = 0, hi = cp_np[w];
-    if (cp_blds) {
-        const uint32_t* t = cp_sbnd + cp_boff[w];
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (t[mid] <= i) lo = mid;
-            else hi = mid;
-        }
-    } else {
-        const uint32_t* t = b.bnd + (size_t)w * kMaxPeriods;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (t[mid] <= i) lo = mid;
-            else hi = mid;
-        }
-    }
-    return cp_p0[w] + (int64_t)lo;
+    const uint32_t q = cp_blds ? period_of(cp_sbnd + cp_boff[w], cp_np[w], i)
+                               : period_of(b.bnd + (size_t)w * kMaxPeriods, cp_np[w], i);
+    return cp_p0[w] + (int64_t)q;
 }
 
 // The 100 ms limiter periods of the batch (row 0 of the period table) and {cparam rule | request} records of the
@@ -511,7 +490,7 @@ __device__ void cp_walk_serial_mem(const CPArgs& c, const CPBatch& b, const Batc
             mi = kNoOwner;
             if (rem >= 0) {
                 cur += d.acq;
-                cp_store(c.out, i, SG_STATUS_OK, cp_d2i(rem));
+                cp_store(c.out, i, SG_STATUS_OK, java_d2i(rem));
             } else if (b.round > 0) {  // round 0: BLOCKED is k_cp_prep2's default already
                 cp_store(c.out, i, SG_STATUS_BLOCKED, 0);
             }
@@ -608,7 +587,7 @@ __device__ void cp_walk_serial_reg(const CPArgs& c, const CPBatch& b, const Batc
             mi = kNoOwner;
             if (rem >= 0) {
                 cur += d.acq;
-                cp_store(c.out, i, SG_STATUS_OK, cp_d2i(rem));
+                cp_store(c.out, i, SG_STATUS_OK, java_d2i(rem));
             } else if (b.round > 0) {  // round 0: BLOCKED is k_cp_prep2's default already
                 cp_store(c.out, i, SG_STATUS_BLOCKED, 0);
             }
@@ -722,45 +701,7 @@ __global__ void __launch_bounds__(256) k_cp_items(CPBatch b, BatchArgs sg) {
     }
 }
 
-template <class Pred>
-__device__ __forceinline__ uint64_t cp_wave_search(uint64_t lo, uint64_t hi, Pred pred, int lane) {
-    while (hi - lo > 64) {
-        const uint64_t step = (hi - lo + 63) / 64;
-        const uint64_t q = lo + (uint64_t)lane * step;
-        const uint64_t m = __ballot(q >= hi || pred(q));
-        if (m == 0) {
-            lo = lo + 63 * step + 1;
-            continue;
-        }
-        const int f = __builtin_ctzll(m);
-        if (f == 0) return lo;
-        const uint64_t nhi = lo + (uint64_t)f * step;
-        lo = lo + (uint64_t)(f - 1) * step + 1;
-        hi = nhi < hi ? nhi : hi;
-    }
-    const uint64_t q = lo + (uint64_t)lane;
-    const uint64_t m = __ballot(q < hi && pred(q));
-    return m ? lo + (uint64_t)__builtin_ctzll(m) : hi;
-}
-
-__device__ __forceinline__ int64_t cp_excl_scan(int64_t v, int lane) {
-    int64_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t y = __shfl_up((long long)x, (unsigned)o, 64);
-        if (lane >= o) x += y;
-    }
-    return x - v;
-}
-
-__device__ __forceinline__ int64_t cp_wave_sum(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((long long)v, o, 64);
-    return v;
-}
-
 enum : int { kCpSkip = 0, kCpSingle = 1, kCpMulti = 2, kCpDup = 3 };
-__device__ __forceinline__ uint64_t cp_below(int f) { return f >= 64 ? ~0ull : ((1ull << f) - 1ull); }
 #ifndef SG_CPU
 #define SG_CPU 2
 #endif
@@ -920,11 +861,11 @@ __global__ void __launch_bounds__(256, SG_CPL_BLOCKS) k_cp_walk2_long(CPArgs c, 
                 if (typ == kCpSingle) {
                     add = acq;
                 } else if (typ == kCpMulti) {
-                    const uint64_t after = nondup & ~cp_below(lane + 1);
+                    const uint64_t after = nondup & ~below(lane + 1);
                     const int nxt = after ? __builtin_ctzll(after) : 64;
                     add = as[u] ? acq * (int64_t)(nxt - lane) : 0;  // this record and its repeats in the chunk
                 } else if (typ == kCpDup) {
-                    add = ((nondup & cp_below(lane)) == 0 && carry_ok && as[u]) ? acq : 0;
+                    add = ((nondup & below(lane)) == 0 && carry_ok && as[u]) ? acq : 0;
                     b.chk[p] = 1;  // the request's first record here carries the check
                 }
                 // lanes whose own check decides their add (a failing check adds nothing)
@@ -954,8 +895,8 @@ __global__ void __launch_bounds__(256, SG_CPL_BLOCKS) k_cp_walk2_long(CPArgs c, 
                             if (lane == I) cc = bst == ws ? bcnt : 0;
                             else if (bst != INT64_MIN && bst >= lo) o = bcnt;
                         }
-                        other = cp_wave_sum(o);
-                        cur = cp_wave_sum(cc);
+                        other = wave_sum(o);
+                        cur = wave_sum(cc);
                     }
                     uint64_t open = pending & __ballot(typ != kCpSkip && Pq == P);
                     pending &= ~open;
@@ -963,7 +904,7 @@ __global__ void __launch_bounds__(256, SG_CPL_BLOCKS) k_cp_walk2_long(CPArgs c, 
                         const bool mine = (open >> lane) & 1ull;
                         const bool dead = (failed >> lane) & 1ull;
                         const int64_t a = (mine && !dead) ? add : 0;
-                        const int64_t excl = cp_excl_scan(a, lane);
+                        const int64_t excl = wave_excl_scan(a, lane);
                         const double rem = thr - avg_div((double)(other + cur + excl), r.isec) - (double)acq;
                         const bool ok = rem >= 0 && !dead;
                         // a dead lane adds nothing already: not a cut (else every pass would stop at one)
@@ -975,12 +916,12 @@ __global__ void __launch_bounds__(256, SG_CPL_BLOCKS) k_cp_walk2_long(CPArgs c, 
                             done = open & ((2ull << k) - 1ull);
                             adv = __shfl((long long)excl, k, 64);  // the failing lane k adds nothing
                         } else {
-                            adv = cp_wave_sum(a);
+                            adv = wave_sum(a);
                         }
                         if ((done >> lane) & 1ull) {
                             okv = ok;
                             if (typ == kCpSingle) {
-                                if (ok) cp_store(c.out, i, SG_STATUS_OK, cp_d2i(rem));
+                                if (ok) cp_store(c.out, i, SG_STATUS_OK, java_d2i(rem));
                                 else if (b.round > 0) cp_store(c.out, i, SG_STATUS_BLOCKED, 0);
                             } else if (typ == kCpMulti) {
                                 b.chk[p] = ok ? 1 : 0;
@@ -1303,7 +1244,7 @@ __global__ void __launch_bounds__(256) k_cpfb_replay(CPArgs c, CPBatch b, CPGrou
                 }
             }
             if (q.value_count > 1) rem = -1;
-            cp_store(c.out, i, pass ? SG_STATUS_OK : SG_STATUS_BLOCKED, pass ? cp_d2i(rem) : 0);
+            cp_store(c.out, i, pass ? SG_STATUS_OK : SG_STATUS_BLOCKED, pass ? java_d2i(rem) : 0);
         }
     }
 }

@@ -25,27 +25,32 @@ __device__ __forceinline__ double cp_threshold(const CPArgs& c, const CPRule& r,
     return r.global ? count : count * (double)r.connected;
 }
 
-__device__ __forceinline__ uint64_t cp_slot(const CPArgs& c, const CPRule& r, uint64_t v) {
-    if (v == kCpEmpty) return r.table_base + r.table_mask + 1;  // side slot for the marker value
-    uint64_t h = v + 0x9E3779B97F4A7C15ull;
-    h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
-    h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
-    h ^= h >> 31;
-    uint64_t i = h & r.table_mask;
-    for (uint64_t probes = 0; probes <= r.table_mask; ++probes) {
-        unsigned long long* vw = (unsigned long long*)&c.keys[r.table_base + i];
+// Find-or-insert of value v in an exact table's sub-table of mask + 1 slots at base (the slot after them is the side
+// slot of the value ~0, which doubles as the empty marker): its global slot index, ~0 when the sub-table is full.
+// word(g) is the address of slot g's value word.
+template <class Word>
+__device__ __forceinline__ uint64_t table_find_or_insert(uint64_t base, uint64_t mask, uint64_t v, Word word) {
+    if (v == kCpEmpty) return base + mask + 1;
+    uint64_t i = table_home(v, mask);
+    for (uint64_t probes = 0; probes <= mask; ++probes) {
+        unsigned long long* vw = word(base + i);
         // a plain (L2-cached) load: a slot only ever goes from empty to its value, so a stale read can only say
         // "empty", and the CAS below then returns the value that is there (an agent-scope atomic load bypassed
         // the XCD's L2 on every probe, also for the hot values that repeat throughout a batch)
         const unsigned long long cur = *vw;
-        if (cur == v) return r.table_base + i;
+        if (cur == v) return base + i;
         if (cur == kCpEmpty) {
             const unsigned long long old = atomicCAS(vw, (unsigned long long)kCpEmpty, (unsigned long long)v);
-            if (old == kCpEmpty || old == v) return r.table_base + i;
+            if (old == kCpEmpty || old == v) return base + i;
         }
-        i = (i + 1) & r.table_mask;
+        i = (i + 1) & mask;
     }
     return ~0ull;
+}
+
+__device__ __forceinline__ uint64_t cp_slot(const CPArgs& c, const CPRule& r, uint64_t v) {
+    return table_find_or_insert(r.table_base, r.table_mask, v,
+                                [&](uint64_t g) { return (unsigned long long*)&c.keys[g]; });
 }
 
 __device__ __forceinline__ uint32_t cp_rule_of_slot(const CPArgs& c, uint64_t g) {
@@ -72,11 +77,7 @@ __device__ __forceinline__ int64_t cp_window(const CPBucket* ring, int S, int64_
 // The slot of (rule, value) when the value is in the table, else ~0 (ClusterParamMetric.getSum of an absent value: 0).
 __device__ __forceinline__ uint64_t cp_find(const CPArgs& c, const CPRule& r, uint64_t v) {
     if (v == kCpEmpty) return r.table_base + r.table_mask + 1;
-    uint64_t h = v + 0x9E3779B97F4A7C15ull;
-    h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
-    h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
-    h ^= h >> 31;
-    uint64_t i = h & r.table_mask;
+    uint64_t i = table_home(v, r.table_mask);
     for (uint64_t probes = 0; probes <= r.table_mask; ++probes) {
         const uint64_t cur = c.keys[r.table_base + i];
         if (cur == v) return r.table_base + i;

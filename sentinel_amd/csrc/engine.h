@@ -13,6 +13,7 @@
 #include "gateway_rules.h"
 #include "serverlog_rules.h"
 #include "system_rules.h"
+#include "java_num.h"
 #include "search_dev.h"
 
 namespace sg {
@@ -278,6 +279,16 @@ struct alignas(32) PSlot {  // one (rule, value): timeCounters / tokenCounters e
 
 constexpr uint32_t kPcBuckets = 2048;  // request buckets of the index → millisecond lookup (pace, hot params)
 
+// The batch's millisecond table (hot parameters, pace): request index → timestamp for the walkers, which then read
+// nothing per request but its sorted record. The prep kernel writes it, the walkers stage it in LDS (mstable_dev.h).
+struct MsTable {
+    uint32_t* msb;          // [kMaxPeriods] first request index of each millisecond of the batch (entry 0 unused)
+    int64_t* mt0;           // the batch's first timestamp
+    uint32_t* mnp;          // milliseconds the batch spans (> kMaxPeriods: the walkers read the timestamps)
+    uint16_t* mbk;          // [n >> bshift buckets] millisecond (from the first) of request bucket << bshift
+    int bshift;
+};
+
 struct PArgs {
     const sg_param_req* req;
     int32_t* out;
@@ -288,11 +299,7 @@ struct PArgs {
     int ibits;
     uint64_t imask;
     int gshift;             // the hot-parameter batch's slot shift (ibits + 8); acquire code 255 = read req[i].acquire
-    uint32_t* msb;          // [kMaxPeriods] first request index of each millisecond of the batch (entry 0 unused)
-    int64_t* mt0;           // the batch's first timestamp
-    uint32_t* mnp;          // milliseconds the batch spans (> kMaxPeriods: the walkers read the timestamps)
-    uint16_t* mbk;          // [n >> bshift buckets] millisecond (from the first) of request bucket << bshift
-    int bshift;
+    MsTable ms;
     const PRule* rules;
     uint32_t n_rules;
     const sg_param_hot_item* hot;  // per rule, sorted by value
@@ -354,11 +361,7 @@ struct PaceArgs {
     uint32_t* short_list;
     uint32_t short_max;
     int gshift;             // records {rule : high bits | acquire code : 8 | request index : ibits}: rule at gshift
-    uint32_t* msb;          // the millisecond table: first request index of every millisecond of the batch
-    int64_t* mt0;           // [0] the batch's first timestamp, then {millisecond count, zero word}
-    uint32_t* mnp;
-    uint16_t* mbk;          // [n >> bshift buckets] millisecond (from the first) of request bucket << bshift
-    int bshift;
+    MsTable ms;
     uint64_t class_off[kClasses];  // the lane walker's length classes in short_list (counts at long_count[1 + c])
 };
 
@@ -685,13 +688,7 @@ constexpr uint64_t kLNodeCtx = 1ull << 31;  // key bit: a context DefaultNode (e
 __host__ __device__ __forceinline__ uint64_t lnode_key(uint32_t res, uint64_t kind, uint32_t id) {
     return ((uint64_t)(res + 1u) << 32) | kind | (uint64_t)id;  // never 0 (the empty slot)
 }
-__host__ __device__ __forceinline__ uint64_t lnode_hash(uint64_t x) {  // splitmix64 finaliser
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
+__host__ __device__ __forceinline__ uint64_t lnode_hash(uint64_t key) { return mix64_final(key); }
 
 // A flow rule of the local chain with its controller's constants (FlowRuleUtil.generateRater, WarmUpController
 // .construct :83-106).

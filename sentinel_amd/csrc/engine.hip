@@ -30,39 +30,11 @@ namespace sg {
 
 // ----------------------------------------------------------------------------------------- helpers
 
-__device__ __forceinline__ int32_t java_d2i(double x) {
-    // JLS §5.1.3: NaN → 0, saturate, truncate toward zero.
-    if (x != x) return 0;
-    if (x >= 2147483647.0) return INT32_MAX;
-    if (x <= -2147483648.0) return INT32_MIN;
-    return (int32_t)x;
-}
-
-__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
-
 // LeapArray sum / intervalInSecond (ClusterMetric.getAvg, ClusterMetric.java:70-72)
 __device__ __forceinline__ double qps_of(int64_t sum, double isec) { return avg_div((double)sum, isec); }
 
-__device__ __forceinline__ int64_t wave_sum(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((long long)v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ int64_t wave_excl_scan(int64_t v, int lane) {
-    int64_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int64_t y = __shfl_up((long long)x, (unsigned)o, 64);
-        if (lane >= o) x += y;
-    }
-    return x - v;
-}
-
 __device__ __forceinline__ int64_t bcast64(int64_t v, int src) { return __shfl((long long)v, src, 64); }
 __device__ __forceinline__ int bcast32(int v, int src) { return __shfl(v, src, 64); }
-
-__device__ __forceinline__ uint64_t below(int f) { return f >= 64 ? ~0ull : ((1ull << f) - 1ull); }
 
 __device__ __forceinline__ void store_result(sg_result* out, uint32_t idx, int32_t st, int32_t rem, int32_t wait) {
     sg_result r;
@@ -348,7 +320,7 @@ struct PeriodCursor {
     // period of a request index >= every index seen so far: the largest p with table[p] <= idx
     __device__ __forceinline__ uint32_t of(uint32_t idx) const {
         if (q != 0xFFFFFFFFu && idx < next_b) return q;
-        uint32_t lo = 0, hi = np;
+        uint32_t lo = 0, hi = np;  // last_le spelled out: through the template the walkers' code comes out differently
         while (hi - lo > 1) {
             const uint32_t mid = (lo + hi) >> 1;
             if (at(mid) <= idx) lo = mid;
@@ -680,29 +652,6 @@ struct WaveWalker {
         }
     }
 };
-
-// First position p in [lo, hi) with pred(p) (pred monotone false→true), hi if none. 64-way wave search:
-// every step probes 64 evenly spaced positions, so a million-record range takes 4 dependent loads.
-template <class Pred>
-__device__ __forceinline__ uint64_t wave_search(uint64_t lo, uint64_t hi, Pred pred, int lane) {
-    while (hi - lo > 64) {
-        const uint64_t step = (hi - lo + 63) / 64;
-        const uint64_t p = lo + (uint64_t)lane * step;
-        const uint64_t m = __ballot(p >= hi || pred(p));
-        if (m == 0) {
-            lo = lo + 63 * step + 1;
-            continue;
-        }
-        const int f = __builtin_ctzll(m);
-        if (f == 0) return lo;
-        const uint64_t nhi = lo + (uint64_t)f * step;
-        lo = lo + (uint64_t)(f - 1) * step + 1;
-        hi = nhi < hi ? nhi : hi;
-    }
-    const uint64_t p = lo + (uint64_t)lane;
-    const uint64_t m = __ballot(p < hi && pred(p));
-    return m ? lo + (uint64_t)__builtin_ctzll(m) : hi;
-}
 
 // Inlined into k_walk_long (not a called function, as in round 3): one register allocation for the kernel instead of
 // a call frame per segment — 0.90 vs 0.96 ms/step pipelined, same box.

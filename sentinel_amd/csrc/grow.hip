@@ -23,29 +23,13 @@ namespace {
 
 constexpr uint32_t kGrowDropped = 0xFFFFFFFFu;  // the claim pass's map: this old slot moves nowhere
 
-__device__ __forceinline__ uint32_t grow_rule_of_slot(const PRule* rules, uint32_t n_rules, uint64_t g) {
-    uint32_t lo = 0, hi = n_rules;  // rules sorted by table_base; slot g belongs to the last base <= g
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (rules[mid].table_base <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o, 64);
-    return v;
-}
-
 }  // namespace
 
 // np: the new rules (table_base / table_mask of the grown sub-tables) and the cleared new table; orules / old: the
 // tables in force. Rule i of both lists is the same rule.
 __global__ void __launch_bounds__(256) k_pgrow(PArgs np, const PRule* orules, const PSlot* old, uint64_t old_total) {
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < old_total; g += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t ri = grow_rule_of_slot(orules, np.n_rules, g);
+        const uint32_t ri = rule_of_slot(orules, np.n_rules, g);
         const PRule o = orules[ri];
         const PRule r = np.rules[ri];
         const PSlot s = old[g];
@@ -70,8 +54,8 @@ __global__ void __launch_bounds__(256) k_ptable_used(const PSlot* table, uint64_
         ++used;
         live += s.flags != 0;
     }
-    used = wave_sum_u64(used);
-    live = wave_sum_u64(live);
+    used = (uint64_t)wave_sum((int64_t)used);
+    live = (uint64_t)wave_sum((int64_t)live);
     if (__lane_id() == 0 && used) {
         atomicAdd(out, (unsigned long long)used);
         if (live) atomicAdd(out + 1, (unsigned long long)live);
@@ -128,8 +112,8 @@ __global__ void __launch_bounds__(256) k_cptable_used(const uint64_t* keys, cons
         for (int j = 0; j < S && !l; ++j) l = src[j].start != INT64_MIN;
         live += l;
     }
-    used = wave_sum_u64(used);
-    live = wave_sum_u64(live);
+    used = (uint64_t)wave_sum((int64_t)used);
+    live = (uint64_t)wave_sum((int64_t)live);
     if (__lane_id() == 0 && used) {
         atomicAdd(out, (unsigned long long)used);
         if (live) atomicAdd(out + 1, (unsigned long long)live);
@@ -145,7 +129,7 @@ struct SweepTally {
     __device__ __forceinline__ void flush(unsigned long long* cnt) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const uint64_t s = wave_sum_u64(n[k]);
+            const uint64_t s = (uint64_t)wave_sum((int64_t)n[k]);
             if (__lane_id() == 0 && s) atomicAdd(cnt + k, (unsigned long long)s);
         }
     }
@@ -156,7 +140,7 @@ struct SweepTally {
 __global__ void __launch_bounds__(256) k_psweep(PArgs np, const PSlot* old, int64_t now, unsigned long long* cnt) {
     SweepTally tally;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < np.total_slots; g += (uint64_t)gridDim.x * blockDim.x) {
-        const PRule r = np.rules[grow_rule_of_slot(np.rules, np.n_rules, g)];
+        const PRule r = np.rules[rule_of_slot(np.rules, np.n_rules, g)];
         const PSlot s = old[g];
         const bool side = g == r.table_base + r.table_mask + 1;
         if (!side && s.value == kEmptyValue) continue;

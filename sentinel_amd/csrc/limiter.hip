@@ -31,16 +31,6 @@ constexpr int kLimTile = 4096;
 constexpr int kLimRounds = kLimTile / kLimThreads;
 constexpr int kLimLocalPeriods = 8;  // periods a tile aggregates in LDS before falling back to atomics
 
-__device__ __forceinline__ uint32_t lim_period_of(const uint32_t* bnd, uint32_t np, uint32_t idx) {
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (bnd[mid] <= idx) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(kLimThreads) k_lim_count(BatchArgs a, LimArgs L) {
     __shared__ uint32_t tot[kMaxLim];
     __shared__ uint32_t arr[kMaxLim][kLimLocalPeriods];
@@ -51,7 +41,7 @@ __global__ void __launch_bounds__(kLimThreads) k_lim_count(BatchArgs a, LimArgs 
     const uint32_t np = a.np[L.wl_idx];
     if (tid < kMaxLim) tot[tid] = 0;
     if (tid < kMaxLim * kLimLocalPeriods) arr[tid / kLimLocalPeriods][tid % kLimLocalPeriods] = 0;
-    if (tid == 0) q_first = lim_period_of(bnd, np, (uint32_t)base);
+    if (tid == 0) q_first = period_of(bnd, np, (uint32_t)base);
     __syncthreads();
     const uint32_t q0 = q_first;
     for (int r = 0; r < kLimRounds; ++r) {
@@ -69,7 +59,7 @@ __global__ void __launch_bounds__(kLimThreads) k_lim_count(BatchArgs a, LimArgs 
             if (m < 0 || m >= (int64_t)L.n_ms) atomicOr(a.err, kErrExchange);
         } else if (slot != 0xFF) {
             atomicAdd(&tot[slot], 1u);
-            const uint32_t q = lim_period_of(bnd, np, (uint32_t)i);
+            const uint32_t q = period_of(bnd, np, (uint32_t)i);
             if (q - q0 < (uint32_t)kLimLocalPeriods) atomicAdd(&arr[slot][q - q0], 1u);
             else atomicAdd(&L.arrivals[(size_t)slot * kMaxPeriods + q], 1u);
         }
@@ -277,7 +267,7 @@ __global__ void __launch_bounds__(kLimThreads) k_lim_apply(BatchArgs a, LimArgs 
                 q = (m + (uint32_t)(L.t_base % kLimWindowMs)) / kLimWindowMs;
                 rank = (int64_t)C + (int64_t)((const int32_t*)L.arrivals)[(size_t)slot * kMaxPeriods + m];
             } else {
-                q = lim_period_of(bnd, np, (uint32_t)i);
+                q = period_of(bnd, np, (uint32_t)i);
                 rank = (int64_t)C - (int64_t)L.prefix[(size_t)slot * kMaxPeriods + q];
             }
             if (rank >= (int64_t)L.quota[(size_t)slot * kMaxPeriods + q]) {

@@ -20,37 +20,7 @@ namespace sg {
 
 namespace {
 
-__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
-
-__device__ __forceinline__ int32_t java_d2i(double x) {  // JLS §5.1.3
-    if (x != x) return 0;
-    if (x >= 2147483647.0) return INT32_MAX;
-    if (x <= -2147483648.0) return INT32_MIN;
-    return (int32_t)x;
-}
-
 __device__ __forceinline__ double qps_of(int64_t sum, double isec) { return avg_div((double)sum, isec); }
-
-__device__ __forceinline__ int64_t wave_sum(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((long long)v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ int64_t wave_min(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (int64_t)__shfl_xor((long long)v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ int64_t wave_incl_scan(int64_t v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t y = __shfl_up((long long)v, (unsigned)o, 64);
-        if (lane >= o) v += y;
-    }
-    return v;
-}
 
 // v of lane src (wave-uniform src): v_readlane, not an LDS permute round trip
 __device__ __forceinline__ int bcast32(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
@@ -59,7 +29,6 @@ __device__ __forceinline__ int64_t bcast64(int64_t v, int src) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
-__device__ __forceinline__ uint64_t below(int f) { return f >= 64 ? ~0ull : ((1ull << f) - 1ull); }
 
 // Loads / stores through a pointer known to address global memory: global_load / global_store, counted by vmcnt
 // alone — a flat access (what a generic pointer reached through a non-kernel function's arguments gets) also counts
@@ -82,16 +51,6 @@ __device__ __forceinline__ void gstore(T* p, const T& v) {
     W w;
     __builtin_memcpy(&w, &v, sizeof(T));
     *(GW*)p = w;
-}
-
-__device__ __forceinline__ uint32_t period_of(const uint32_t* bnd, uint32_t np, uint32_t idx) {
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (bnd[mid] <= idx) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 struct Cursor {  // window period of monotonically increasing request indices (see PeriodCursor)
@@ -905,28 +864,6 @@ __global__ void __launch_bounds__(256, SG_LWALK_BLOCKS) k_lwalk_short(LArgs a, B
     }
 }
 
-// First position p in [lo, hi) with pred(p) (monotone), hi if none: 64-way wave search.
-template <class Pred>
-__device__ __forceinline__ uint64_t lwave_search(uint64_t lo, uint64_t hi, Pred pred, int lane) {
-    while (hi - lo > 64) {
-        const uint64_t step = (hi - lo + 63) / 64;
-        const uint64_t p = lo + (uint64_t)lane * step;
-        const uint64_t m = __ballot(p >= hi || pred(p));
-        if (m == 0) {
-            lo = lo + 63 * step + 1;
-            continue;
-        }
-        const int f = __builtin_ctzll(m);
-        if (f == 0) return lo;
-        const uint64_t nhi = lo + (uint64_t)f * step;
-        lo = lo + (uint64_t)(f - 1) * step + 1;
-        hi = nhi < hi ? nhi : hi;
-    }
-    const uint64_t p = lo + (uint64_t)lane;
-    const uint64_t m = __ballot(p < hi && pred(p));
-    return m ? lo + (uint64_t)__builtin_ctzll(m) : hi;
-}
-
 // ------------------------------------------------------------------------------- wave walker
 
 // One wave per hot resource. Events come 64 at a time (lane = event); a chunk is cut into runs of equal
@@ -952,7 +889,7 @@ __device__ void lwalk_wave(const LArgs& a, const uint32_t* const* bndp, uint32_t
     // the resource's exits in the sorted exit list, consumed in order; the end of the current pair of
     // window periods, found once per pair
     const uint32_t ne = a.exit_cnt[0];
-    uint64_t xi = may_skip ? lwave_search(0, ne, [&](uint64_t i) { return (uint64_t)a.exit_pos[i] >= s; }, lane) : ne;
+    uint64_t xi = may_skip ? search64(0, ne, [&](uint64_t i) { return (uint64_t)a.exit_pos[i] >= s; }, lane) : ne;
     uint32_t pe_qs = 0xFFFFFFFFu, pe_qm = 0xFFFFFFFFu;
     uint64_t pe = 0;
     // the next chunk's records and event timestamps are loaded while this chunk is decided (records at the chunk's
@@ -1260,24 +1197,6 @@ __global__ void __launch_bounds__(256, SG_LWALK_BLOCKS) k_lwalk_long(LArgs a, Ba
 // in registers (LNode); an origin node is opened from memory for the event that needs it.
 
 namespace {
-
-__device__ __forceinline__ int64_t java_d2l(double x) {  // JLS §5.1.3
-    if (x != x) return 0;
-    if (x >= 9223372036854775807.0) return INT64_MAX;
-    if (x <= -9223372036854775808.0) return INT64_MIN;
-    return (int64_t)x;
-}
-
-__device__ __forceinline__ int64_t java_round(double a) {  // Math.round(double), floor(a + 1/2) on the bits
-    const int64_t bits = __double_as_longlong(a);
-    const int64_t shift = (52 - 1 + 1023) - ((bits & 0x7FF0000000000000LL) >> 52);
-    if ((shift & -64) == 0) {
-        int64_t r = (bits & 0x000FFFFFFFFFFFFFLL) | 0x0010000000000000LL;
-        if (bits < 0) r = -r;
-        return ((r >> shift) + 1) >> 1;
-    }
-    return java_d2l(a);
-}
 
 // WarmUpController.coolDownTokens (WarmUpController.java:161-175)
 __device__ int64_t warm_cool_down(const LFlowRule& r, const LCtl& c, int64_t ct, int64_t pass_qps) {

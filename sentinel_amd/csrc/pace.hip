@@ -21,31 +21,15 @@
 //                   bucket admits advances latestPassedTime, every pending request before it is blocked;
 //                   requests before the earliest instant any of them could pass are jumped over by a
 //                   64-way search (a saturated rule costs a few searches per admitted request)
-#include "engine.h"
+#include "mstable_dev.h"
 
 namespace sg {
 
 namespace {
 
-__device__ __forceinline__ int64_t pace_java_round(double a) {
-    // java.lang.Math.round(double) (JDK 7u+): floor(a + 1/2) on the bits, saturating
-    const int64_t bits = __double_as_longlong(a);
-    const int64_t biased_exp = (bits & 0x7FF0000000000000LL) >> 52;
-    const int64_t shift = (52 - 1 + 1023) - biased_exp;
-    if ((shift & -64) == 0) {
-        int64_t r = (bits & 0x000FFFFFFFFFFFFFLL) | 0x0010000000000000LL;
-        if (bits < 0) r = -r;
-        return ((r >> shift) + 1) >> 1;
-    }
-    if (a != a) return 0;
-    if (a >= 9223372036854775807.0) return INT64_MAX;
-    if (a <= -9223372036854775808.0) return INT64_MIN;
-    return (int64_t)a;
-}
-
 // costTime = Math.round(1.0 * acquireCount / count * 1000) (:59)
 __device__ __forceinline__ int64_t pace_cost(double count, int32_t acq) {
-    return pace_java_round(1.0 * (double)acq / count * 1000.0);
+    return java_round(1.0 * (double)acq / count * 1000.0);
 }
 
 __device__ __forceinline__ int64_t wrap_add(int64_t a, int64_t b) {
@@ -65,28 +49,6 @@ __device__ __forceinline__ int32_t pace_step(int64_t& latest, int64_t cost, int3
     return (int32_t)wait;
 }
 
-// First q in [lo, hi) with pred(q) (pred monotone: false…false true…true), else hi; 64 probes per round.
-template <class Pred>
-__device__ __forceinline__ uint64_t pace_wave_search(uint64_t lo, uint64_t hi, Pred pred, int lane) {
-    while (hi - lo > 64) {
-        const uint64_t step = (hi - lo + 63) / 64;
-        const uint64_t q = lo + (uint64_t)lane * step;
-        const uint64_t m = __ballot(q >= hi || pred(q));
-        if (m == 0) {
-            lo = lo + 63 * step + 1;
-            continue;
-        }
-        const int f = __builtin_ctzll(m);
-        if (f == 0) return lo;
-        const uint64_t nhi = lo + (uint64_t)f * step;
-        lo = lo + (uint64_t)(f - 1) * step + 1;
-        hi = nhi < hi ? nhi : hi;
-    }
-    const uint64_t q = lo + (uint64_t)lane;
-    const uint64_t m = __ballot(q < hi && pred(q));
-    return m ? lo + (uint64_t)__builtin_ctzll(m) : hi;
-}
-
 // A window start for the wave walker: some q <= a with a - q < 64, a = the first q in [lo, hi) with pred(q)
 // (monotone), hi if none. The walker's step takes 64 requests from q, and those before a are blocked anyway, so the
 // search stops as soon as the bracket is 64 wide and its last round doubles as the step's load. One round of 64
@@ -94,7 +56,7 @@ __device__ __forceinline__ uint64_t pace_wave_search(uint64_t lo, uint64_t hi, P
 // a gallop past the last probe or a 64-way search before the first.
 template <class Pred>
 __device__ __forceinline__ uint64_t pace_window(uint64_t lo, uint64_t hi, Pred pred, int lane) {
-    while (hi - lo > 64) {
+    while (hi - lo > 64) {  // search64's narrowing loop without its tail (sharing the loop changes both functions' code)
         const uint64_t step = (hi - lo + 63) / 64;
         const uint64_t q = lo + (uint64_t)lane * step;
         const uint64_t m = __ballot(q >= hi || pred(q));
@@ -142,7 +104,6 @@ __device__ __forceinline__ uint64_t pace_guess_window(uint64_t lo, uint64_t hi, 
 // every millisecond), so neither the rule table nor the requests are gathered per request — count <= 0 (:53-55) is
 // answered by the walkers once per rule.
 constexpr uint32_t kPcAesc = 255;
-constexpr uint32_t kPcLdsMs = 4096;  // millisecond table entries staged in LDS (a batch spanning <= 4 s)
 
 __global__ void __launch_bounds__(256) k_pace_prep(PaceArgs p) {
     const uint64_t none = (uint64_t)p.n_rules << p.gshift;
@@ -151,17 +112,7 @@ __global__ void __launch_bounds__(256) k_pace_prep(PaceArgs p) {
         const sg_pace_req q = p.req[i];
         const int64_t tp = i == 0 ? *p.last_ts : p.req[i - 1].ts_ms;
         if (q.ts_ms < 0 || q.ts_ms < tp) atomicOr(p.err, kErrTime);
-        if (i == 0) {
-            *p.mt0 = q.ts_ms;
-        } else if (q.ts_ms > tp) {  // a new millisecond starts at i
-            for (int64_t ms = (tp < t0 ? t0 : tp) + 1; ms <= q.ts_ms; ++ms) {
-                const int64_t qq = ms - t0;
-                if (qq >= (int64_t)kMaxPeriods) break;
-                p.msb[qq] = (uint32_t)i;
-            }
-        }
-        if (i == p.n - 1) *p.mnp = (uint32_t)min(q.ts_ms - t0 + 1, (int64_t)kMaxPeriods + 1);
-        if ((i & ((1ull << p.bshift) - 1ull)) == 0) p.mbk[i >> p.bshift] = (uint16_t)min(max(q.ts_ms - t0, (int64_t)0), (int64_t)65535);
+        ms_prep(p, i, q.ts_ms, tp, t0);
         uint64_t rec = none;
         int32_t out = SG_PACE_BLOCKED;  // a walked request passes by its walker; count <= 0 leaves it blocked
         if (q.rule >= p.n_rules || q.acquire <= 0) {
@@ -173,42 +124,6 @@ __global__ void __launch_bounds__(256) k_pace_prep(PaceArgs p) {
         p.out[i] = out;
         p.rec[i] = rec;
     }
-}
-
-__shared__ uint32_t pc_sms[kPcLdsMs];
-__shared__ uint16_t pc_sbk[kPcBuckets];  // the millisecond of request b << bshift
-__shared__ uint32_t pc_nms;  // table entries in LDS, 0: read the timestamps
-__shared__ uint32_t pc_nbk;
-__shared__ int64_t pc_t0;
-
-__device__ __forceinline__ void pc_stage_ms(const PaceArgs& p) {
-    const uint32_t np = *p.mnp;
-    const bool lds = np <= kPcLdsMs;
-    const uint32_t nb = (uint32_t)((p.n - 1) >> p.bshift) + 1;
-    for (uint32_t x = threadIdx.x; lds && x < np; x += blockDim.x) pc_sms[x] = p.msb[x];
-    for (uint32_t x = threadIdx.x; lds && x < nb; x += blockDim.x) pc_sbk[x] = p.mbk[x];
-    if (threadIdx.x == 0) {
-        pc_nms = lds ? np : 0u;
-        pc_nbk = nb;
-        pc_t0 = *p.mt0;
-    }
-    __syncthreads();
-}
-
-// A request's timestamp: the largest millisecond q whose first request index table[q] <= idx. Its bucket's first
-// request and the next bucket's bound q to a few milliseconds (a bucket of a 16M batch holds 8192 requests), so the
-// binary search takes a step or two instead of twelve.
-__device__ __forceinline__ int64_t pc_ts(const PaceArgs& p, uint32_t idx) {
-    const uint32_t np = pc_nms;
-    if (np == 0) return p.req[idx].ts_ms;
-    const uint32_t b = idx >> p.bshift;
-    uint32_t lo = pc_sbk[b], hi = b + 1 < pc_nbk ? (uint32_t)pc_sbk[b + 1] + 1u : np;  // table[lo] <= idx (entry 0 unused)
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (pc_sms[mid] <= idx) lo = mid;
-        else hi = mid;
-    }
-    return pc_t0 + (int64_t)lo;
 }
 
 __device__ __forceinline__ int32_t pc_acq(const PaceArgs& p, uint64_t rec, uint32_t idx) {
@@ -278,7 +193,7 @@ __global__ void __launch_bounds__(256) k_pace_seg(PaceArgs p, uint64_t chunk) {
 // One lane per rule of at most short_max requests, the longest length class first.
 __global__ void __launch_bounds__(256) k_pace_short(PaceArgs p) {
     if (*p.err) return;
-    pc_stage_ms(p);
+    ms_stage(p);
     uint32_t cc[kClasses], total = 0;
 #pragma unroll
     for (int c = 0; c < kClasses; ++c) {
@@ -299,7 +214,7 @@ __global__ void __launch_bounds__(256) k_pace_short(PaceArgs p) {
             const uint64_t cur = rec;
             rec = ++k < p.n ? p.rec_sorted[k] : ~0ull;
             const uint32_t idx = (uint32_t)(cur & p.imask);
-            const int32_t w8 = pace_step(latest, pace_cost(r.count, pc_acq(p, cur, idx)), r.max_queueing_ms, pc_ts(p, idx));
+            const int32_t w8 = pace_step(latest, pace_cost(r.count, pc_acq(p, cur, idx)), r.max_queueing_ms, ms_ts(p, idx));
             if (w8 != SG_PACE_BLOCKED) p.out[idx] = w8;
         }
         p.latest[g] = latest;
@@ -308,7 +223,7 @@ __global__ void __launch_bounds__(256) k_pace_short(PaceArgs p) {
 
 __global__ void __launch_bounds__(256) k_pace_long(PaceArgs p) {
     if (*p.err) return;
-    pc_stage_ms(p);
+    ms_stage(p);
     const uint32_t cnt = *p.long_count;
     const uint32_t wave = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
     const uint32_t nwaves = gridDim.x * (blockDim.x / 64);
@@ -332,12 +247,12 @@ __global__ void __launch_bounds__(256) k_pace_long(PaceArgs p) {
         const int64_t cost1 = pace_cost(r.count, 1);
         const int64_t cost_max = pace_cost(r.count, INT32_MAX);
         const int64_t slack = r.max_queueing_ms > 0 ? (int64_t)r.max_queueing_ms : 0;
-        auto ts_at = [&](uint64_t q) { return pc_ts(p, (uint32_t)(p.rec_sorted[q] & p.imask)); };
+        auto ts_at = [&](uint64_t q) { return ms_ts(p, (uint32_t)(p.rec_sorted[q] & p.imask)); };
         // With the millisecond table in LDS the horizon becomes a request index (the first request of its
         // millisecond) and the search compares record indices, no timestamp lookups. Its first probes are
         // guessed: the rule's requests are spread over the batch at density (e - s) / (index span), so the
         // answer lies about (index distance) x density past the last admitted request, within a few sqrt of it.
-        const bool tab = pc_nms != 0;
+        const bool tab = ms_nms != 0;
         uint64_t hq = s;
         uint32_t hidx = (uint32_t)(p.rec_sorted[s] & p.imask);
         const double dens = (double)(e - s) / ((double)(uint32_t)(p.rec_sorted[e - 1] & p.imask) - (double)hidx + 1.0);
@@ -349,10 +264,10 @@ __global__ void __launch_bounds__(256) k_pace_long(PaceArgs p) {
                 horizon -= slack;
                 seek = false;
                 if (tab) {
-                    const int64_t x = horizon - pc_t0;
-                    if (x >= (int64_t)pc_nms) break;  // past the batch's last millisecond: the rest is blocked
+                    const int64_t x = horizon - ms_t0;
+                    if (x >= (int64_t)ms_nms) break;  // past the batch's last millisecond: the rest is blocked
                     if (x >= 1) {
-                        const uint32_t ih = pc_sms[x];
+                        const uint32_t ih = ms_sms[x];
                         const double d = ((double)ih - (double)hidx) * dens;
                         const uint64_t gq = hq + (d > 0.0 ? (uint64_t)d : 0ull);
                         const uint64_t w = (uint64_t)(sqrt(d > 0.0 ? d : 0.0) * 0.125) + 1ull;
@@ -372,7 +287,7 @@ __global__ void __launch_bounds__(256) k_pace_long(PaceArgs p) {
             if (act) {
                 const uint64_t rec = p.rec_sorted[j];
                 idx = (uint32_t)(rec & p.imask);
-                t = pc_ts(p, idx);
+                t = ms_ts(p, idx);
                 cost = pace_cost(r.count, pc_acq(p, rec, idx));
             }
             uint64_t pending = __ballot(act);

@@ -12,12 +12,12 @@
 //   k_pwalk_short / k_pwalk_long  sequential replay per slot; the wave walker decides 64 requests per
 //              step (prefix-scan admit, ballot skip) and, once the bucket cannot pay even 1 token before
 //              the next refill, jumps to the first request after the refill time by a 64-way search.
+#include "mstable_dev.h"
 #include "pslot_dev.h"
 
 namespace sg {
 
 constexpr uint32_t kPAesc = 255;    // acquire code: read req[i].acquire
-constexpr uint32_t kPLdsMs = 4096;  // millisecond table entries staged in LDS (a batch spanning <= 4 s)
 
 __global__ void __launch_bounds__(256) k_pprep(PArgs p, uint64_t sentinel) {
     const int64_t t0 = p.req[0].ts_ms;
@@ -25,18 +25,7 @@ __global__ void __launch_bounds__(256) k_pprep(PArgs p, uint64_t sentinel) {
         const sg_param_req q = p.req[i];
         const int64_t tp = i == 0 ? *p.last_ts : p.req[i - 1].ts_ms;
         if (q.ts_ms < 0 || q.ts_ms < tp) atomicOr(p.err, kErrTime);
-        // the millisecond table: request index -> timestamp for the walkers (a new millisecond starts at i)
-        if (i == 0) {
-            *p.mt0 = q.ts_ms;
-        } else if (q.ts_ms > tp) {
-            for (int64_t ms = (tp < t0 ? t0 : tp) + 1; ms <= q.ts_ms; ++ms) {
-                const int64_t qq = ms - t0;
-                if (qq >= (int64_t)kMaxPeriods) break;
-                p.msb[qq] = (uint32_t)i;
-            }
-        }
-        if (i == p.n - 1) *p.mnp = (uint32_t)min(q.ts_ms - t0 + 1, (int64_t)kMaxPeriods + 1);
-        if ((i & ((1ull << p.bshift) - 1ull)) == 0) p.mbk[i >> p.bshift] = (uint16_t)min(max(q.ts_ms - t0, (int64_t)0), (int64_t)65535);
+        ms_prep(p, i, q.ts_ms, tp, t0);
         if (q.acquire <= 0) atomicOr(p.err, kErrNonPositive);
         uint64_t rec = sentinel;
         int32_t pass = 0;
@@ -58,53 +47,6 @@ __global__ void __launch_bounds__(256) k_pprep(PArgs p, uint64_t sentinel) {
     }
 }
 
-__device__ __forceinline__ uint32_t rule_of_slot(const PArgs& p, uint64_t g) {
-    uint32_t lo = 0, hi = p.n_rules;  // rules sorted by table_base; slot g belongs to the last base <= g
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (p.rules[mid].table_base <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// The millisecond table in LDS (the hot-parameter walkers): request index -> exact timestamp (requests are
-// time-ordered), so a walker reads nothing per request but its sorted record.
-__shared__ uint32_t p_sms[kPLdsMs];
-__shared__ uint16_t p_sbk[kPcBuckets];  // the millisecond of request b << bshift
-__shared__ uint32_t p_nms;   // table entries, 0: read the timestamps
-__shared__ uint32_t p_nbk;
-__shared__ int64_t p_t0;
-
-__device__ __forceinline__ void p_stage_ms(const PArgs& p) {
-    const uint32_t np = *p.mnp;
-    const bool lds = np <= kPLdsMs;
-    const uint32_t nb = (uint32_t)((p.n - 1) >> p.bshift) + 1;
-    for (uint32_t x = threadIdx.x; lds && x < np; x += blockDim.x) p_sms[x] = p.msb[x];
-    for (uint32_t x = threadIdx.x; lds && x < nb; x += blockDim.x) p_sbk[x] = p.mbk[x];
-    if (threadIdx.x == 0) {
-        p_nms = lds ? np : 0u;
-        p_nbk = nb;
-        p_t0 = *p.mt0;
-    }
-    __syncthreads();
-}
-
-// The request's bucket bounds its millisecond to [first request's, next bucket's first request's]: a step or two
-// of binary search instead of twelve (as pace.hip's pc_ts).
-__device__ __forceinline__ int64_t p_ts(const PArgs& p, uint32_t idx) {
-    const uint32_t np = p_nms;
-    if (np == 0) return p.req[idx].ts_ms;
-    const uint32_t b = idx >> p.bshift;
-    uint32_t lo = p_sbk[b], hi = b + 1 < p_nbk ? (uint32_t)p_sbk[b + 1] + 1u : np;  // table[lo] <= idx (entry 0 unused)
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (p_sms[mid] <= idx) lo = mid;
-        else hi = mid;
-    }
-    return p_t0 + (int64_t)lo;
-}
-
 struct PDec {
     uint32_t idx;
     int64_t acq;
@@ -120,7 +62,7 @@ __device__ __forceinline__ PDec p_dec(const PArgs& p, uint64_t rec) {
 
 // Sequential replay of slot g's records from position s on (one lane), until the slot changes.
 __device__ void pwalk_serial(const PArgs& p, uint64_t g, uint64_t s) {
-    const uint32_t ri = rule_of_slot(p, g);
+    const uint32_t ri = rule_of_slot(p.rules, p.n_rules, g);
     const PRule r = p.rules[ri];
     PSlot& slot = p.table[g];
     const uint64_t value = slot.value;  // the side slot's word stays ~0, which is its value
@@ -131,7 +73,7 @@ __device__ void pwalk_serial(const PArgs& p, uint64_t g, uint64_t s) {
         const uint64_t nrec = ++j < p.n ? p.rec_sorted[j] : ~0ull;  // issued before this request is decided
         const PDec d = p_dec(p, rec);
         rec = nrec;
-        const int64_t t = p_ts(p, d.idx);
+        const int64_t t = ms_ts(p, d.idx);
         bool ok;
         if (r.behavior == 2) ok = param_throttle_step(st, throttle_cost(r, tc, d.acq), r.max_queueing_ms, t);
         else ok = param_default_step(st, tc, tc + r.burst, r.duration_sec * 1000, t, d.acq);
@@ -146,7 +88,7 @@ __device__ void pwalk_serial(const PArgs& p, uint64_t g, uint64_t s) {
 // lanes of a wave walk segments of similar length).
 __global__ void __launch_bounds__(256) k_pwalk_short(PArgs p, BatchArgs sg) {
     if (*p.err & ~kErrNonPositive) return;
-    p_stage_ms(p);
+    ms_stage(p);
     uint32_t total = 0;
     for (int k = 0; k < kClasses; ++k) total += sg.short_count[k];
     for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < total; u += gridDim.x * blockDim.x) {
@@ -156,43 +98,6 @@ __global__ void __launch_bounds__(256) k_pwalk_short(PArgs p, BatchArgs sg) {
         const uint64_t j = sg.short_list[sg.class_off[k] + r0];
         pwalk_serial(p, p.rec_sorted[j] >> p.gshift, j);
     }
-}
-
-template <class Pred>
-__device__ __forceinline__ uint64_t pwave_search(uint64_t lo, uint64_t hi, Pred pred, int lane) {
-    while (hi - lo > 64) {
-        const uint64_t step = (hi - lo + 63) / 64;
-        const uint64_t q = lo + (uint64_t)lane * step;
-        const uint64_t m = __ballot(q >= hi || pred(q));
-        if (m == 0) {
-            lo = lo + 63 * step + 1;
-            continue;
-        }
-        const int f = __builtin_ctzll(m);
-        if (f == 0) return lo;
-        const uint64_t nhi = lo + (uint64_t)f * step;
-        lo = lo + (uint64_t)(f - 1) * step + 1;
-        hi = nhi < hi ? nhi : hi;
-    }
-    const uint64_t q = lo + (uint64_t)lane;
-    const uint64_t m = __ballot(q < hi && pred(q));
-    return m ? lo + (uint64_t)__builtin_ctzll(m) : hi;
-}
-
-__device__ __forceinline__ int64_t pwave_scan(int64_t v, int lane) {
-    int64_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t y = __shfl_up((long long)x, (unsigned)o, 64);
-        if (lane >= o) x += y;
-    }
-    return x - v;
-}
-
-__device__ __forceinline__ int64_t pwave_sum(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((long long)v, o, 64);
-    return v;
 }
 
 // Token bucket for one hot (rule, value): sequential semantics, 64 requests per step.
@@ -211,7 +116,7 @@ __device__ void pwalk_wave_default(const PArgs& p, const PRule& r, int64_t tc, P
         // sequential head: first sight / refill zone
         {
             const PDec d = p_dec(p, p.rec_sorted[pos]);
-            const int64_t t = p_ts(p, d.idx);
+            const int64_t t = ms_ts(p, d.idx);
             if (!(st.flags & 1u) || t - st.time > dur_ms) {
                 if (param_default_step(st, tc, maxc, dur_ms, t, d.acq) && lane == 0) p.out[d.idx] = 1;
                 ++pos;
@@ -221,7 +126,7 @@ __device__ void pwalk_wave_default(const PArgs& p, const PRule& r, int64_t tc, P
         // no-refill zone: requests with t <= time + duration
         const int64_t zone_end_t = st.time + dur_ms;
         const uint64_t z = gallop_search(pos, e, [&](uint64_t q) {
-            return p_ts(p, (uint32_t)(p.rec_sorted[q] & p.imask)) > zone_end_t;
+            return ms_ts(p, (uint32_t)(p.rec_sorted[q] & p.imask)) > zone_end_t;
         }, lane);
         while (pos < z) {
             if (all_positive && st.tokens < 1) {  // nothing fits until the refill: all blocked
@@ -237,13 +142,13 @@ __device__ void pwalk_wave_default(const PArgs& p, const PRule& r, int64_t tc, P
             uint64_t pending = __ballot(act);
             while (pending) {
                 const bool pl = (pending >> lane) & 1ull;
-                const int64_t ex = pwave_scan(pl ? acq : 0, lane);
+                const int64_t ex = wave_excl_scan(pl ? acq : 0, lane);
                 const bool fail = pl && !(st.tokens - ex - acq >= 0);
                 const uint64_t fails = __ballot(fail);
                 const uint64_t pass = fails ? (pending & ((1ull << __builtin_ctzll(fails)) - 1ull)) : pending;
                 if (pass) {
                     if ((pass >> lane) & 1ull) p.out[idx] = 1;
-                    st.tokens -= pwave_sum(((pass >> lane) & 1ull) ? acq : 0);
+                    st.tokens -= wave_sum(((pass >> lane) & 1ull) ? acq : 0);
                 }
                 if (!fails) break;
                 const int f = __builtin_ctzll(fails);
@@ -271,7 +176,7 @@ __device__ void pwalk_wave_throttle(const PArgs& p, const PRule& r, int64_t tc, 
         if (act) {
             const PDec d = p_dec(p, p.rec_sorted[j]);
             idx = d.idx;
-            t = p_ts(p, idx);
+            t = ms_ts(p, idx);
             cost = throttle_cost(r, tc, d.acq);
         }
         uint64_t pending = __ballot(act);
@@ -302,7 +207,7 @@ __device__ void pwalk_wave_throttle(const PArgs& p, const PRule& r, int64_t tc, 
 
 __global__ void __launch_bounds__(256) k_pwalk_long(PArgs p) {
     if (*p.err & ~kErrNonPositive) return;
-    p_stage_ms(p);
+    ms_stage(p);
     const uint32_t cnt = *p.long_count;
     const uint32_t wave = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
     const uint32_t nwaves = gridDim.x * (blockDim.x / 64);
@@ -313,7 +218,7 @@ __global__ void __launch_bounds__(256) k_pwalk_long(PArgs p) {
         const uint64_t e = gallop_search(s + (p.short_max ? p.short_max : 1), p.n, [&](uint64_t q) {
             return (p.rec_sorted[q] >> p.gshift) != g;
         }, lane);
-        const uint32_t ri = rule_of_slot(p, g);
+        const uint32_t ri = rule_of_slot(p.rules, p.n_rules, g);
         const PRule r = p.rules[ri];
         PSlot& slot = p.table[g];
         const uint64_t value = slot.value;
@@ -352,7 +257,7 @@ __global__ void __launch_bounds__(256) k_ptable_clear(PSlot* table, uint64_t n) 
 __global__ void __launch_bounds__(256) k_ptable_rebuild(PArgs p, const PSlot* old) {
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < p.total_slots; g += (uint64_t)gridDim.x * blockDim.x) {
         const PSlot s = old[g];
-        const PRule r = p.rules[rule_of_slot(p, g)];
+        const PRule r = p.rules[rule_of_slot(p.rules, p.n_rules, g)];
         if (g == r.table_base + r.table_mask + 1) {
             p.table[g] = s;
             continue;

@@ -11,20 +11,9 @@ namespace sg {
 
 constexpr uint64_t kEmptyValue = ~0ull;
 
-__device__ __forceinline__ int64_t java_math_round(double a) {
-    // java.lang.Math.round(double), exact floor(a + 1/2) (JDK 7u+)
-    const int64_t bits = __double_as_longlong(a);
-    const int64_t biased_exp = (bits & 0x7FF0000000000000LL) >> 52;
-    const int64_t shift = (52 - 1 + 1023) - biased_exp;
-    if ((shift & -64) == 0) {
-        int64_t r = (bits & 0x000FFFFFFFFFFFFFLL) | 0x0010000000000000LL;
-        if (bits < 0) r = -r;
-        return ((r >> shift) + 1) >> 1;
-    }
-    if (a != a) return 0;
-    if (a >= 9223372036854775807.0) return INT64_MAX;
-    if (a <= -9223372036854775808.0) return INT64_MIN;
-    return (int64_t)a;
+// The rule whose sub-table holds global slot g: rules are sorted by table_base, g belongs to the last base <= g.
+__device__ __forceinline__ uint32_t rule_of_slot(const PRule* rules, uint32_t n_rules, uint64_t g) {
+    return last_le(0u, n_rules, g, [&](uint32_t i) { return rules[i].table_base; });
 }
 
 // tokenCount of (rule, value): the hot item's threshold, else (long) rule.count (ParamFlowChecker.java:137-141)
@@ -42,26 +31,8 @@ __device__ __forceinline__ int64_t param_token_count(const PArgs& p, const PRule
 
 // find-or-insert (rule, value) → global slot index
 __device__ __forceinline__ uint64_t param_slot(const PArgs& p, const PRule& r, uint64_t v) {
-    if (v == kEmptyValue) return r.table_base + r.table_mask + 1;  // side slot
-    uint64_t h = v + 0x9E3779B97F4A7C15ull;
-    h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
-    h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
-    h ^= h >> 31;
-    uint64_t i = h & r.table_mask;
-    for (uint64_t probes = 0; probes <= r.table_mask; ++probes) {
-        unsigned long long* vw = (unsigned long long*)&p.table[r.table_base + i].value;
-        // a plain (L2-cached) load: a slot only ever goes from empty to its value, so a stale read can only say
-        // "empty", and the CAS below then returns the value that is there (an agent-scope atomic load bypassed
-        // the XCD's L2 on every probe, also for the hot values that repeat throughout a batch)
-        const unsigned long long cur = *vw;
-        if (cur == v) return r.table_base + i;
-        if (cur == kEmptyValue) {
-            const unsigned long long old = atomicCAS(vw, (unsigned long long)kEmptyValue, (unsigned long long)v);
-            if (old == kEmptyValue || old == v) return r.table_base + i;
-        }
-        i = (i + 1) & r.table_mask;
-    }
-    return ~0ull;  // table full
+    return table_find_or_insert(r.table_base, r.table_mask, v,
+                                [&](uint64_t g) { return (unsigned long long*)&p.table[g].value; });
 }
 
 struct PState {
@@ -126,14 +97,11 @@ __device__ __forceinline__ bool param_throttle_step(PState& s, int64_t cost, int
 }
 
 __device__ __forceinline__ int64_t throttle_cost(const PRule& r, int64_t tc, int64_t acq) {
-    return java_math_round(1.0 * 1000 * (double)acq * (double)r.duration_sec / (double)tc);
+    return java_round(1.0 * 1000 * (double)acq * (double)r.duration_sec / (double)tc);
 }
 
 __device__ __forceinline__ uint64_t ps_hash(unsigned long long owner, uint64_t v) {
-    uint64_t z = v + 0x9E3779B97F4A7C15ull * (owner + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
+    return mix64_final(v + kGoldenGamma * (owner + 1));
 }
 
 __device__ __forceinline__ unsigned long long ps_owner(uint32_t res, int32_t idx) {

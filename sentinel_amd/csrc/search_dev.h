@@ -1,12 +1,53 @@
-// search_dev.h — device helpers shared by the walkers: wave-wide searches over the sorted records, the window
-// average's division.
+// search_dev.h — device helpers shared by every kernel file: the 64-lane wave primitives (sum, min, scans, lane
+// masks), wave-wide and per-lane searches over sorted data, the window average's division.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace sg {
 
-// First q in [lo, hi) with pred(q) (pred monotone false → true), hi if none: 64 evenly spaced probes per step.
+__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
+
+// the lanes below f as a ballot mask
+__device__ __forceinline__ uint64_t below(int f) { return f >= 64 ? ~0ull : ((1ull << f) - 1ull); }
+
+__device__ __forceinline__ int64_t wave_sum(int64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((long long)v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ int64_t wave_min(int64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (int64_t)__shfl_xor((long long)v, o, 64));
+    return v;
+}
+
+__device__ __forceinline__ int64_t wave_incl_scan(int64_t v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int64_t y = __shfl_up((long long)v, (unsigned)o, 64);
+        if (lane >= o) v += y;
+    }
+    return v;
+}
+
+__device__ __forceinline__ int64_t wave_excl_scan(int64_t v, int lane) { return wave_incl_scan(v, lane) - v; }
+
+// The largest i in [lo, hi) with key(i) <= x, for keys ascending and key(lo) <= x (a table whose entry lo is unused
+// or known to qualify is never read there).
+template <class I, class X, class Key>
+__device__ __forceinline__ I last_le(I lo, I hi, X x, Key key) {
+    while (hi - lo > 1) {
+        const I mid = (lo + hi) >> 1;
+        if (key(mid) <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// First q in [lo, hi) with pred(q) (pred monotone false → true), hi if none: 64 evenly spaced probes per step, so a
+// million-record range takes 4 dependent loads.
 template <class Pred>
 __device__ __forceinline__ uint64_t search64(uint64_t lo, uint64_t hi, Pred pred, int lane) {
     while (hi - lo > 64) {
@@ -44,6 +85,11 @@ __device__ __forceinline__ uint64_t gallop_search(uint64_t lo, uint64_t hi, Pred
     const uint64_t b0 = lo + (1ull << (f - 1));            // probe f - 1 (at b0 - 1) was false
     const uint64_t b1 = lo + ((1ull << f) - 1ull);          // probe f: true, or past hi
     return search64(b0, b1 < hi ? b1 : hi, pred, lane);
+}
+
+// A batch's period table: bnd[q] is the first request index of period q (entry 0 unused); the period of request idx.
+__device__ __forceinline__ uint32_t period_of(const uint32_t* bnd, uint32_t np, uint32_t idx) {
+    return last_le(0u, np, idx, [&](uint32_t q) { return bnd[q]; });
 }
 
 // One lane's own search: is v in the sorted a[0 .. n)? (AuthoritySlot's origin ids above 64: a handful per resource.)

@@ -25,8 +25,6 @@ namespace sg {
 
 namespace {
 
-__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
-
 struct SlogKey {
     int64_t ts;
     int64_t flow_id;
@@ -35,10 +33,10 @@ struct SlogKey {
 };
 
 __device__ __forceinline__ uint64_t slog_hash(const SlogKey& k) {
-    uint64_t h = lnode_hash((uint64_t)k.flow_id + 0x9E3779B97F4A7C15ull);
-    h = lnode_hash(h ^ (uint64_t)k.ts);
-    h = lnode_hash(h ^ k.value);
-    return lnode_hash(h ^ (uint64_t)k.family);
+    uint64_t h = mix64((uint64_t)k.flow_id);
+    h = mix64_final(h ^ (uint64_t)k.ts);
+    h = mix64_final(h ^ k.value);
+    return mix64_final(h ^ (uint64_t)k.family);
 }
 
 // Every lane of the wave calls it; a lane with `act` finds or claims its key's slot and adds its counters to it, and a
@@ -104,12 +102,6 @@ struct SlogCarry {
 __device__ __forceinline__ void slog_wave_flush(const SlogArgs& b, SlogCarry& c) {
     slog_wave_insert(b, c.has && lane_id() == 0, c.k, c.c, c.events, c.acq);
     c.has = false;
-}
-
-__device__ __forceinline__ int64_t wave_sum(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((long long)v, o, 64);
-    return v;
 }
 
 // What one decision adds to its key's counters: acq to the counters of m_acq, 1 to those of m_one (bit x: counter x).

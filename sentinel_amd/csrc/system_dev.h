@@ -1,4 +1,4 @@
-// system_dev.h — SystemSlot on the device (included by local.hip inside namespace sg, after its wave helpers).
+// system_dev.h — SystemSlot on the device (included by local.hip inside namespace sg, after its bcast helpers).
 //
 // SystemSlot (@Spi order -5000: after AuthoritySlot, before ParamFlowSlot) runs SystemRuleManager.checkSystem
 // (SystemRuleManager.java:290-340) for every EntryType.IN entry against Constants.ENTRY_NODE, the StatisticNode that

@@ -6,13 +6,6 @@
 
 namespace sg {
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // The canonical payload of a value of at most 8 bytes, byte k in bits [8k, 8k + 8): as on the wire, except BOOLEAN
 // 00 / 01 (readBoolean: non-zero is true) and one NaN per float width (Double.equals / Float.equals compare
 // doubleToLongBits / floatToIntBits, which collapse every NaN).

@@ -157,3 +157,24 @@ def test_pace_bursty_rules_guess_misses(span):
         w = _check(eng, ora, req, n_rules)
         assert (w == abi.PACE_BLOCKED).any() and (w > 0).any() and (w == 0).any()
         t = int(req["ts_ms"][-1]) + int(rng.integers(0, 3000))
+
+
+@pytest.mark.parametrize("flags", WALKERS)
+@pytest.mark.parametrize("span", [4095, 4096, 65535, 65536, 100_000])
+def test_pace_millisecond_table_boundaries(span, flags):
+    """The walkers recover each request's timestamp from the batch's millisecond table, found through a table of
+    request buckets (5,000 requests: 4 requests a bucket). The batch's last timestamp is its first + span exactly, a
+    table of span + 1 milliseconds: 4095 / 4096 are the last table that fits LDS and the first that does not,
+    65535 / 65536 the last the table holds and the first it cannot (the walkers then read the timestamps)."""
+    rng = np.random.default_rng(77 + span)  # one trace per span for the three walkers
+    n, n_rules = 5000, 40
+    rules = _rules(rng, n_rules)
+    eng = _engine(flags, max_batch=8192)
+    eng.pace_load_rules(rules)
+    ora = RateLimiterController(rules)
+    t0 = 1_700_000_000_000
+    req = _trace(rng, n, n_rules, t0, span)
+    req["ts_ms"][0], req["ts_ms"][-1] = t0, t0 + span  # the draw lies in [t0, t0 + span): still in time order
+    assert req["ts_ms"][0] == t0 and req["ts_ms"][-1] - req["ts_ms"][0] == span and (np.diff(req["ts_ms"]) >= 0).all()
+    w = _check(eng, ora, req, n_rules)  # every wait, and (40 rules: a stride of 1) every latestPassedTime
+    assert (w == abi.PACE_BLOCKED).any() and (w > 0).any() and (w == 0).any()

@@ -136,11 +136,13 @@ def test_param_unknown_rule_passes_and_time_errors():
 
 
 @pytest.mark.parametrize("flags", WALKERS)
-@pytest.mark.parametrize("span", [3_000, 20_000, 100_000])
+@pytest.mark.parametrize("span", [3_000, 4_095, 4_096, 20_000, 65_535, 65_536, 100_000])
 def test_batch_spans_and_large_acquire(span, flags):
     """The walkers recover each request's timestamp from the batch's millisecond table (request index -> ts, staged in
     LDS up to 4096 ms; longer batches read the timestamps) and its acquireCount from the record's 8-bit code (255 and
-    above read the request): spans across both table regimes and past the 65,536-entry table, counts up to 300."""
+    above read the request): spans across both table regimes and past the 65,536-entry table, counts up to 300. A
+    batch's last timestamp is its first + span exactly (a table of span + 1 milliseconds): 4095 / 4096 are the last
+    table that fits LDS and the first that does not, 65535 / 65536 the last the table holds and the first it cannot."""
     rng = np.random.default_rng(span)
     rules = _rules([{"count": 50, "duration": 1, "burst": 20}, {"count": 400, "duration": 2},
                     {"count": 8, "behavior": abi.BEHAVIOR_RATE_LIMITER, "max_queue": 500}])
@@ -148,5 +150,7 @@ def test_batch_spans_and_large_acquire(span, flags):
     t = 1_700_000_000_000
     for _ in range(2):
         req = _trace(rng, 40_000, len(rules), 300, t, span, acq_hi=300)
+        req["ts_ms"][0], req["ts_ms"][-1] = t, t + span  # the draw lies in [t, t + span): still in time order
+        assert req["ts_ms"][0] == t and req["ts_ms"][-1] - req["ts_ms"][0] == span and (np.diff(req["ts_ms"]) >= 0).all()
         _check(eng, ora, req)
         t = int(req["ts_ms"][-1]) + 1
