@@ -1281,15 +1281,55 @@ int sg_codec_encode_flow(sg_handle* h, const int32_t* xid, const uint8_t* kind, 
  *                    SG_E_INVAL) → ids_out[n]. How the shim names hot-item values (ParamFlowRuleUtil.parseHotItems,
  *                    typed by classType) before sg_cparam_load_rules. It runs the decoder's device pipeline.
  *   sg_vdict_lookup  ids[n] → types_out[n], offsets_out[n + 1], bytes_out (canonical payloads), HOST memory; for
- *                    sg_cparam_top_values reporting. An id of 0 or above the value count is SG_E_INVAL; bytes_cap too
- *                    small is SG_E_CAPACITY with offsets_out filled.
- *   sg_vdict_size    values and arena bytes in use.
+ *                    sg_cparam_top_values reporting. An id of 0, above the highest id handed out, or given back by
+ *                    sg_vdict_sweep and not handed out again is SG_E_INVAL; bytes_cap too small is SG_E_CAPACITY with
+ *                    offsets_out filled.
+ *   sg_vdict_size    live values and arena bytes in use.
  *   sg_vdict_grow    a larger dictionary in place: capacity_log2 (at most 28) and arena_bytes both at least what they
  *                    are (SG_E_INVAL otherwise, or before sg_vdict_init). Entries and the used arena bytes are copied
  *                    and the lookup table is rebuilt on the device from the entries; every id, sg_vdict_size,
  *                    sg_vdict_lookup and the ids handed out next (count + 1, …) are as in a dictionary that was this
  *                    large from the start. max_batch_values is unchanged. All or nothing: SG_E_NOMEM leaves the
- *                    dictionary as it was.
+ *                    dictionary as it was. After a sweep the ids given back stay given back, the free list carries over
+ *                    and the next ids are what they would have been without the growth.
+ *   sg_vdict_sweep   gives back the ids that nothing names any more. Ids stay array positions and are never renumbered
+ *                    (the value tables hash them, hot items carry them, the shim caches them): an id in [1, high] —
+ *                    high = the largest id ever handed out, it never decreases — that is not free already stays live
+ *                    iff it appears in at least one of
+ *                      1. the value word of a taken slot of a table sg_param_sweep / sg_cparam_sweep read on this
+ *                         handle: the sg_param_* table, the ParamFlowSlot chain's tables, the cluster param keys
+ *                         (the embedded token server's included);
+ *                      2. a thread-count entry of the ParamFlowSlot chain whose owner word is taken;
+ *                      3. a hot item of a rule set in force (sg_param_load_rules, sg_cparam_load_rules,
+ *                         sg_pslot_load_rules — the gateway's converted rules are loaded through the last);
+ *                      4. the gateway's "$NM" and "$D" ids, once sg_gateway_load_rules has run;
+ *                      5. a row not yet fetched from the block log with app_kind SG_BLOCK_APP_VALUE or _LABEL;
+ *                      6. a row not yet fetched from the server log of the param family (the caller resolves 5 and 6
+ *                         with sg_vdict_lookup after it fetches them: they still mean the same value);
+ *                      7. keep_ids[0 .. n_keep) (HOST memory): the ids the shim holds outside the handle.
+ *                    A table word that is no dictionary id (outside [1, high], the ~0 of a side slot) is ignored: a
+ *                    table keyed by the caller's own numbering can only keep too much. Everything else is freed: its
+ *                    entry is dead, sg_vdict_lookup of it is SG_E_INVAL, its arena bytes are reclaimed (the live long
+ *                    payloads are compacted in id order, arena_used = the sum of their lengths), n_values counts the
+ *                    live values, and the capacity refusals compare live + fresh values with the capacity and the
+ *                    compacted arena bytes + new bytes with the arena size. A live id looks up to the same type and
+ *                    bytes as before. New values then take ids as follows: the fresh values of a batch are ranked by
+ *                    first appearance, as ever; rank r takes the r-th free id in ascending order while free ids last,
+ *                    then high + 1, high + 2, …. With no free id every id is what it always was.
+ *                    No decision changes: a freed value has no entry in any table, so the request that brings it back
+ *                    is decided as a first-seen value under whatever id it gets — what the table sweeps guarantee for
+ *                    the table side.
+ *                    IN FLIGHT: an id from sg_codec_decode_param, sg_gateway_parse_batch or sg_vdict_intern that has not
+ *                    been sent through a decide call yet is in no table: list it in keep_ids, or sweep after the
+ *                    decide call. The same holds for ids the shim caches for hot items it has not loaded yet.
+ *                    The call completes enqueued work first. All or nothing: the new entries, lookup table, arena and
+ *                    free list are built beside the ones in force and swapped at the end; SG_E_NOMEM and every other
+ *                    refusal leave the handle as it was. SG_E_INVAL before anything changes: before sg_vdict_init;
+ *                    n_keep > 0 with null keep_ids; a keep_ids entry that is 0, above high or already free. No
+ *                    timestamp is involved, so there is no SG_E_TIME. *out (may be null): live, removed (by this
+ *                    call), free_ids (after the call, earlier sweeps' unused ids included), high, arena_before,
+ *                    arena_after. The shim's cycle: sweep the tables at the current time, sweep the dictionary with
+ *                    the ids it still holds, and grow only if live is still near the capacity.
  * All or nothing: a batch whose new values would exceed the capacity, or whose new long payloads the arena, returns
  * SG_E_CAPACITY and leaves the dictionary as it was — size, ids and arena.
  *
@@ -1333,6 +1373,15 @@ int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* type
                     uint8_t* bytes_out, uint64_t bytes_cap);
 int sg_vdict_size(sg_handle* h, uint64_t* n_values, uint64_t* arena_used);
 int sg_vdict_grow(sg_handle* h, int32_t capacity_log2, uint64_t arena_bytes);
+typedef struct sg_vdict_sweep_stats {
+    uint64_t live;           /* values after the call                                              */
+    uint64_t removed;        /* ids this call freed                                                */
+    uint64_t free_ids;       /* free ids after the call: removed + earlier sweeps' not yet reused  */
+    uint64_t high;           /* the largest id ever handed out                                     */
+    uint64_t arena_before;   /* arena bytes in use before                                          */
+    uint64_t arena_after;    /* ... and after: the sum of the live payloads longer than 8 bytes    */
+} sg_vdict_sweep_stats;
+int sg_vdict_sweep(sg_handle* h, const uint64_t* keep_ids, uint64_t n_keep, sg_vdict_sweep_stats* out);
 int sg_codec_decode_param(sg_handle* h, const uint8_t* payload, const uint32_t* offsets, const int64_t* ts_ms,
                           uint64_t n, sg_cparam_req* req_out, uint64_t* values_out, uint64_t values_cap,
                           uint64_t* n_values, int32_t* xid_out, uint8_t* kind_out, void* stream);

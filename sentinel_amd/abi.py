@@ -79,6 +79,11 @@ class sg_vdict_config(C.Structure):
                 ("max_batch_values", C.c_uint64)]
 
 
+class sg_vdict_sweep_stats(C.Structure):
+    _fields_ = [("live", C.c_uint64), ("removed", C.c_uint64), ("free_ids", C.c_uint64), ("high", C.c_uint64),
+                ("arena_before", C.c_uint64), ("arena_after", C.c_uint64)]
+
+
 class sg_batch_stats(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("walk_ms", C.c_float), ("sort_ms", C.c_float),
                 ("touched_keys", C.c_uint64), ("long_segments", C.c_uint64), ("skipped_ranges", C.c_uint64)]
@@ -237,7 +242,7 @@ assert RES_DTYPE.itemsize == C.sizeof(sg_result) == 12
 assert RULE_DTYPE.itemsize == C.sizeof(sg_flow_rule) == 32
 assert NS_DTYPE.itemsize == C.sizeof(sg_namespace) == 16
 assert CPARAM_RULE_DTYPE.itemsize == 40 and CPARAM_REQ_DTYPE.itemsize == 24
-assert C.sizeof(sg_vdict_config) == 24
+assert C.sizeof(sg_vdict_config) == 24 and C.sizeof(sg_vdict_sweep_stats) == 48
 assert DEGRADE_RULE_DTYPE.itemsize == 32 and LOCAL_RULE_DTYPE.itemsize == 80
 assert LOCAL_EVENT_DTYPE.itemsize == 32 and LOCAL_RES_DTYPE.itemsize == 8
 assert LOCAL_FLOW_RULE_DTYPE.itemsize == 56 and SLOT_EXT_DTYPE.itemsize == 16

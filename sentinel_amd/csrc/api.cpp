@@ -18,6 +18,7 @@
 #include "devmem.h"
 #include "engine.h"
 #include "table_grow.h"
+#include "vdict_sweep.h"
 
 using namespace sg;
 
@@ -186,6 +187,10 @@ struct sg_handle {
         bool on = false;
         uint64_t capacity = 0, arena_bytes = 0, max_batch = 0;
         uint64_t count = 0, arena_used = 0;   // the device state's size: every batch ends with the host knowing it
+        // sg_vdict_sweep gives ids back: every id in [1, high] is live (count of them) or free, high = count + n_free
+        uint64_t high = 0;                    // the largest id ever handed out
+        DevBuf<uint32_t> free_ids;            // the last sweep's dead ids, ascending
+        uint64_t free_head = 0, n_free = 0;   // entries batches have taken since; entries left
         DevBuf<uint64_t> tab;
         uint64_t tab_mask = 0;
         DevBuf<VEntry> entries;
@@ -1156,8 +1161,10 @@ VDictArgs vd_args(sg_handle* h, uint64_t m, const uint8_t* src, uint64_t* ids) {
     a.tab_mask = v.tab_mask;
     a.entries = v.entries;
     a.arena = v.arena;
-    a.count = v.count;
+    a.high = v.high;
     a.arena_used = v.arena_used;
+    a.free_ids = v.free_ids.get() ? v.free_ids.get() + v.free_head : nullptr;
+    a.n_free = v.n_free;
     a.m = m;
     a.src = src;
     a.desc = v.desc;
@@ -1193,7 +1200,11 @@ int vd_finish(sg_handle* h, VDictArgs a, hipStream_t stream) {
     if (v.arena_used + bytes > v.arena_bytes) return fail(h, SG_E_CAPACITY, "value dictionary arena full");
     HIP_TRY(h, launch_vd_commit(a, stream));
     HIP_TRY(h, hipStreamSynchronize(stream));
-    v.count += fresh;
+    const VdBook b = vd_after_batch(VdBook{v.free_head, v.n_free, v.high, v.count}, fresh);
+    v.free_head = b.head;
+    v.n_free = b.n_free;
+    v.high = b.high;
+    v.count = b.live;
     v.arena_used += bytes;
     return SG_OK;
 }
@@ -1254,7 +1265,7 @@ int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* type
     if (n == 0) return SG_OK;
     if (!ids || !types_out) return fail(h, SG_E_INVAL, "null buffer");
     for (uint64_t j = 0; j < n; ++j)
-        if (ids[j] == 0 || ids[j] > h->vd.count) return fail(h, SG_E_INVAL, "unknown value id");
+        if (!vd_id_in_range(ids[j], h->vd.high)) return fail(h, SG_E_INVAL, "unknown value id");
     HIP_TRY(h, hipSetDevice(h->device));
     DevBuf<uint64_t> d_ids;
     DevBuf<VEntry> d_e;
@@ -1268,6 +1279,8 @@ int sg_vdict_lookup(sg_handle* h, const uint64_t* ids, uint64_t n, uint8_t* type
         HIP_TRY(h, hipMemcpy(d_ids, ids, 8 * n, hipMemcpyHostToDevice));
         HIP_TRY(h, launch_vd_gather(h->vd.entries, d_ids, n, d_e, nullptr));
         HIP_TRY(h, hipMemcpy(e.data(), d_e, sizeof(VEntry) * n, hipMemcpyDeviceToHost));
+        for (uint64_t j = 0; j < n; ++j)  // an id a sweep gave back and no batch has taken since
+            if (e[j].type == kVdTombType) return fail(h, SG_E_INVAL, "unknown value id");
         uint64_t total = 0;
         for (uint64_t j = 0; j < n; ++j) {
             types_out[j] = (uint8_t)e[j].type;
@@ -1297,9 +1310,10 @@ int sg_vdict_size(sg_handle* h, uint64_t* n_values, uint64_t* arena_used) {
     return SG_OK;
 }
 
-// The reference interns nothing: its maps hold the values themselves and grow. Entries [1, count] and the used arena
+// The reference interns nothing: its maps hold the values themselves and grow. Entries [1, high] and the used arena
 // bytes are copied into the larger arrays — ids are array positions, so none moves — and the main table is filled
-// again from the entries (pcodec.hip k_vd_rehash). The per-batch scratch (max_batch_values) is not touched.
+// again from the entries that are no tombstones (pcodec.hip k_vd_rehash). The free list of the last sweep stays as it
+// is: it only ever shrinks between sweeps. The per-batch scratch (max_batch_values) is not touched.
 int sg_vdict_grow(sg_handle* h, int32_t capacity_log2, uint64_t arena_bytes) {
     if (!h) return SG_E_INVAL;
     auto& v = h->vd;
@@ -1315,7 +1329,7 @@ int sg_vdict_grow(sg_handle* h, int32_t capacity_log2, uint64_t arena_bytes) {
         !arena.alloc_bytes(arena_bytes ? arena_bytes : 1))
         return fail(h, SG_E_NOMEM, "grown value dictionary");
     HIP_TRY(h, hipMemsetAsync(tab, 0, 8 * slots, nullptr));
-    HIP_TRY(h, hipMemcpyAsync(entries, v.entries, sizeof(VEntry) * (v.count + 1), hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(h, hipMemcpyAsync(entries, v.entries, sizeof(VEntry) * (v.high + 1), hipMemcpyDeviceToDevice, nullptr));
     if (v.arena_used)
         HIP_TRY(h, hipMemcpyAsync(arena, v.arena, v.arena_used, hipMemcpyDeviceToDevice, nullptr));
     VDictArgs a{};
@@ -1323,7 +1337,7 @@ int sg_vdict_grow(sg_handle* h, int32_t capacity_log2, uint64_t arena_bytes) {
     a.tab_mask = slots - 1;
     a.entries = entries;
     a.arena = arena;
-    a.count = v.count;
+    a.high = v.high;
     HIP_TRY(h, launch_vd_rehash(a, nullptr));
     HIP_TRY(h, hipDeviceSynchronize());
     v.tab = std::move(tab);
@@ -1332,6 +1346,106 @@ int sg_vdict_grow(sg_handle* h, int32_t capacity_log2, uint64_t arena_bytes) {
     v.tab_mask = slots - 1;
     v.capacity = capacity;
     v.arena_bytes = arena_bytes;
+    return SG_OK;
+}
+
+// The dictionary's own sweep, by the mechanism of the table sweeps: new entries, main table, arena and free list are
+// built beside the ones in force (vdict_sweep.hip) from the ids that something still names, and swapped in at the end.
+// Purely referential: no timestamp is read or raised. The sources are everything on this handle that holds a value
+// id between calls — the value tables sg_param_sweep / sg_cparam_sweep read, the thread counts, the hot items of the
+// rule sets in force, the gateway's two ids, the unfetched rows of both logs — and the caller's keep list.
+int sg_vdict_sweep(sg_handle* h, const uint64_t* keep_ids, uint64_t n_keep, sg_vdict_sweep_stats* out) {
+    if (!h) return SG_E_INVAL;
+    auto& v = h->vd;
+    VdsRefusal ref = vd_sweep_refusal(v.on, n_keep, keep_ids == nullptr, 0);
+    if (ref.code) return fail(h, ref.code, ref.why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    drain_async(h);
+    HIP_TRY(h, hipDeviceSynchronize());  // batches on the caller's streams: their table writes are sources
+    uint64_t bad = 0;
+    for (uint64_t j = 0; j < n_keep; ++j) bad += !vd_id_in_range(keep_ids[j], v.high);
+    ref = vd_sweep_refusal(true, n_keep, false, bad);
+    if (ref.code) return fail(h, ref.code, ref.why);
+    sg_vdict_sweep_stats st{};
+    st.high = v.high;
+    st.live = v.count;
+    st.free_ids = v.n_free;
+    st.arena_before = st.arena_after = v.arena_used;
+    if (v.high == 0) {  // nothing was ever interned
+        if (out) *out = st;
+        return SG_OK;
+    }
+    const uint64_t high = v.high, words = (high >> 5) + 1, slots = 2 * v.capacity;
+    const uint64_t gw_ids[2] = {h->gw.nm_id, h->gw.d_id};
+    const uint64_t n_gw = h->gw.on ? 2 : 0;
+    DevBuf<uint32_t> d_bits, d_free;
+    DevBuf<uint64_t> d_dead, d_bytes, d_sums, d_tot, d_keep, tab;
+    DevBuf<VEntry> entries;
+    DevBuf<uint8_t> arena;
+    if (!d_bits.alloc(words) || !d_dead.alloc(high) || !d_bytes.alloc(high) || !d_sums.alloc(scan_blocks(high) + 1) ||
+        !d_tot.alloc(3) || !d_keep.alloc(n_keep + 2) || !tab.alloc(slots) || !entries.alloc(v.capacity + 1) ||
+        !arena.alloc(v.arena_bytes ? v.arena_bytes : 1))
+        return fail(h, SG_E_NOMEM, "swept value dictionary");
+    HIP_TRY(h, hipMemsetAsync(d_bits, 0, 4 * words, nullptr));
+    HIP_TRY(h, hipMemsetAsync(d_tot, 0, 24, nullptr));
+    HIP_TRY(h, hipMemsetAsync(tab, 0, 8 * slots, nullptr));
+    if (n_keep) HIP_TRY(h, hipMemcpy(d_keep, keep_ids, 8 * n_keep, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_keep + n_keep, gw_ids, 16, hipMemcpyHostToDevice));
+    // the mark passes, one per kind of source; the extents are this handle's own sizes
+    constexpr uint32_t kPSlotWords = sizeof(PSlot) / 8, kThreadWords = sizeof(PSThread) / 8, kHotWords = sizeof(sg_param_hot_item) / 8;
+    static_assert(offsetof(PSlot, value) == 0 && offsetof(PSThread, owner) == 0 && offsetof(PSThread, value) == 8 &&
+                      offsetof(sg_param_hot_item, value) == 0,
+                  "word offsets of the strided mark pass");
+    HIP_TRY(h, launch_vds_mark_words(d_bits, high, reinterpret_cast<const uint64_t*>(h->d_ptable.get()), h->ptotal,
+                                     kPSlotWords, 0, -1, nullptr));
+    HIP_TRY(h, launch_vds_mark_words(d_bits, high, h->d_cpkeys, h->cptotal, 1, 0, -1, nullptr));
+    if (h->ps_loaded)
+        HIP_TRY(h, launch_vds_mark_words(d_bits, high, reinterpret_cast<const uint64_t*>(h->d_ps_tc.get()), h->ps_tc_slots,
+                                         kThreadWords, 1, 0, nullptr));
+    HIP_TRY(h, launch_vds_mark_words(d_bits, high, reinterpret_cast<const uint64_t*>(h->d_phot.get()), h->d_phot.size(),
+                                     kHotWords, 0, -1, nullptr));
+    HIP_TRY(h, launch_vds_mark_words(d_bits, high, reinterpret_cast<const uint64_t*>(h->d_cphot.get()), h->d_cphot.size(),
+                                     kHotWords, 0, -1, nullptr));
+    HIP_TRY(h, launch_vds_mark_words(d_bits, high, d_keep + n_keep, n_gw, 1, 0, -1, nullptr));
+    HIP_TRY(h, launch_vds_mark_blog(d_bits, high, h->d_blog, h->d_blog.size(), nullptr));
+    HIP_TRY(h, launch_vds_mark_slog(d_bits, high, h->d_slog, h->d_slog.size(), nullptr));
+    HIP_TRY(h, launch_vds_mark_keep(d_bits, high, d_keep, n_keep, v.entries, reinterpret_cast<unsigned long long*>(d_tot + 2),
+                                    nullptr));
+    VdSweepArgs a{};
+    a.entries = v.entries;
+    a.arena = v.arena;
+    a.high = high;
+    a.bits = d_bits;
+    a.dead = d_dead;
+    a.bytes = d_bytes;
+    HIP_TRY(h, launch_vds_flags(a, nullptr));
+    HIP_TRY(h, launch_scan_u64(d_dead, high, d_sums, d_tot, nullptr));
+    HIP_TRY(h, launch_scan_u64(d_bytes, high, d_sums, d_tot + 1, nullptr));
+    uint64_t tot[3] = {0, 0, 0};  // dead ids, live arena bytes, bad keep entries
+    HIP_TRY(h, hipMemcpy(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost));
+    ref = vd_sweep_refusal(true, n_keep, false, tot[2]);
+    if (ref.code) return fail(h, ref.code, ref.why);
+    if (!d_free.alloc(tot[0] ? tot[0] : 1)) return fail(h, SG_E_NOMEM, "swept value dictionary");
+    a.n_entries = entries;
+    a.n_tab = tab;
+    a.n_tab_mask = slots - 1;
+    a.n_arena = arena;
+    a.n_free_ids = d_free;
+    HIP_TRY(h, launch_vds_move(a, nullptr));
+    HIP_TRY(h, hipDeviceSynchronize());
+    st.removed = tot[0] - v.n_free;  // the ids free before are dead again: they are not removed twice
+    st.live = high - tot[0];
+    st.free_ids = tot[0];
+    st.arena_after = tot[1];
+    v.tab = std::move(tab);
+    v.entries = std::move(entries);
+    v.arena = std::move(arena);
+    v.free_ids = std::move(d_free);
+    v.free_head = 0;
+    v.n_free = tot[0];
+    v.count = st.live;
+    v.arena_used = tot[1];
+    if (out) *out = st;
     return SG_OK;
 }
 

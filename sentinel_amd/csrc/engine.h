@@ -1202,8 +1202,10 @@ struct VDictArgs {
     uint64_t tab_mask;
     VEntry* entries;        // [capacity + 1], entry 0 unused
     uint8_t* arena;
-    uint64_t count;         // values before this batch
+    uint64_t high;          // the largest id handed out before this batch
     uint64_t arena_used;
+    const uint32_t* free_ids;  // [n_free] the ids a sweep gave back and no batch has taken since, ascending: the
+    uint64_t n_free;           // fresh value of rank r takes free_ids[r], past them high + 1 + (r - n_free)
     // the batch
     uint64_t m;             // values
     const uint8_t* src;     // the bytes VDesc.off points into
@@ -1249,11 +1251,41 @@ hipError_t launch_pcodec_encode(const PCodecArgs& c, hipStream_t stream);
 hipError_t launch_vd_host_lookup(const VDictArgs& v, hipStream_t stream);
 hipError_t launch_vd_dedupe(const VDictArgs& v, hipStream_t stream);   // misses → dedupe table, representative flags
 hipError_t launch_vd_commit(const VDictArgs& v, hipStream_t stream);   // append + insert the new values, ids of all misses
-// the main table (zeroed, v.tab_mask) filled again from entries [1, v.count]: each entry's hash recomputed from its payload
+// the main table (zeroed, v.tab_mask) filled again from the entries in [1, v.high] that are no tombstones: each entry's
+// hash recomputed from its payload
 hipError_t launch_vd_rehash(const VDictArgs& v, hipStream_t stream);
 hipError_t launch_vd_gather(const VEntry* entries, const uint64_t* ids, uint64_t n, VEntry* out, hipStream_t stream);
 hipError_t launch_vd_bytes(const VEntry* e, const uint32_t* offsets, uint64_t n, const uint8_t* arena, uint8_t* out,
                            hipStream_t stream);
+
+// ---- sg_vdict_sweep (vdict_sweep.hip; the host-side rules are in vdict_sweep.h) ----
+
+struct VdSweepArgs {
+    const VEntry* entries;  // the dictionary in force
+    const uint8_t* arena;
+    uint64_t high;
+    const uint32_t* bits;   // [(high >> 5) + 1] the mark passes' bitmap, bit id
+    uint64_t* dead;         // [high] at id - 1: 1 for a dead id, then the exclusive scan (its place in the free list)
+    uint64_t* bytes;        // [high] at id - 1: a live long payload's length, then the scan (its new arena offset)
+    // the dictionary beside it (launch_vds_move)
+    VEntry* n_entries;
+    uint64_t* n_tab;        // zeroed
+    uint64_t n_tab_mask;
+    uint8_t* n_arena;
+    uint32_t* n_free_ids;   // [the dead total]
+};
+
+// words[i * stride + value_off], i < n, as ids into the zeroed bitmap; guard_off >= 0: only where words[i * stride +
+// guard_off] is a taken PSThread owner word. A word outside [1, high] is no id and marks nothing.
+hipError_t launch_vds_mark_words(uint32_t* bits, uint64_t high, const uint64_t* words, uint64_t n, uint32_t stride,
+                                 uint32_t value_off, int guard_off, hipStream_t stream);
+hipError_t launch_vds_mark_blog(uint32_t* bits, uint64_t high, const BlogSlot* tab, uint64_t slots, hipStream_t stream);
+hipError_t launch_vds_mark_slog(uint32_t* bits, uint64_t high, const SlogSlot* tab, uint64_t slots, hipStream_t stream);
+// *bad += the keep entries that are 0, above high or tombstones; the others are marked
+hipError_t launch_vds_mark_keep(uint32_t* bits, uint64_t high, const uint64_t* keep, uint64_t n, const VEntry* entries,
+                                unsigned long long* bad, hipStream_t stream);
+hipError_t launch_vds_flags(const VdSweepArgs& a, hipStream_t stream);
+hipError_t launch_vds_move(const VdSweepArgs& a, hipStream_t stream);
 
 // ---- GatewayFlowSlot's request parameter parser (gateway.hip; the tables come from gateway_rules.h) ----
 

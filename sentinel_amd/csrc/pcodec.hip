@@ -15,11 +15,13 @@
 //                    batch payload: no two-phase publish
 //   k_vd_flags+scan  representatives ranked in batch order → the new ids and arena offsets; the totals go to the host,
 //                    which refuses a batch that does not fit (nothing has been written to the dictionary by then)
-//   k_vd_commit      every miss reads its representative's id; the representative writes entries[id], its arena bytes
+//   k_vd_commit      every miss reads its representative's id (rank → vd_next_id, vdict_sweep.h: the ids a sweep gave
+//                    back first, then high + 1, …); the representative writes entries[id], its arena bytes
 //                    and CAS(0 → tag | id) into the main table. The insert reads no other entry, and no lookup runs in
 //                    this launch: kernel boundaries do all publishing, nothing on the device waits for another lane.
 #include "engine.h"
 #include "vdict_dev.h"
+#include "vdict_sweep.h"
 
 namespace sg {
 
@@ -312,7 +314,7 @@ __global__ void __launch_bounds__(256) k_vd_commit(VDictArgs v) {
     if (j >= v.m || v.ids[j] != 0) return;  // ids[j] is read and written by this lane alone
     const uint32_t rep = v.dedupe[v.slot_of[j]];
     const uint64_t sc = v.scan[rep];
-    const uint64_t id = v.count + 1 + (sc >> 32);
+    const uint64_t id = vd_next_id(sc >> 32, v.free_ids, v.n_free, v.high);  // a swept id again while they last
     v.ids[j] = id;
     if (rep != (uint32_t)j) return;
     const VDesc d = v.desc[j];
@@ -347,13 +349,15 @@ __global__ void __launch_bounds__(256) k_vd_bytes(const VEntry* e, const uint32_
     for (uint32_t k = 0; k < x.len; ++k) o[k] = x.len <= 8 ? (uint8_t)(x.data >> (8 * k)) : arena[x.data + k];
 }
 
-// sg_vdict_grow: the zeroed main table of the grown dictionary filled from its entries, one lane per id. The hash
+// sg_vdict_grow: the zeroed main table of the grown dictionary filled from its entries, one lane per id in [1, high]
+// (a swept id's tombstone is skipped). The hash
 // is computed again from the entry's payload with the lookup's function (vd_lookup_store), so the slot an id lands
 // on is the one every later lookup of its value probes from.
 __global__ void __launch_bounds__(256) k_vd_rehash(VDictArgs v) {
     const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
-    if (id > v.count) return;
+    if (id > v.high) return;
     const VEntry e = v.entries[id];
+    if (e.type == kVdTombType) return;  // a swept id: in no table until a batch takes it again
     const bool inl = e.len <= 8;
     const uint64_t h = value_hash((e.len << 8) | e.type, inl ? e.data : 0, inl ? v.arena : v.arena + e.data);
     const uint64_t val = (h & 0xFFFFFFFF00000000ull) | id;
@@ -414,8 +418,8 @@ hipError_t launch_vd_commit(const VDictArgs& v, hipStream_t stream) {
 }
 
 hipError_t launch_vd_rehash(const VDictArgs& v, hipStream_t stream) {
-    if (v.count == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_vd_rehash, dim3(grid_for(v.count, 256)), dim3(256), 0, stream, v);
+    if (v.high == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_vd_rehash, dim3(grid_for(v.high, 256)), dim3(256), 0, stream, v);
     return hipGetLastError();
 }
 

@@ -49,7 +49,8 @@ EXPORTS = ["sg_create", "sg_destroy", "sg_last_error", "sg_set_namespaces", "sg_
            "sg_node_server_log_enable", "sg_node_server_log", "sg_node_local_block_log_enable",
            "sg_node_local_block_log",
            "sg_gateway_load_rules", "sg_gateway_converted", "sg_gateway_param_rule_count", "sg_gateway_parse_batch",
-           "sg_gateway_load_apis", "sg_gateway_verdict_ids", "sg_gateway_set_item_fields", "sg_gateway_expand_batch"]
+           "sg_gateway_load_apis", "sg_gateway_verdict_ids", "sg_gateway_set_item_fields", "sg_gateway_expand_batch",
+           "sg_vdict_sweep"]
 
 _lib = None
 
@@ -225,6 +226,7 @@ def load_library():
         "sg_cparam_resize": (C.c_int, [vp, C.c_int32]),
         "sg_cparam_table_used": (C.c_int, [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "sg_vdict_grow": (C.c_int, [vp, C.c_int32, u64]),
+        "sg_vdict_sweep": (C.c_int, [vp, vp, u64, C.POINTER(abi.sg_vdict_sweep_stats)]),
         "sg_param_sweep": (C.c_int, [vp, C.c_int64, C.POINTER(abi.sg_sweep_stats)]),
         "sg_cparam_sweep": (C.c_int, [vp, C.c_int64, C.POINTER(abi.sg_sweep_stats)]),
         "sg_node_param_sweep": (C.c_int, [vp, C.c_int64, C.POINTER(abi.sg_sweep_stats)]),
@@ -755,6 +757,16 @@ class FlowEngine:
     def vdict_grow(self, capacity_log2: int, arena_bytes: int):
         """A larger dictionary in place (both sizes at least the current ones): every id stays what it is."""
         self._check(self._L.sg_vdict_grow(self.h, capacity_log2, arena_bytes))
+
+    def vdict_sweep(self, keep_ids=None):
+        """Gives back every id that no value table, thread count, hot item, unfetched log row or gateway rule of this
+        engine names and that is not in keep_ids (the ids the caller holds outside the engine: a decoded or parsed batch
+        not decided yet, hot-item ids not loaded yet). Ids are not renumbered; a later intern hands the freed ones out
+        again, lowest first. Returns sg_vdict_sweep_stats as a dict."""
+        keep = np.ascontiguousarray(keep_ids if keep_ids is not None else [], dtype=np.uint64)
+        st = abi.sg_vdict_sweep_stats()
+        self._check(self._L.sg_vdict_sweep(self.h, abi.ptr(keep) if len(keep) else None, len(keep), C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in abi.sg_vdict_sweep_stats._fields_}
 
     def codec_decode_param(self, payload_ptr: int, offsets_ptr: int, ts_ptr: int, n: int, req_ptr: int,
                            values_ptr: int, values_cap: int, xid_ptr: int, kind_ptr: int, stream_ptr: int = 0) -> int:
